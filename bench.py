@@ -1,11 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- random-policy rollout throughput of the batched Foundation env.step().
 
-    python bench.py --gpus N --steps K --warmup W [--workload C1|C2|C2v|P2|C3|C4|C4x|C5] [--no-workloads]
+    python bench.py --gpus N --steps K --warmup W [--workload C1|C2|C2v|P2|C3|C4|C4x|C5] [--dump-outputs DIR]
+    python bench.py --gpus 1 --full [--no-workloads] [--no-cpu-baseline]
 
-Workloads = BASELINE.json configs[0..4].  The default run (1 GPU, C2) is the headline line and
-ALSO times every other BASELINE configuration in a short window of the same invocation (`"workloads": {C1, C3, C4, C4x,
-C5: {value, ms_per_step, roofline}}`), so that all of them are measured under the caller's clock.  C2 is the
+Workloads = BASELINE.json configs[0..4].  A plain run times the headline workload only: set
+up, warm up, K timed steps, the result line.  `--full` (1 GPU, C2) ALSO times every other BASELINE configuration in a
+short window of the same invocation (`"workloads": {C1, C3, C4, C4x, C5: {value, ms_per_step, roofline}}`), so that
+all of them are measured under the caller's clock, plus the CPU baselines below.  C2 is the
 configuration the metric is quoted on: layout_from_file/simple_wood_and_stone, 25x25 quadrant layout, 4 mobile agents + planner, Build +
 ContinuousDoubleAuction(max_num_orders 5) + Gather + PeriodicBracketTax (model_wrapper, us-federal, period 100),
 starting_agent_coin 10, episode_length 1000, 4096 replicas PER GPU (weak scaling), uniform random actions from a
@@ -29,8 +31,13 @@ line the driver parses, <= 4 KB (compact_line) -- the contract fields plus the n
                 same command (-> hbm_traffic_frac, issue_frac, valu_frac = the share of all VALU pipe time the
                 kernel's vector instructions fill, and `bound` derived from them); C5: the box's own pure-store roof
                 measured live
-  cpu_baseline  the UNMODIFIED reference env.step (oracle/_ref, kind "reference") on this host's cores, P pinned
-                processes timed concurrently on a bounded window; `cpu_port` = the C restatement (oracle/) beside it
+  cpu_baseline  (--full) the UNMODIFIED reference env.step (oracle/_ref, kind "reference") on this host's cores, P
+                pinned processes timed concurrently on a bounded window; `cpu_port` = the C restatement (oracle/) beside it
+
+`--dump-outputs DIR` writes what the last timed step handed its caller -- the observations, rewards and done flags of
+the batch -- as DIR/<tensor name>.npy (float32; float64 for f64 and 32-bit integer tensors), a fixed seeded sample of
+the replicas where the whole batch would exceed 64 MB.  Same arguments, same inputs: two builds compare output for
+output.
 """
 import argparse
 import json
@@ -544,9 +551,9 @@ def store_roof_gbs(device, nbytes=4 << 30):
     return best
 
 
-def run_workload(wl, args, steps, warmup, rank, local_rank, world, device):
+def run_workload(wl, args, steps, warmup, rank, local_rank, world, device, dump_dir=None):
     """One workload's rollout on this rank: environment, de-phasing prologue, warm-up, the timed window.  Returns the
-    JSON fields of the workload (rank 0) or None."""
+    JSON fields of the workload (rank 0) or None.  dump_dir: rank 0 writes what the last timed step computed there."""
     import gc
 
     import torch
@@ -674,6 +681,8 @@ def run_workload(wl, args, steps, warmup, rank, local_rank, world, device):
         allt = [torch.zeros_like(tt) for _ in range(world)]
         torch.distributed.all_gather(allt, tt)
         per_rank_launch_ms = [float(x.item()) for x in allt]
+    if rank == 0 and dump_dir:
+        dump_outputs(caller_outputs(be.tensors), dump_dir)
     if rank == 0:
         lay = layout_bytes_per_env_step(be, wl)
         units = (n + 1) if wl.startswith("C4") else n  # C4's per-unit figure counts the planner
@@ -703,7 +712,7 @@ def run_workload(wl, args, steps, warmup, rank, local_rank, world, device):
         # a wave64 vector instruction keeps its SIMD's 16-lane pipe for 4 clocks: the share of all VALU pipe time the
         # kernel's vector instructions fill
         valu_frac = (4.0 * valu_insts / (N_SIMDS * SM_CLOCK_HZ * avg_ms * 1e-3)) if (valu_insts and E == W["envs"]) else None
-        store_roof = store_roof_gbs(device) if wl == "C5" else None
+        store_roof = store_roof_gbs(device) if wl == "C5" and args.full else None
         store_frac = None
         if store_roof and traffic:
             store_frac = (traffic / (avg_ms * 1e-3) / 1e9) / store_roof
@@ -911,6 +920,40 @@ SIDE_CPU_BASELINES = ("C1", "C3", "C4x", "C4xu", "C5")  # (C2v, P2 and C4 step t
 SIDE_CPU_SECONDS = 3.0
 
 
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000  # (the dump may take 64 MB: the .npy headers and a margin below that)
+DUMP_SAMPLE_SEED = 0
+
+
+def caller_outputs(tensors):
+    """What a step hands its caller (base_env.step: obs, rew, done): the backend's observation, reward and done
+    tensors, all of them batched over the replicas along dimension 0."""
+    return {k: v for k, v in sorted(tensors.items())
+            if k.startswith(("obs_a_", "obs_p_")) or k in ("rewards_a", "rewards_p", "done")}
+
+
+def dump_outputs(tensors, out_dir, limit=DUMP_LIMIT_BYTES):
+    """tensors (name -> device tensor [E, ...]) -> out_dir/<name>.npy in float32 (float64 for f64 and 32-bit integer
+    tensors, which float32 would round).  Past `limit` bytes in all, the same seeded sample of replicas of every tensor,
+    in replica order.  Returns the replica indices written."""
+    import numpy as np
+    import torch
+
+    def out_dtype(t):
+        return np.float64 if t.dtype in (torch.float64, torch.int32, torch.int64) else np.float32
+
+    E = next(iter(tensors.values())).shape[0]
+    per_replica = sum(np.dtype(out_dtype(t)).itemsize * (t.numel() // E) for t in tensors.values())
+    keep = max(1, min(E, limit // max(1, per_replica)))
+    rows = np.arange(E) if keep == E else np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(E, keep, replace=False))
+    idx = torch.from_numpy(rows)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in tensors.items():
+        assert t.shape[0] == E, (name, tuple(t.shape))
+        a = t.index_select(0, idx.to(t.device)).cpu().numpy().astype(out_dtype(t))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return rows
+
+
 def emit(out, detail_file):
     """Full result -> bench_detail.json + an earlier stdout line; the compact line LAST."""
     detail = json.dumps(out)
@@ -928,7 +971,7 @@ SIDE_WORKLOADS = [("C1", 200, 20), ("C1f", 200, 20), ("C2v", 200, 20), ("C2f", 2
                   ("C4xu", 100, 10), ("C2@16384", 100, 20), ("C2@65536", 60, 10), ("C5", 60, 20)]
 
 
-def run_policy_workload(args, steps, warmup, device):
+def run_policy_workload(args, steps, warmup, device, dump_dir=None):
     """C2pi: BASELINE configs[1] with a POLICY in the loop: a small torch MLP on `obs_a_flat` /
     `obs_p_flat`, `action_mask` applied to its logits, Gumbel-max sampling, actions written on the device, aie_step --
     issued call by call from Python (eager) and as one captured hipGraph replay per step
@@ -973,6 +1016,8 @@ def run_policy_workload(args, steps, warmup, device):
 
     dt_e, iss_e, gpu_e = timed(lambda: gs.eager(1))
     dt_g, iss_g, gpu_g = timed(lambda: gs.replay(1))
+    if dump_dir:  # (the policy-only replay below writes actions only)
+        dump_outputs(caller_outputs(be.tensors), dump_dir)
     dt_p, _, gpu_p = timed(g_pol.replay)
     assert int(be.tensors["error_flags"].abs().sum()) == 0  # the policy honoured the masks
     out = {
@@ -1033,13 +1078,20 @@ def main():
     ap.add_argument("--workload", choices=sorted(WORKLOADS) + ["C2pi"], default="C2",
                     help="C2pi: configs[1] with a torch MLP policy in the loop, alone (one JSON line; no CPU legs)")
     ap.add_argument("--envs-per-gpu", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the other BASELINE configurations in short windows (1-GPU C2), the CPU "
+                         "baselines, C5's live store roof (a plain run times the headline workload only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (observations, rewards, done; float32 / float64 .npy, "
+                         "<= 64 MB: a fixed seeded sample of the replicas beyond that) to DIR")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--cpu-baseline-episodes", type=int, default=0,
                     help="time the headline's cpu_baseline on SURVEY 8(d)'s protocol -- 1 warm-up + N timed WHOLE episodes incl. "
                          "resets per process -- instead of the default free-running 10 s window (3 = the survey's figure; takes "
                          "~4 x episode_length x 0.5 ms per process)")
     ap.add_argument("--no-workloads", action="store_true",
-                    help="headline workload only (default: a 1-GPU C2 run also times C1, C3, C4, C4x, C5 in short windows)")
+                    help="--full without the other workloads (with it, a 1-GPU C2 run also times C1, C3, C4, C4x, C5 in "
+                         "short windows)")
     ap.add_argument("--generic-kernel", action="store_true",
                     help="development: time the generic step kernel instead of the configuration's compile-time instance")
     ap.add_argument("--no-stagger", action="store_true", help="keep all replicas in lock-step (round-1 behaviour)")
@@ -1098,11 +1150,12 @@ def main():
     device = torch.device("cuda", local_rank)
 
     if args.workload == "C2pi":  # the policy-in-the-loop side workload on its own (profiling)
-        r = run_policy_workload(args, min(args.steps, 400), min(args.warmup, 40), device)
+        r = run_policy_workload(args, args.steps, args.warmup, device, dump_dir=args.dump_outputs)
         r.pop("compact", None)
         print(json.dumps(r), flush=True)
         return
-    out = run_workload(args.workload, args, args.steps, args.warmup, rank, local_rank, world, device)
+    out = run_workload(args.workload, args, args.steps, args.warmup, rank, local_rank, world, device,
+                       dump_dir=args.dump_outputs)
     if world > 1:
         # every rank empties its native stdio buffers (RCCL's version banner) before rank 0 prints the JSON line, so
         # that nothing follows it on the job's stdout
@@ -1119,7 +1172,7 @@ def main():
         cfg = out.pop("_cfg")
         wl = args.workload
         side_cfgs = {}
-        if world == 1 and wl == "C2" and not args.no_workloads and not args.envs_per_gpu:
+        if args.full and world == 1 and wl == "C2" and not args.no_workloads and not args.envs_per_gpu:
             # every BASELINE configuration under the same clock, in the same invocation (short windows)
             sides = {}
             for swl, ssteps, swarm in SIDE_WORKLOADS:
@@ -1145,7 +1198,7 @@ def main():
                         alts = {mb: c5_fresh_process(1, piece_mb=mb) for mb in (16, 64, 128)}
                         sides["C5"]["fresh_process_other_piece_sizes"] = alts
             out["workloads"] = sides
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             ref = None
             try:
                 ref = cpu_reference_baseline(cfg, episodes=args.cpu_baseline_episodes)

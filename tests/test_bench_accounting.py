@@ -1,5 +1,5 @@
 """bench.py's roofline accounting reads committed rocprofv3 summaries (profiles/): the lookups must hold for every
-workload the default run times, with and without a summary, and the derived fractions must follow from the numbers in
+workload `bench.py --full` times, with and without a summary, and the derived fractions must follow from the numbers in
 the files.  CPU only (no kernel is launched)."""
 import glob
 import json
@@ -151,3 +151,35 @@ def test_summary_provenance_flags_summaries_of_other_kernels(tmp_path, monkeypat
     assert bench.summary_provenance("profiles/r06_c2_pmc.json") == (6, False)
     assert bench.summary_provenance("profiles/r06_c3_pmc.json") == (6, True)
     assert bench.summary_provenance(None) == (None, None)
+
+
+def test_dump_outputs_writes_a_seeded_replica_sample_within_the_limit(tmp_path):
+    """bench.dump_outputs: the caller's arrays of the last step as float32 / float64 .npy; past the byte limit the same
+    seeded sample of replicas in every file, in replica order, and the same sample from run to run."""
+    import numpy as np
+    import torch
+
+    E = 1000
+    g = torch.Generator().manual_seed(3)
+    tensors = {"obs_a_world-map": torch.randint(0, 7, (E, 4, 11, 11), dtype=torch.uint8, generator=g),
+               "obs_p_flat": torch.rand((E, 9), generator=g),
+               "rewards_a": torch.rand((E, 4), generator=g).double(),
+               "done": torch.randint(0, 2, (E,), dtype=torch.uint8, generator=g),
+               "coin": torch.randint(0, 1 << 30, (E, 4), dtype=torch.int32, generator=g),
+               "state_not_an_output": torch.zeros((E, 3))}
+    picked = bench.caller_outputs(tensors)
+    assert set(picked) == {"obs_a_world-map", "obs_p_flat", "rewards_a", "done"}
+    rows = bench.dump_outputs(tensors, str(tmp_path / "all"))
+    assert np.array_equal(rows, np.arange(E))
+    for name, t in tensors.items():
+        a = np.load(tmp_path / "all" / (name + ".npy"))
+        assert a.dtype == (np.float64 if t.dtype in (torch.float64, torch.int32) else np.float32)
+        assert np.array_equal(a, t.numpy().astype(a.dtype))
+    limit = 100_000
+    rows = bench.dump_outputs(tensors, str(tmp_path / "a"), limit=limit)
+    assert 0 < len(rows) < E and np.all(np.diff(rows) > 0)
+    assert sum(os.path.getsize(p) - 128 for p in glob.glob(str(tmp_path / "a" / "*.npy"))) <= limit
+    assert np.array_equal(rows, bench.dump_outputs(tensors, str(tmp_path / "b"), limit=limit))
+    for name, t in tensors.items():
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert np.array_equal(a, b) and np.array_equal(a, t.numpy()[rows].astype(a.dtype))
