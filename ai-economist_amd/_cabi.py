@@ -201,7 +201,7 @@ def bind(lib):
     lib.aie_set_reward_log.restype = C.c_int
     lib.aie_set_reward_log.argtypes = [vp, vp, C.c_int32]
     lib.aie_step_range.restype = C.c_int
-    lib.aie_step_range.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp]
+    lib.aie_step_range.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
     lib.aie_step_sample_next.restype = C.c_int
     lib.aie_step_sample_next.argtypes = [vp, vp, vp, C.c_uint64, C.c_int64, vp, vp, vp]
     lib.aie_step_sample_next_masked.restype = C.c_int

@@ -564,7 +564,7 @@ int aie_step(aie_env* env, const int32_t* d_actions_a, const int32_t* d_actions_
 }
 
 int aie_step_range(aie_env* env, const int32_t* d_actions_a, const int32_t* d_actions_p, int32_t comp_lo, int32_t comp_hi,
-                   int32_t phases, void* stream) {
+                   int32_t phases, void* stream, const uint8_t* d_env_mask) {
   if (!env) return AIE_E_INVALID;
   const aie_params& P = env->P;
   if (P.c.scenario != AIE_SCN_GTB || P.saez_stride || (P.ev_replicas > 0 && env->log_active)) {
@@ -584,6 +584,7 @@ int aie_step_range(aie_env* env, const int32_t* d_actions_a, const int32_t* d_ac
   next.comp_lo = comp_lo;
   next.comp_hi = comp_hi;
   next.phase = phases | 32;  // (never 0 = "a whole step": bit 5 marks a ranged launch)
+  next.mask = d_env_mask;
   hipLaunchKernelGGL(aie_step_kernel_log, dim3((unsigned)P.E), dim3(2 * AIE_NT), env->lds, static_cast<hipStream_t>(stream),
                      env->d_params, env->arena, d_actions_a, d_actions_p, next);
   if ((phases & AIE_STEP_TAIL) && P.auto_reset)  // as behind aie_step: the replicas this step finished restart right behind it

@@ -2726,6 +2726,9 @@ struct NextActions {  // aie_step_sample_next: where and how to sample the next 
   // masks, rewards, done), AIE_STEP_OBSERVE (observations and masks of the state as it stands, nothing else); phase == 0:
   // a whole step.  Honoured by the full-featured kernel only (aie_step_kernel_log); everybody else steps whole steps.
   int32_t comp_lo, comp_hi, phase;
+  // aie_step_range: the replicas the launch touches (uint8 [E], nonzero = yes), nullptr = all of them -- a masked reset's
+  // follow-up launches leave the replicas it did not reset alone.  The full-featured kernel only, like the ranges above.
+  const uint8_t* mask;
 };
 // This step's slot of the reward log: the replica's slot counter selects it and moves on (`writer`: the one lane that
 // stores the counter back; every lane of the wave calls this with the same fields).
@@ -2782,6 +2785,7 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
   static_assert(NW == 2, "a replica is a workgroup of two wavefronts");
   const int e_blk = replica_of_block((int)blockIdx.x, next.E);  // (the replica count travels as a kernel argument)
   if (next.e_hi > 0 && (e_blk < next.e_lo || e_blk >= next.e_hi)) return;  // (uniform over the workgroup, ahead of every barrier)
+  if (LOG && next.mask && !next.mask[e_blk]) return;  // (likewise: a replica outside an aie_step_range mask, as in reset_body)
   const bool FAST = rng_fast(P);  // the counter stream (include/aie.h: AIE_RNG_FAST); compile-time in the instances
   const int tid0 = (int)(threadIdx.x & (AIE_NT - 1));
   uint8_t* grec = arena + (int64_t)e_blk * P.rec_bytes;  // (a_records == 0: the records open the arena, aie_layout.h)
@@ -2880,11 +2884,13 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
     __syncthreads();  // (4) components done; the generator's position (and, after a refill that twisted, its state in HBM) is final
     // flat observation vectors and rewards: neither looks at the map
     if (w0_tail_prio) __builtin_amdgcn_s_setprio(2);
+    if (RETAX && P.has_tax) {  // (ahead of the flat observations: the marginal rate they show is measured from the snapshot)
+      if (c.tid < P.n) R_F64(c, o_tax_last_coin)[c.tid] = R_F64(c, o_inv_coin)[c.tid] + R_F64(c, o_esc_coin)[c.tid];
+      AIE_WSYNC();
+    }
     if (!(skip & 8) && (TAIL || OBSERVE)) write_flat_observations(c, arena);
     if (TRACE && R.dev_trace && c.tid == 0) R.dev_trace[12 * blockIdx.x + 10] = wall_clock64();
     if (!REW_ON_W1 && TAIL) step_rewards_and_done(c, arena, next, skip);
-    if (RETAX && P.has_tax && c.tid < P.n)
-      R_F64(c, o_tax_last_coin)[c.tid] = R_F64(c, o_inv_coin)[c.tid] + R_F64(c, o_esc_coin)[c.tid];
     if (REBASE) {  // (reset_body's last lines: the metrics of the state as the host's reset hooks left it)
       AIE_WSYNC();
       current_metrics(c);

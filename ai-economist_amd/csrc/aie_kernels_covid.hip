@@ -512,6 +512,10 @@ __device__ __forceinline__ void cv_step_body(const aie_params* __restrict__ para
     // with the batch's: a replica that sat a launch out writes the same reward-log slot as its peers, and
     // draws with the same index, once it is reset.
     if (s == 0 && (next.a || next.p)) *reinterpret_cast<int32_t*>(rec + P.o_sample_t) = sample_t + 1;
+    // and the reward-log slot it claimed holds this launch's row, not one of an earlier pass over the slots: no rewards,
+    // `done` as the step that ended the episode left it
+    if (rew_log)
+      for (int i = s; i < n + 2; i += AIE_NT) rew_log[(int64_t)e * (n + 2) + i] = i == n + 1 ? 1.0f : 0.0f;
     return;
   }
   // Every load of the replica's record is issued here, before anything waits: a replica is one wavefront whose whole

@@ -35,6 +35,9 @@ class DeviceBackend:
 
         self.lib = _native.lib(dev=os.environ.get("AIE_DEV_LIB") == "1")
         self.cfg = cfg
+        # names of the environment's host components (foundation.BatchedComponent), set by the environment: whole-step
+        # calls and auto-reset are refused then (_refuse_with_host_components)
+        self.host_components = ()
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device(device)
@@ -192,19 +195,30 @@ class DeviceBackend:
         m = self._ptr(env_mask, torch.uint8, "env_mask", self.E)
         self._check(self.lib.aie_reset(self.handle, m, self._stream()))
 
+    def _refuse_with_host_components(self, what):
+        """An environment with host components (foundation.BatchedComponent) marks its backend: a whole step or an
+        auto-reset inside the step would run without the components' hooks, so those calls raise instead."""
+        if self.host_components:
+            raise NotImplementedError(
+                "%s: this environment has host components (%s); a whole-step launch or an auto-reset would skip their "
+                "hooks -- step and reset it through env.step / env.reset" % (what, ", ".join(self.host_components)))
+
     def step(self, actions_a=None, actions_p=None):
+        self._refuse_with_host_components("Backend.step")
         torch = _torch()
         a = self._ptr(actions_a, torch.int32, "actions_a", self.act_a_numel)
         p = self._ptr(actions_p, torch.int32, "actions_p", self.act_p_numel)
         self._check(self.lib.aie_step(self.handle, a, p, self._stream()))
 
-    def step_range(self, actions_a, actions_p, comp_lo, comp_hi, phases):
+    def step_range(self, actions_a, actions_p, comp_lo, comp_hi, phases, mask=None):
         """aie_step_range: the built-in components [comp_lo, comp_hi) and the named parts of a step (_cabi.STEP_HEAD /
-        STEP_TAIL / STEP_OBSERVE) -- what foundation.BatchedComponent hooks run between."""
+        STEP_TAIL / STEP_OBSERVE) -- what foundation.BatchedComponent hooks run between.  mask: uint8 [E] device tensor
+        of the replicas the launch touches (a masked reset's follow-up launches), None = all."""
         torch = _torch()
         a = self._ptr(actions_a, torch.int32, "actions_a", self.act_a_numel)
         p = self._ptr(actions_p, torch.int32, "actions_p", self.act_p_numel)
-        self._check(self.lib.aie_step_range(self.handle, a, p, int(comp_lo), int(comp_hi), int(phases), self._stream()))
+        m = self._ptr(mask, torch.uint8, "env_mask", self.E)
+        self._check(self.lib.aie_step_range(self.handle, a, p, int(comp_lo), int(comp_hi), int(phases), self._stream(), m))
 
     def set_reward_log(self, n_slots):
         """Allocates a reward log of `n_slots` step slots, f32 [n_slots, E, n_agents + 2] = (agent rewards,
@@ -228,6 +242,8 @@ class DeviceBackend:
     def set_auto_reset(self, on=True):
         """Replicas restart inside / right behind the step that ends their episode (include/aie.h:
         aie_set_auto_reset): `done` and the rewards are the terminal step's, state and observations the new episode's."""
+        if on:
+            self._refuse_with_host_components("Backend.set_auto_reset(True)")
         self._check(self.lib.aie_set_auto_reset(self.handle, 1 if on else 0))
 
     def set_dense_log_active(self, on=True):
@@ -239,6 +255,7 @@ class DeviceBackend:
         """One launch: step with (actions_a, actions_p) and fill the action buffers of `next_slot`
         with the uniform random policy's next draw (same values as sample_random_actions; masked=True, COVID only:
         as sample_masked_actions, from the masks this step writes)."""
+        self._refuse_with_host_components("Backend.step_sample_next")
         torch = _torch()
         a = self._ptr(actions_a, torch.int32, "actions_a", self.act_a_numel)
         p = self._ptr(actions_p, torch.int32, "actions_p", self.act_p_numel)

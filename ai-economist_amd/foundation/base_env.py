@@ -252,6 +252,7 @@ class BaseEnvironment:
 
             self._backend = DeviceBackend(self.build_config(), self.layout_planes(),
                                           device=self._device)
+            self._backend.host_components = tuple(comp.name for _, comp in self._host_components)
             self.upload_model_constants(self._backend)
             if self._pending_seed is not None:
                 self._backend.seed(self._pending_seed + self.env_offset)
@@ -442,13 +443,13 @@ class BaseEnvironment:
             for n_before, comp in self._host_components:
                 ahead = tax_at is None or n_before <= tax_at  # listed ahead of the tax component (or there is none)
                 if not ahead and edited_ahead and not retaken:
-                    self.backend.step_range(None, None, 0, 0, _cabi.STEP_OBSERVE | _cabi.STEP_RETAX)
+                    self.backend.step_range(None, None, 0, 0, _cabi.STEP_OBSERVE | _cabi.STEP_RETAX, mask=env_mask)
                     retaken = True
                 e = bool(comp.additional_reset_steps(self.backend.tensors, env_mask))
                 edited_ahead, edited_behind = edited_ahead or (e and ahead), edited_behind or (e and not ahead)
             if edited_ahead or edited_behind:  # the reset kernel's observations no longer show the state: rewrite them
                 retax = _cabi.STEP_RETAX if (tax_at is not None and edited_ahead and not retaken) else 0
-                self.backend.step_range(None, None, 0, 0, _cabi.STEP_OBSERVE | _cabi.STEP_REBASE | retax)
+                self.backend.step_range(None, None, 0, 0, _cabi.STEP_OBSERVE | _cabi.STEP_REBASE | retax, mask=env_mask)
         if log_replica_resets:
             self._dense_log = {"world": [], "states": [], "actions": [], "rewards": []}
             if self._dense_log_this_episode:

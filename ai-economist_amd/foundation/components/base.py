@@ -77,10 +77,12 @@ class BatchedComponent(BaseComponent):
     that key with flatten_observations=False), keep its own torch state, take part in reset (`additional_reset_steps`).
     What it cannot (yet): own an ACTION subspace (`get_n_actions` must return None: the action layout and the masks are
     the kernels'), draw from a replica's NumPy stream, run in the COVID / one-step-economy scenarios, be captured in a
-    hipGraph with data-dependent Python control flow.  Cost: one extra launch per stretch, the full-featured kernel
-    instead of the configuration's instance, and whatever the hook's torch code costs -- an extension point, not the hot
-    path.  tests/test_batched_component.py holds a toy component against the same component added to the live
-    reference."""
+    hipGraph (rollout.GraphedStep) or restart inside the step (auto-reset): both would run steps and resets without its
+    hooks, so on an environment with host components GraphedStep, the backend's whole-step calls (`step`,
+    `step_sample_next`) and `set_auto_reset(True)` raise; step and reset it with env.step / env.reset.  Cost: one extra
+    launch per stretch, the full-featured kernel instead of the configuration's instance, and whatever the hook's torch
+    code costs -- an extension point, not the hot path.  tests/test_batched_component.py holds toy components against
+    the same components added to the live reference."""
     comp_id = 0  # no device kernel
     is_batched_host_component = True
 

@@ -27,6 +27,10 @@ class GraphedStep:
         unroll: environment steps per replay."""
         import torch
 
+        if env.backend.host_components:  # (its captured aie_step and auto-reset would skip their hooks)
+            raise NotImplementedError("GraphedStep: the environment has host components (%s), which run between launches "
+                                      "issued from Python: step it with env.step / env.reset"
+                                      % ", ".join(env.backend.host_components))
         self.torch = torch
         self.env, self.be = env, env.backend
         self.policy = policy

@@ -438,7 +438,10 @@ int aie_step_sample_next_masked(aie_env* env, const int32_t* d_actions_a, const 
  * aie_step(a, p) == aie_step_range(a, p, 0, n_components, HEAD | TAIL).  Every call takes the same action buffers.
  * Between two calls of a step the caller may edit state tensors; the TAIL call rewrites all observations.  Always the
  * full-featured kernel (no compile-time / run-time instance).  Gather-trade-build scenarios; AIE_E_UNSUPPORTED elsewhere,
- * with tax_model "saez" and while a dense-log replica records. */
+ * with tax_model "saez" and while a dense-log replica records.
+ * d_env_mask: the replicas the call touches (uint8 [n_envs], nonzero = yes), NULL = every replica -- the convention of
+ * aie_reset.  The OBSERVE calls behind a masked aie_reset pass its mask: the replicas it did not reset keep their
+ * observations, reward baseline and tax snapshot.  The calls of a step pass NULL. */
 #define AIE_STEP_HEAD 1
 #define AIE_STEP_TAIL 2
 #define AIE_STEP_OBSERVE 4
@@ -446,7 +449,7 @@ int aie_step_sample_next_masked(aie_env* env, const int32_t* d_actions_a, const 
 #define AIE_STEP_RETAX 16 /* with OBSERVE: PeriodicBracketTax's reset-time snapshot of the agents' coin (redistribution.py:1106-1110) taken
                            * again -- a host component listed AHEAD of the tax component edited coin in its reset hook */
 int aie_step_range(aie_env* env, const int32_t* d_actions_a, const int32_t* d_actions_p, int32_t comp_lo, int32_t comp_hi,
-                   int32_t phases, void* stream);
+                   int32_t phases, void* stream, const uint8_t* d_env_mask);
 
 /* Reward log for learners on another device: every following aie_step / aie_step_sample_next ALSO
  * writes replica e's (agent rewards [n_agents], planner reward, done as 0/1) as n_agents + 2 floats to

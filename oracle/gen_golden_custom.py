@@ -89,6 +89,37 @@ def register_reference_toys():
         def generate_masks(self, completions=0):
             return {}
 
+    @component_registry.add
+    class ResetGrant(BaseComponent):
+        """Grants every agent `amount` coin at the reset: listed ahead of PeriodicBracketTax, a grant beyond the first
+        bracket cutoffs shows whether the tax's reset-time snapshot of coin (redistribution.py:1106-1110) sees it."""
+        name = "ResetGrant"
+        required_entities = ["Coin"]
+        agent_subclasses = ["BasicMobileAgent"]
+
+        def __init__(self, *args, amount=50.0, **kwargs):
+            super().__init__(*args, **kwargs)
+            self.amount = float(amount)
+
+        def get_n_actions(self, agent_cls_name):
+            return None
+
+        def get_additional_state_fields(self, agent_cls_name):
+            return {}
+
+        def additional_reset_steps(self):
+            for agent in self.world.agents:
+                agent.state["inventory"]["Coin"] += self.amount
+
+        def component_step(self):
+            pass
+
+        def generate_observations(self):
+            return {}
+
+        def generate_masks(self, completions=0):
+            return {}
+
     return foundation
 
 
@@ -113,6 +144,23 @@ CASES = {
                              GTB[3]],
                  starting_agent_coin=10, env_layout_file="quadrant_25x25_20each_30clump.txt"),
         seed=9, t_steps=40, obs_steps=[0, 1, 5, 6, 40]),
+    # a reset grant ahead of a fixed-rate tax (60 coin: the third bracket of the scaled 2018 schedule), nothing behind
+    # it: the last reset launch retakes the tax's coin snapshot, and the reset observations' marginal rates must see it
+    "custom_grant_ahead_of_tax_4ag": dict(
+        cfg=dict(scenario_name="layout_from_file/simple_wood_and_stone", n_agents=4, world_size=[25, 25], episode_length=20,
+                 components=[["ResetGrant", {"amount": 60.0}], GTB[0], GTB[1], GTB[2],
+                             ["PeriodicBracketTax", {"tax_model": "us-federal-single-filer-2018-scaled", "period": 8}]],
+                 starting_agent_coin=10, resource_regen_prob=0.05, env_layout_file="uniform_25x25_25each_65clump.txt"),
+        seed=31, t_steps=30, obs_steps=[0, 1, 8, 9, 16, 20, 21, 28, 30]),
+    # a grant ahead of the tax and LaborRelief's +2 coin behind it: the snapshot is retaken between the two hooks
+    # (the two-launch reset), so it holds the grant and not the relief
+    "custom_grant_around_tax_5ag": dict(
+        cfg=dict(scenario_name="layout_from_file/simple_wood_and_stone", n_agents=5, world_size=[25, 25], episode_length=18,
+                 components=[["ResetGrant", {"amount": 120.0}], GTB[0], GTB[1], GTB[2],
+                             ["PeriodicBracketTax", {"tax_model": "us-federal-single-filer-2018-scaled", "period": 8}],
+                             ["LaborRelief", {"cap": 3.0}]],
+                 starting_agent_coin=10, resource_regen_prob=0.05, env_layout_file="uniform_25x25_25each_65clump.txt"),
+        seed=37, t_steps=28, obs_steps=[0, 1, 8, 9, 16, 18, 19, 26, 28]),
 }
 
 

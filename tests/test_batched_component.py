@@ -1,6 +1,6 @@
 """User-registered components: the reference's component registry is open (F/base/base_component.py:378,
 F/base/registrar.py:48-66); here a component of the user's subclasses foundation.BatchedComponent -- its dynamics run as
-torch code on the batch's state tensors between launches of aie_step_range.  Two toy components, written once against the
+torch code on the batch's state tensors between launches of aie_step_range.  Three toy components, written once against the
 reference's BaseComponent (oracle/gen_golden_custom.py, which produced tests/golden/custom_*.npz by running the UNMODIFIED
 reference with them registered) and once as BatchedComponents (below), listed first, last, between and next to the
 built-in components: state after every step, rewards, done, resets, and the flat observation vectors with the components'
@@ -70,6 +70,27 @@ def register_toys():
 
         def component_step(self, t):
             t["labor"].clamp_(max=self.cap)
+
+    @foundation.components.add
+    class ResetGrant(foundation.BatchedComponent):
+        name = "ResetGrant"
+        required_entities = ["Coin"]
+        agent_subclasses = ["BasicMobileAgent"]
+
+        def __init__(self, *args, amount=50.0, **kwargs):
+            super().__init__(*args, **kwargs)
+            self.amount = float(amount)
+
+        def additional_reset_steps(self, t, env_mask=None):
+            coin = t["inv_coin"]
+            if env_mask is None:
+                coin += self.amount
+            else:
+                coin += self.amount * env_mask.to(coin.dtype)[:, None]
+            return True
+
+        def component_step(self, t):
+            pass
 
 
 def _replica(be, e):
@@ -214,3 +235,194 @@ def test_host_component_with_actions_or_in_other_scenarios_is_refused():
     foundation.components.add(Plain)
     with pytest.raises(NotImplementedError, match="BatchedComponent"):
         foundation.make_env_instance("layout_from_file/simple_wood_and_stone", components=[("PlainToy", {})], **base)
+
+
+# ---- masked resets with host components: twins instead of the oracle ----
+#
+# Three kinds of environment built from one configuration and seed step with the same actions: S resets the replicas of a
+# mask at step k, F resets all of them at step k, N does not reset.  The kernels are the same and every replica draws
+# from its own stream, so from then on the rows of S outside the mask must equal N's and the rows inside it F's, bit
+# for bit: state tensors, rewards, done and the observations env.reset / env.step return (the host components' keys
+# included).  A reset that reached past its mask -- the follow-up launches that rewrite the observations after the
+# components' reset hooks, or retake the tax's coin snapshot -- shows up as a difference in the rows it should not touch.
+
+TWIN_E = 7  # odd: "alternate rows" is not half of the batch
+
+
+def _twin_masks(E):
+    return {"first": [0], "last": [E - 1], "alternate": list(range(0, E, 2)),
+            "all_but_one": [e for e in range(E) if e != E // 2], "none": [], "all": list(range(E))}
+
+
+def _tax_period(cfg):
+    for name, kw in cfg["components"]:
+        if name == "PeriodicBracketTax":
+            return int(kw.get("period", 100))
+    return None
+
+
+def _twin_cases():
+    out = []
+    for name in custom_golden_names():
+        cfg = load_golden(name)["cfg"]
+        T, P = int(cfg["episode_length"]), _tax_period(cfg)
+        if P is not None and P < T:
+            ks = [("mid_period", P + P // 2 if P + P // 2 < T else P // 2), ("tax_day", P)]
+        else:  # no tax day inside an episode: the middle of the episode and its first step
+            ks = [("mid_period", T // 2), ("first_step", 1)]
+        for what, k in ks:
+            out.append(pytest.param(name, "numpy", k, id="%s-k%d-%s" % (name, k, what)))
+    # generated layouts drawn ahead of their resets (rng_mode "fast")
+    out.append(pytest.param("custom_first_and_last_5ag", "fast", 7, id="custom_first_and_last_5ag-fast-k7"))
+    return out
+
+
+def _leaves(prefix, d, E, out):
+    import torch
+
+    for k, v in d.items():
+        if isinstance(v, dict):
+            _leaves("%s/%s" % (prefix, k), v, E, out)
+        elif isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == E:
+            out["%s/%s" % (prefix, k)] = v.detach().cpu().clone()
+
+
+def _twin_snapshot(env, obs):
+    """Every tensor of the backend whose leading dimension is the replica, and every observation (CPU copies)."""
+    be = env.backend
+    out = {}
+    for k, t in be.tensors.items():
+        if t.dim() >= 1 and t.shape[0] == be.E:
+            out[k] = t.detach().cpu().clone()
+    _leaves("obs", obs, be.E, out)
+    return out
+
+
+def _twin_assert(got, want, rows, where):
+    import torch
+
+    if not rows:
+        return
+    assert sorted(got) == sorted(want), where
+    idx = torch.as_tensor(rows, dtype=torch.long)
+    bad = [k for k in want if not torch.equal(got[k][idx], want[k][idx])]
+    assert not bad, "%s: rows %s differ in %s" % (where, rows, bad)
+
+
+def _twin_actions(env, rng, E):
+    import torch
+
+    n = env.n_agents
+    sub_a, sub_p = env.action_subspace_names()
+    be = env.backend
+    wa = be.act_a_numel // (E * n)
+    if wa == 1:
+        a = rng.randint(0, 1 + sum(k for _, k in sub_a), size=(E, n, 1))
+    else:
+        a = np.stack([rng.randint(0, k, size=(E, n)) for _, k in sub_a], axis=-1)
+    act = {"a": torch.as_tensor(a.astype(np.int32), device=be.device)}
+    if sub_p:  # (a planner without actions -- a fixed-rate tax -- takes the NO-OPs env.step fills in)
+        p = np.stack([rng.randint(0, k, size=E) for _, k in sub_p], axis=-1)
+        act["p"] = torch.as_tensor(p.astype(np.int32), device=be.device)
+    return act
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,rng_mode,k", _twin_cases())
+def test_masked_reset_with_host_components_touches_only_its_rows(name, rng_mode, k):
+    import torch
+
+    register_toys()
+    cfg = load_golden(name)["cfg"]
+    E = TWIN_E
+    masks = _twin_masks(E)
+    extra = dict(rng_mode=rng_mode) if rng_mode != "numpy" else {}
+
+    def build():
+        env = make_env(cfg, n_envs=E, device="cuda:0", **extra)
+        env.seed(17)
+        return env
+
+    S = {m: build() for m in masks}
+    N, F = build(), build()
+    envs = list(S.values()) + [N, F]
+    snap = {id(env): _twin_snapshot(env, env.reset()) for env in envs}
+    T, P = int(cfg["episode_length"]), _tax_period(cfg)
+    steps = k + max(2 * P if P is not None and P < T else 0, T - k) + 2  # two tax periods and past N's episode end
+    rng = np.random.RandomState(1000 + k)
+
+    def check(where):
+        for m, rows in masks.items():
+            s = snap[id(S[m])]
+            _twin_assert(s, snap[id(N)], [e for e in range(E) if e not in rows], "%s: mask %s, outside vs no reset" % (where, m))
+            _twin_assert(s, snap[id(F)], rows, "%s: mask %s, inside vs full reset" % (where, m))
+
+    for t in range(1, steps + 1):
+        act = _twin_actions(N, rng, E)
+        for env in envs:
+            obs, _, _, _ = env.step(act)
+            snap[id(env)] = _twin_snapshot(env, obs)
+        check("%s step %d" % (name, t))
+        if t == k:
+            for m, rows in masks.items():
+                mask = torch.zeros(E, dtype=torch.uint8, device="cuda:0")
+                mask[rows] = 1
+                snap[id(S[m])] = _twin_snapshot(S[m], S[m].reset(mask))
+            snap[id(F)] = _twin_snapshot(F, F.reset())
+            check("%s reset at step %d" % (name, t))
+            continue
+        # replicas whose episode ended restart (a rollout's env.reset(done)); the rows of S follow their twins' clocks
+        reset_any = False
+        for env in envs:
+            done = env.backend.tensors["done"]
+            if bool(done.any().item()):
+                snap[id(env)] = _twin_snapshot(env, env.reset(done))
+                reset_any = True
+        if reset_any:
+            check("%s reset(done) after step %d" % (name, t))
+    assert int(N.backend.tensors["completions"].min()) >= 1  # the untouched rows crossed an episode end
+
+
+@pytest.mark.gpu
+def test_paths_that_skip_the_host_hooks_are_refused():
+    """The backend's whole-step calls (aie_step, aie_step_sample_next), auto-reset inside the step and GraphedStep (which
+    captures aie_step and turns auto-reset on) would run steps and resets without the host components' hooks: on an
+    environment with host components they raise before they launch anything; env.step and env.reset keep working."""
+    import torch
+
+    from ai_economist_amd.rollout import GraphedStep
+
+    register_toys()
+    env = make_env(load_golden("custom_grant_ahead_of_tax_4ag")["cfg"], n_envs=4, device="cuda:0")
+    env.seed(3)
+    env.reset()
+    be = env.backend
+    a, p = be.sample_random_actions(5, 0, slot=0)
+    torch.cuda.synchronize()
+    before = {k: t.clone() for k, t in be.tensors.items()}
+    with pytest.raises(NotImplementedError, match="ResetGrant"):
+        GraphedStep(env, lambda tensors, act_a, act_p: None, auto_reset=False)
+    with pytest.raises(NotImplementedError, match="ResetGrant"):
+        GraphedStep(env, lambda tensors, act_a, act_p: None)
+    with pytest.raises(NotImplementedError, match="host components"):
+        be.step(a, p)
+    with pytest.raises(NotImplementedError, match="host components"):
+        be.step_sample_next(a, p, 5, 0, next_slot=1)
+    with pytest.raises(NotImplementedError, match="host components"):
+        be.set_auto_reset(True)
+    be.set_auto_reset(False)  # (off is what such an environment runs with)
+    torch.cuda.synchronize()
+    for k, t in be.tensors.items():
+        assert torch.equal(t, before[k]), "a refused call changed %s" % k
+    obs, rew, done, _ = env.step({"a": a, "p": p})
+    assert int(be.tensors["timestep"].min()) == 1 and int(be.tensors["timestep"].max()) == 1
+    env.reset()
+    assert int(be.tensors["timestep"].max()) == 0
+    # an environment without host components keeps every path
+    plain = make_env(dict(load_golden("custom_grant_ahead_of_tax_4ag")["cfg"], components=[["Build", {}], ["Gather", {}]]),
+                     n_envs=4, device="cuda:0")
+    plain.seed(3)
+    plain.reset()
+    plain.backend.step(None, None)
+    plain.backend.set_auto_reset(True)
+    plain.backend.set_auto_reset(False)

@@ -87,7 +87,7 @@ def test_host_registry_and_kwargs_validation():
     builtin = ["Build", "ContinuousDoubleAuction", "ControlUSStateOpenCloseStatus", "FederalGovernmentSubsidy", "Gather",
                "PeriodicBracketTax", "SimpleLabor", "VaccinationCampaign", "WealthRedistribution"]
     # (the registry is open: tests/test_batched_component.py adds its toy components to it in the same process)
-    toys = {"ActingToy", "CoinSubsidy", "LaborRelief", "PlainToy"}
+    toys = {"ActingToy", "CoinSubsidy", "LaborRelief", "PlainToy", "ResetGrant"}
     assert [c for c in foundation.components.entries if c not in toys] == builtin
     assert foundation.scenarios.entries == ["CovidAndEconomySimulation", "layout_from_file/simple_wood_and_stone",
                                             "multi_zone/simple_wood_and_stone", "one-step-economy",

@@ -843,7 +843,8 @@ def test_covid_replica_past_its_episode_end_keeps_its_call_counters_with_the_bat
     env = make_env(cfg, n_envs=E, device="cuda:0")
     env.reset()
     be = env.backend
-    be.set_reward_log(4)
+    log = be.set_reward_log(4)
+    log.fill_(-7.0)  # (whatever a slot held before: each row a step claims has to be written)
     T = int(env.episode_length)
     # put replicas 0..2 at the end of their episode (the state a rollout reaches after T steps), leave 3..5 at the start
     be.tensors["timestep"][:3] = T
@@ -855,6 +856,16 @@ def test_covid_replica_past_its_episode_end_keeps_its_call_counters_with_the_bat
     assert be.tensors["timestep"].cpu().tolist() == [T] * 3 + [3] * 3  # the first three sat the launches out ...
     assert be.tensors["rew_log_slot"].cpu().tolist() == [3] * E      # ... and kept their slot
     assert be.tensors["sample_t"].cpu().tolist() == [int(be.tensors["sample_t"][5])] * E  # ... and their draw index
+    # ... and wrote the rows they claimed: no rewards, `done` as the step that ended their episode left it
+    n = be.n
+    rows = log.cpu().numpy()
+    assert np.all(rows[:3, :3, :n + 1] == 0.0), rows[:3, :3, :n + 1]
+    assert np.all(rows[:3, :3, n + 1] == 1.0), rows[:3, :3, n + 1]
+    # the live replicas' rows of the last step are the step's rewards and done
+    assert np.array_equal(rows[2, 3:, :n], be.tensors["rewards_a"][3:].cpu().numpy())
+    assert np.array_equal(rows[2, 3:, n], be.tensors["rewards_p"][3:].cpu().numpy())
+    assert np.array_equal(rows[2, 3:, n + 1], be.tensors["done"][3:].cpu().numpy().astype(np.float32))
+    assert np.all(rows[3] == -7.0)  # (no step claimed the fourth slot)
 
 
 def test_captured_step_follows_a_later_set_reward_log_call():
