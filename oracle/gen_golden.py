@@ -283,6 +283,27 @@ CASES = {
                  num_wood_and_stone_zones=2, starting_stone_coverage=0.08, starting_wood_coverage=0.08),
         seed=29, t_steps=120, obs_steps=[0, 1, 60, 61, 120],
         action_kw=dict(p_move=0.6, p_build=0.3, p_trade=0.0)),
+    # non-square worlds (H != W: a swapped row / column is invisible on every other fixture's map): window counts of
+    # source blocks for the regeneration, an observation window wider than the map is high; 2 episodes => 2 layouts
+    "uniform_12x37_halfwidth_4ag": dict(
+        cfg=dict(scenario_name="uniform/simple_wood_and_stone", n_agents=4, world_size=[12, 37], episode_length=50,
+                 components=GTB[:3] + [["PeriodicBracketTax", {"period": 15}]], starting_agent_coin=10,
+                 starting_stone_coverage=0.08, starting_wood_coverage=0.08, mobile_agent_observation_range=7,
+                 wood_regen_halfwidth=2, wood_regen_weight=0.5, stone_regen_halfwidth=1, stone_regen_weight=0.4),
+        seed=43, t_steps=100, obs_steps=[0, 1, 50, 51, 100]),
+    "quadrant_20x30_4ag": dict(
+        cfg=dict(scenario_name="quadrant/simple_wood_and_stone", n_agents=4, world_size=[20, 30], episode_length=50,
+                 components=GTB, starting_agent_coin=10, starting_stone_coverage=0.10, starting_wood_coverage=0.10,
+                 wood_regen_weight=0.3, stone_regen_weight=0.3),
+        seed=47, t_steps=100, obs_steps=[0, 1, 50, 51, 100]),
+    # 33 agents x 2 orders: a 66-slot order book (just past the 64 a non-log kernel holds), gini's sorted-sum branch
+    "quadrant40_33ag_book66": dict(
+        cfg=dict(scenario_name="layout_from_file/simple_wood_and_stone", n_agents=33, world_size=[40, 40],
+                 episode_length=30,
+                 components=[["Build", {}], ["ContinuousDoubleAuction", {"max_num_orders": 2, "order_duration": 25}],
+                             ["Gather", {}], ["PeriodicBracketTax", {"period": 8}]],
+                 starting_agent_coin=40, resource_regen_prob=0.08, env_layout_file="quadrant_40x40_50each.txt"),
+        seed=53, t_steps=45, obs_steps=[0, 1, 30, 31, 45], action_kw=dict(p_move=0.4, p_build=0.05, p_trade=0.5)),
 }
 
 

@@ -300,6 +300,98 @@ C1_INSTANCE = dict(scenario_name="uniform/simple_wood_and_stone", n_agents=4, wo
                    starting_wood_coverage=0.10)
 
 
+# ---- shapes where a step kernel typically breaks: non-square worlds, the 4096-cell limit of device-drawn layouts, order
+# books on either side of 64 slots, gini's branches.  The same configurations are pinned against the live reference
+# (tests/test_oracle_vs_reference_shapes.py) and run on the device against the oracle (tests/test_gpu_shapes.py). ----
+def _shape_cfg(kind, h, w, **kw):
+    cfg = dict(scenario_name=kind + "/simple_wood_and_stone", n_agents=4, world_size=[h, w], episode_length=20,
+               components=[["Build", {}], ["ContinuousDoubleAuction", {"max_num_orders": 4, "order_duration": 15}],
+                           ["Gather", {}], ["PeriodicBracketTax", {"period": 7}]],
+               starting_agent_coin=5, starting_wood_coverage=0.06, starting_stone_coverage=0.06,
+               wood_regen_weight=0.3, stone_regen_weight=0.3)
+    cfg.update(kw)
+    return cfg
+
+
+SHAPE_CASES = {
+    # d x d window counts of source blocks (regen_halfwidth > 0, max_health 1); observation windows wider than the short
+    # side only
+    "uniform_12x37_source_counts": _shape_cfg("uniform", 12, 37, wood_regen_halfwidth=2, stone_regen_halfwidth=1,
+                                              mobile_agent_observation_range=7),
+    "uniform_37x12_source_counts": _shape_cfg("uniform", 37, 12, wood_regen_halfwidth=2, stone_regen_halfwidth=2,
+                                              mobile_agent_observation_range=7, planner_gets_spatial_info=False),
+    # max_health > 1 beside a window: the general convolution (regen_general) of max(map, source) per step
+    "uniform_12x37_general_regen": _shape_cfg("uniform", 12, 37, wood_regen_halfwidth=2, stone_max_health=3,
+                                              stone_regen_halfwidth=1, mobile_agent_observation_range=3),
+    "uniform_37x12_general_regen": _shape_cfg("uniform", 37, 12, wood_max_health=2, wood_regen_halfwidth=3,
+                                              stone_regen_halfwidth=0),
+    # 3840 cells: device-drawn layouts with rows wider than a wavefront, > 128 source blocks (row-by-row regeneration)
+    "uniform_24x160": _shape_cfg("uniform", 24, 160, starting_wood_coverage=0.05, starting_stone_coverage=0.05,
+                                 mobile_agent_observation_range=15),
+    "uniform_160x24": _shape_cfg("uniform", 160, 24, starting_wood_coverage=0.05, starting_stone_coverage=0.05,
+                                 mobile_agent_observation_range=12, planner_gets_spatial_info=False),
+    "quadrant_20x30": _shape_cfg("quadrant", 20, 30, starting_wood_coverage=0.1, starting_stone_coverage=0.1),
+    "quadrant_30x20": _shape_cfg("quadrant", 30, 20, starting_wood_coverage=0.1, starting_stone_coverage=0.1,
+                                 wood_regen_halfwidth=1, stone_regen_halfwidth=2, mobile_agent_observation_range=11),
+    "multi_zone_15x28": _shape_cfg("multi_zone", 15, 28, num_partitions_row=3, num_partitions_col=4, num_wood_zones=3,
+                                   num_stone_zones=3, num_wood_and_stone_zones=2, starting_wood_coverage=0.08,
+                                   starting_stone_coverage=0.08),
+    # the device layout path's 4096-cell limit from both sides (64 x 65 is drawn on the host)
+    "uniform_65x63": _shape_cfg("uniform", 65, 63, n_agents=3, starting_wood_coverage=0.02, starting_stone_coverage=0.02,
+                                components=[["Build", {}], ["Gather", {}]]),
+    "uniform_64x64": _shape_cfg("uniform", 64, 64, n_agents=3, starting_wood_coverage=0.02, starting_stone_coverage=0.02,
+                                components=[["Build", {}], ["Gather", {}]], wood_regen_halfwidth=1),
+    "uniform_64x65": _shape_cfg("uniform", 64, 65, n_agents=3, starting_wood_coverage=0.02, starting_stone_coverage=0.02,
+                                components=[["Build", {}], ["Gather", {}]]),
+    # the whole map as the agents' observation, with and without the planner's spatial view
+    "full_observability_18x11": _shape_cfg("uniform", 18, 11, full_observability=True),
+    "full_observability_11x18_planner_blind": _shape_cfg("quadrant", 11, 18, full_observability=True,
+                                                         planner_gets_spatial_info=False),
+}
+
+# quadrant/ puts a water row at width // 2 and a water column at height // 2 (the reference's own swap): shapes with
+# width // 2 >= height or height // 2 >= width raise IndexError in the reference's constructor, and in the product's
+REFUSED_SHAPES = {"quadrant_9x30": _shape_cfg("quadrant", 9, 30), "quadrant_30x9": _shape_cfg("quadrant", 30, 9)}
+
+
+def _agents_cfg(n, orders, **kw):
+    cfg = dict(scenario_name="layout_from_file/simple_wood_and_stone", n_agents=n, world_size=[40, 40], episode_length=18,
+               starting_agent_coin=60, resource_regen_prob=0.08, env_layout_file="quadrant_40x40_50each.txt",
+               components=[["Build", {}], ["ContinuousDoubleAuction", {"max_num_orders": orders, "order_duration": 15}],
+                           ["Gather", {}], ["PeriodicBracketTax", {"period": 6}]])
+    cfg.update(kw)
+    return cfg
+
+
+# name -> configuration with all four components on the 40 x 40 quadrant file; the order book holds
+# M = n_agents * max_num_orders slots: M <= 64 steps in a register-resident or LDS book of the non-log kernels, M > 64 on
+# aie_step_kernel_log
+AGENT_CASES = {
+    "n16_book64": _agents_cfg(16, 4),
+    "n21_book63": _agents_cfg(21, 3),
+    "n32_book64": _agents_cfg(32, 2),
+    "n61_book61": _agents_cfg(61, 1),
+    "n62_book62": _agents_cfg(62, 1),
+    "n13_book65": _agents_cfg(13, 5),
+    "n33_book66": _agents_cfg(33, 2),
+    # gini: pairwise sums below 30 agents, the sorted cumulative sum from 30 on
+    "n29_coin_eq": _agents_cfg(29, 2, planner_reward_type="coin_eq_times_productivity", mixing_weight_gini_vs_coin=0.3),
+    "n30_coin_eq": _agents_cfg(30, 2, planner_reward_type="coin_eq_times_productivity"),
+    "n31_coin_eq": _agents_cfg(31, 2, planner_reward_type="coin_eq_times_productivity", mixing_weight_gini_vs_coin=0.6),
+    "n30_inv_income_coin": _agents_cfg(30, 2, planner_reward_type="inv_income_weighted_coin_endowments",
+                                       mixing_weight_gini_vs_coin=0.3),
+    "n31_inv_income_utility": _agents_cfg(31, 2, planner_reward_type="inv_income_weighted_utility"),
+}
+
+
+def book_slots(cfg):
+    """M = n_agents * max_num_orders: the order book's slots per side (0 without an auction)."""
+    for name, kw in cfg["components"]:
+        if name == "ContinuousDoubleAuction":  # (max_num_orders defaults to order_duration, 50)
+            return cfg["n_agents"] * int(kw.get("max_num_orders") or kw.get("order_duration", 50))
+    return 0
+
+
 def _components_with(base, **per_component):
     return [[name, dict(kw, **per_component.get(name, {}))] for name, kw in base]
 

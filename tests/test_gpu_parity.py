@@ -8,8 +8,8 @@ import os
 import numpy as np
 import pytest
 
-from helpers import (F64_FIELDS, FAMILY_CASES, INT_FIELDS, compare_state, dev_library, golden_names, load_golden, make_env,
-                     state_from_golden)
+from helpers import (AGENT_CASES, F64_FIELDS, FAMILY_CASES, INT_FIELDS, SHAPE_CASES, compare_state, dev_library, golden_names,
+                     load_golden, make_env, state_from_golden)
 
 pytestmark = pytest.mark.gpu
 
@@ -1174,6 +1174,9 @@ JIT_CASES = {
                                        components=[["SimpleLabor", {"skills": [1.0 + 0.05 * i for i in range(37)]}],
                                                    ["PeriodicBracketTax", {"bracket_spacing": "us-federal", "period": 1,
                                                                            "tax_model": "model_wrapper"}]]),
+    # H != W folded in at compile time (H, W and their magic divisors), and 61 agents with a 61-slot book
+    "non_square_12x37": dict(SHAPE_CASES["uniform_12x37_source_counts"], episode_length=50),
+    "agents_61_book61": dict(AGENT_CASES["n61_book61"], episode_length=50),
 }
 
 
