@@ -79,12 +79,20 @@ __device__ __forceinline__ uint8_t* cv_ring_at(const aie_params& P, uint8_t* rec
   return rec + P.o_cv_ring + (tau & 31) * 64 + s;
 }
 
+// The step's only transcendental calls, named so that the development hook aie_test_glibc_math (fn 3-5) evaluates the
+// very functions the kernel calls: the device library's float32 powf (CRRA) and float64 exp / log (softplus).  Not
+// libm's: tests/test_covid_numerics.py measures their error against a correctly rounded reference and sizes the
+// bands the rewards are held to from that.
+__device__ __forceinline__ float cv_powf(float x, float y) { return powf(x, y); }
+__device__ __forceinline__ double cv_exp(double x) { return exp(x); }
+__device__ __forceinline__ double cv_log(double x) { return log(x); }
+
 // crra_nonlinearity (covid19_env.py:1056-1078), float32 like the reference's arrays
 __device__ __forceinline__ float cv_crra(float x, float eta) {
   float ax = 365.0f * x;
   ax = fminf(fmaxf(ax, 0.1f), 3.0f);
   const float ome = 1.0f - eta;
-  const float num = powf(ax, ome) - 1.0f;
+  const float num = cv_powf(ax, ome) - 1.0f;
   return (1.0f + num / ome) / 365.0f;
 }
 __device__ __forceinline__ float cv_minmax(float x, float lo, float hi) { return (x - lo) / (hi - lo + 1e-10f); }
@@ -668,7 +676,7 @@ __device__ __forceinline__ void cv_step_body(const aie_params* __restrict__ para
     for (int f = 0; f < F; ++f) {
       x = x + K[(AIE_CV_K_CONV_W0 + f) * 64 + sl] * acc[f];
     }
-    const double excess = x <= 20.0 ? log(1.0 + exp(x)) : x;  // softplus :1358-1372
+    const double excess = x <= 20.0 ? cv_log(1.0 + cv_exp(x)) : x;  // softplus :1358-1372
     unemployed = ((excess + K[AIE_CV_K_UNEMP_BIAS * 64 + sl]) * pop) / 100.0;
     if (V.replay_data) unemployed = rws[5 * rw_plane + (int64_t)t * 64 + sl];  // :815-818 (not clamped)
     a.U = (float)unemployed;

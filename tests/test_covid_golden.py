@@ -3,8 +3,8 @@ fixtures the live reference produced (oracle/gen_golden_covid.py), and against e
 batched random rollouts.
 
 Tolerances (the reference's own CPU<->CUDA tolerance lives in un-vendored WarpDrive, so these
-are ours): the SIR state is float32 arithmetic with IEEE basic operations only and is compared
-at rtol 1e-6 (HIP vs oracle: a few float32 ulps would show a misplaced cast); unemployment /
+are ours): the SIR state is float32 arithmetic with IEEE basic operations only: rtol 1e-6 against the
+reference's fixtures, bit for bit HIP vs oracle (EXACT_VS_ORACLE, with the agents' health index); unemployment /
 productivity go through exp/log and a reordered float64 filter sum: rtol 1e-5; rewards are
 min-max normalised differences of nearly equal float32 numbers: atol 1e-5 (the 1e-5 of BASELINE's north star;
 measured at 8192 replicas x 64 days: max 2.4e-6, tests/test_gpu_full_size.py)."""
@@ -20,6 +20,21 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
 STATE_TOL = dict(susceptible=1e-6, infected=1e-6, recovered=1e-6, deaths=1e-6, vaccinated=1e-6,
                  unemployed=1e-5, postsubsidy_productivity=1e-5, subsidy=1e-6)
+# HIP vs the oracle: the SIR state and the agents' health index are basic operations in the reference's order and
+# dtypes, so bit for bit (tests/test_covid_numerics.py measures it over rollouts, eta and config edges, injected states)
+EXACT_VS_ORACLE = ("susceptible", "infected", "recovered", "deaths", "vaccinated", "health_index")
+
+
+def assert_state_vs_oracle(t, st, where):
+    """HIP's state tensors against the oracle's state dict: EXACT_VS_ORACLE bit for bit, the rest at STATE_TOL."""
+    for k in EXACT_VS_ORACLE:
+        got = t[k].cpu().numpy()
+        assert got.dtype == np.float32 and np.array_equal(got, np.asarray(st[k], np.float32)), \
+            "%s %s: not the oracle's bit for bit (max |diff| %.3g)" % (
+                where, k, float(np.abs(got.astype(np.float64) - np.asarray(st[k], np.float64)).max()))
+    for k, tol in STATE_TOL.items():
+        np.testing.assert_allclose(t[k].cpu().numpy().astype(np.float64), st[k], rtol=tol, atol=1e-3,
+                                   err_msg="%s %s" % (where, k))
 
 
 def model_for(cfg):
@@ -167,9 +182,7 @@ def test_covid_hip_matches_oracle_on_batched_rollouts(name, E, T, recurrence):
 
     def compare(where):
         st = o.state()
-        for k, tol in STATE_TOL.items():
-            np.testing.assert_allclose(t[k].cpu().numpy().astype(np.float64), st[k], rtol=tol, atol=1e-3,
-                                       err_msg="%s %s" % (where, k))
+        assert_state_vs_oracle(t, st, where)
         assert np.array_equal(t["cooldown_until"].cpu().numpy(), st["cooldown_until"]), where
         assert np.array_equal(t["subsidy_level"].cpu().numpy(), st["subsidy_level"]), where
         for k in ("health_index", "economic_index", "planner_health_economic_index", "sum_unemployed",
@@ -223,9 +236,7 @@ def test_covid_hip_matches_oracle_on_random_configs(seed, recurrence):
 
     def compare(where):
         st = o.state()
-        for k, tol in STATE_TOL.items():
-            np.testing.assert_allclose(t[k].cpu().numpy().astype(np.float64), st[k], rtol=tol, atol=1e-3,
-                                       err_msg="%s %s %r" % (where, k, cfg))
+        assert_state_vs_oracle(t, st, "%s %r" % (where, cfg))
         assert np.array_equal(t["cooldown_until"].cpu().numpy(), st["cooldown_until"]), where
         for k, v in o.observe().items():
             np.testing.assert_allclose(t[k].cpu().numpy().reshape(v.shape), v, rtol=1e-5, atol=1e-6,
@@ -272,9 +283,7 @@ def test_covid_hip_follows_the_reference_consistency_procedure(recurrence):
 
     def compare(where):
         st = o.state()
-        for k, tol in STATE_TOL.items():
-            np.testing.assert_allclose(t[k].cpu().numpy().astype(np.float64), st[k], rtol=tol, atol=1e-3,
-                                       err_msg="%s %s" % (where, k))
+        assert_state_vs_oracle(t, st, where)
         assert np.array_equal(t["cooldown_until"].cpu().numpy(), st["cooldown_until"]), where
         assert np.array_equal(t["subsidy_level"].cpu().numpy(), st["subsidy_level"]), where
         for k, v in o.observe().items():

@@ -1,0 +1,487 @@
+"""The COVID-19 step (csrc/aie_kernels_covid.hip) against a correctly rounded restatement of the reference's day
+(tests/covid_exact.py), at the configurations and states where float pipelines go wrong.
+
+- The SIR state, the agents' health index, stringency, cool-down, subsidy level, masks and `done` use IEEE basic
+  operations only (DESIGN, "COVID-19 (C4)", Numerics): HIP must equal the oracle bit for bit.
+- Unemployment, productivity, the economic indices and the rewards go through exp / log / powf and a float64 filter
+  sum: they must lie inside covid_exact's band -- the recipe over +-K ulps of each transcendental result (K measured
+  below against mpmath, on the device through the -DAIE_DEV hook and on the host for NumPy) plus the sum bound.
+
+CPU tests: the band holds the live reference's recorded days (tests/golden/c4_covid_*.npz) and the oracle's rollouts.
+GPU tests: rollouts, eta near 1 and at 1, reward normalisation and health-priority edges, and injected states
+(S = 0, S below the day's vaccines, I = 0, no new deaths, a negative planner CRRA input, extreme filter responses).
+Run with -s for the measured ulps, band widths and deviations."""
+import ctypes
+import os
+import sys
+
+import numpy as np
+import pytest
+
+import covid_exact as cx
+from helpers import ROOT, covid_golden_names, load_covid_golden, random_covid_config
+
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+
+F32 = np.float32
+ETAS = [0.0, 0.9, 0.99, 0.999, 1.0, 1.001, 1.01, 1.1, 2.0, 5.0]
+
+
+def _model(cfg):
+    from test_covid_golden import model_for
+
+    return model_for(cfg)
+
+
+def _powf_inputs(n, seed):
+    """float32 CRRA inputs: ax in [0.1, 3] (log-uniform and uniform), the clamp ends and their neighbours, 1."""
+    rng = np.random.RandomState(seed)
+    a = np.concatenate([np.exp(rng.uniform(np.log(0.1), np.log(3.0), n // 2)), rng.uniform(0.1, 3.0, n - n // 2)])
+    edges = np.array([0.1, 3.0, 1.0, 0.5, 2.0], F32)
+    edges = np.concatenate([edges, np.nextafter(edges, F32(0)), np.nextafter(edges, F32(4))])
+    return np.clip(np.concatenate([a.astype(F32), edges]), F32(0.1), F32(3.0)).astype(F32)
+
+
+def _softplus_inputs(n, seed):
+    """float64 softplus arguments over the range the filter sums reach (|x| <~ 35) and exp's underflow."""
+    rng = np.random.RandomState(seed)
+    x = np.concatenate([rng.uniform(-40.0, 21.0, n - n // 8), rng.uniform(-745.0, -40.0, n // 8),
+                        np.array([0.0, 20.0, -36.8, -37.5, 1e-300, -1e-300])])
+    return x
+
+
+def _ulp_report(got, want):
+    d = cx.ulp_distance(got, want)
+    return int(d.max()), float((d > 0).mean())
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the host side: what the reference (and the oracle) computes with
+# ------------------------------------------------------------------------------------------------------------------
+def test_host_numpy_math_ulp_error():
+    """NumPy's float32 `**` (the reference's CRRA) and float64 exp / log (its softplus) against mpmath, over the
+    tests' input ranges: within covid_exact's K.  Measured on the development host: powf 1 ulp max (eta 0 .. 5),
+    exp / log 1 ulp max -- NumPy may use its own SIMD code on other CPUs, hence the margin of K_POWF = 2."""
+    ax = _powf_inputs(4000, 1)
+    worst = 0
+    for eta in ETAS:
+        ome = F32(1) - F32(eta)
+        with np.errstate(all="ignore"):
+            got = ax ** ome
+        w, frac = _ulp_report(got, cx.cr_powf(ax, ome))
+        print("host numpy powf eta=%g: max %d ulp, %.3f inexact" % (eta, w, frac))
+        worst = max(worst, w)
+    assert worst <= cx.K_POWF
+    x = _softplus_inputs(6000, 2)
+    e = np.exp(x)
+    w_exp, _ = _ulp_report(e, cx.cr_exp(x))
+    w_log, _ = _ulp_report(np.log(1 + e), cx.cr_log(1 + e))
+    print("host numpy exp: max %d ulp, log: max %d ulp" % (w_exp, w_log))
+    assert w_exp <= cx.K_EXP and w_log <= cx.K_LOG
+
+
+def _golden_day_inputs(g, m, c, t):
+    """covid_exact.day's inputs for day t of a fixture, from the recorded states and stringency levels."""
+    n = len(m["us_state_population"])
+    pre = {k: g["state_" + k][t - 1][None].astype(F32) for k in ("susceptible", "infected", "recovered", "vaccinated",
+                                                                   "deaths")}
+    bd = int(m["beta_delay"])
+    lvl = (np.asarray(m["policy_before_start"][t])[None] if t - bd < 0 else g["state_stringency_level"][t - bd][None])
+    hist = np.concatenate([np.asarray(m["stringency_level_history_0"], np.float64),
+                           g["state_stringency_level"][1:t + 1].astype(np.float64)])
+    window = hist[-(int(m["filter_len"]) + 1):][None]
+    vac = _vaccines(c, t, n)[None]
+    return pre, lvl.astype(np.int64), vac, window, g["state_subsidy"][t][None].astype(F32)
+
+
+def _vaccines(c, t, n, delivery_interval=None):
+    di = c["delivery_interval"] if delivery_interval is None else delivery_interval
+    if t >= c["time_when_vaccine_delivery_begins"] and t % di == 0:
+        return np.asarray(c["num_vaccines_per_delivery"], np.int64)
+    return np.zeros(n, np.int64)
+
+
+@pytest.mark.parametrize("name", covid_golden_names())
+def test_recipe_reproduces_the_reference_golden(name):
+    """Day by day, from the recorded previous day: the restated SIR equals the reference's state bit for bit, and the
+    reference's unemployment, productivity and rewards lie inside the bands (independently of the oracle)."""
+    g = load_covid_golden(name)
+    cfg = g["cfg"]
+    m, c = _model(cfg)
+    c = dict(c, delivery_interval=dict(cfg["components"])["VaccinationCampaign"]["delivery_interval"])
+    steps = len(g["actions_p"])
+    widths = {}
+    for t in range(1, steps + 1):
+        pre, lvl, vac, window, sub = _golden_day_inputs(g, m, c, t)
+        r = cx.day(m, pre, lvl, vac, window, sub)
+        for k in ("susceptible", "infected", "recovered", "vaccinated", "deaths"):
+            assert np.array_equal(r[k][0], g["state_" + k][t]), "%s day %d: %s" % (name, t, k)
+        u_band = tuple(np.asarray(b, np.float64).astype(F32) for b in r["unemployed"])
+        cx.inside(g["state_unemployed"][t], tuple(b[0] for b in u_band), "%s day %d unemployed" % (name, t))
+        cx.inside(g["state_postsubsidy_productivity"][t], tuple(b[0] for b in r["postsubsidy_productivity"]),
+                  "%s day %d productivity" % (name, t))
+        cx.inside(g["rewards"][t - 1][:-1], tuple(b[0] for b in r["rew_a"]), "%s day %d agent rewards" % (name, t))
+        cx.inside(g["rewards"][t - 1][-1], tuple(b[0] for b in r["rew_p"]), "%s day %d planner reward" % (name, t))
+        for k in ("rew_a", "rew_p"):
+            widths[k] = max(widths.get(k, 0.0), cx.width(r[k]))
+    print("%s: largest band widths %s" % (name, widths))
+
+
+def _oracle_inputs(o, reps):
+    """covid_exact.day's inputs for the day the oracle just stepped, for replicas `reps`."""
+    m, c, t = o.m, o.c, o.t
+    bd = int(m["beta_delay"])
+    n = o.n
+    pre = {"susceptible": o.S[reps, t - 1], "infected": o.I[reps, t - 1], "recovered": o.R[reps, t - 1],
+           "vaccinated": o.V[reps, t - 1], "deaths": o.D[reps, t - 1]}
+    if t - bd < 0:
+        lvl = np.repeat(np.asarray(m["policy_before_start"][t], np.int64)[None], len(reps), axis=0)
+    else:
+        lvl = o.stringency[reps, t - bd].astype(np.int64)
+    vac = np.repeat(_vaccines(c, t, n, o.delivery_interval)[None], len(reps), axis=0)
+    return pre, lvl, vac, o.slh[reps], o.subsidy[reps, t]
+
+
+def _as(band, dtype):
+    """A band in the dtype the result is stored in (the library's planner reward is float32, the reference's float64;
+    rounding is monotone, so the rounded ends bound the rounded result)."""
+    return tuple(np.asarray(b, np.float64).astype(dtype) for b in band)
+
+
+class BandTracker:
+    """Checks the oracle's or HIP's day against the bands of replicas `reps`, and keeps the running index sums' bands
+    (float32 sums of the daily lo / hi ends: float32 addition is monotone)."""
+
+    def __init__(self, reps, what):
+        self.reps = np.asarray(reps)
+        self.what = what
+        self.eidx = None
+        self.pidx = None
+        self.widths = {}
+        self.dev = {}
+
+    def day(self, o, got, where, sir_state=None):
+        pre, lvl, vac, window, sub = _oracle_inputs(o, self.reps)
+        r = cx.day(o.m, pre, lvl, vac, window, sub, sir_state=sir_state)
+        if sir_state is None:
+            for k, arr in (("susceptible", o.S), ("infected", o.I), ("recovered", o.R), ("vaccinated", o.V),
+                           ("deaths", o.D)):
+                assert np.array_equal(r[k], arr[self.reps, o.t]), "%s: oracle %s != recipe" % (where, k)
+        e = r["e"]
+        if self.eidx is None:
+            z = np.zeros(e[0].shape, F32)
+            self.eidx = [z, z.copy(), z.copy()]
+            self.pidx = [np.zeros(len(self.reps), F32) for _ in range(3)]
+        self.eidx = [a + b for a, b in zip(self.eidx, e)]
+        self.pidx = [a + np.asarray(b, F32) for a, b in zip(self.pidx, r["pe"])]
+        bands = {"unemployed": tuple(np.asarray(b, np.float64).astype(F32) for b in r["unemployed"]),
+                 "postsubsidy_productivity": r["postsubsidy_productivity"],
+                 "rewards_a": r["rew_a"], "rewards_p": _as(r["rew_p"], got["rewards_p"].dtype),
+                 "economic_index": tuple(self.eidx), "planner_economic_index": tuple(self.pidx)}
+        for k, band in bands.items():
+            x = got[k]
+            cx.inside(x, band, "%s %s %s" % (self.what, where, k))
+            self.widths[k] = max(self.widths.get(k, 0.0), cx.width(band))
+            with np.errstate(invalid="ignore"):
+                d = np.abs(np.asarray(x, np.float64) - np.asarray(band[0], np.float64))
+            d = d[~np.isnan(d)]
+            if d.size:
+                self.dev[k] = max(self.dev.get(k, 0.0), float(d.max()))
+        return r
+
+    def report(self):
+        for k in sorted(self.widths):
+            print("  %-26s band width %.3g  deviation from the correctly rounded value %.3g"
+                  % (k, self.widths[k], self.dev.get(k, 0.0)))
+
+
+def _oracle_got(o, reps):
+    return {"unemployed": o.U[reps, o.t], "postsubsidy_productivity": o.postprod[reps, o.t],
+            "rewards_a": o.rew_a[reps], "rewards_p": o.rew_p[reps], "economic_index": o.economic_index[reps],
+            "planner_economic_index": o.planner_index[reps, 1]}
+
+
+def _make_oracle(cfg, E):
+    from test_covid_golden import make_oracle
+
+    return make_oracle(cfg, n_envs=E)
+
+
+def _actions(rng, E, ns):
+    a = rng.randint(0, 11, size=(E, 51)).astype(np.int32)
+    a[rng.rand(E, 51) < 0.5] = 0
+    return a, rng.randint(0, ns + 1, size=(E,)).astype(np.int32)
+
+
+@pytest.mark.parametrize("seed", [0, 4, 6])
+def test_oracle_inside_bands_on_random_configs(seed):
+    cfg = random_covid_config(seed)
+    E = 4
+    o = _make_oracle(cfg, E)
+    o.reset()
+    rng = np.random.RandomState(seed)
+    ns = dict(cfg["components"])["FederalGovernmentSubsidy"]["num_subsidy_levels"]
+    tr = BandTracker(range(E), "oracle seed %d" % seed)
+    for k in range(1, cfg["episode_length"] + 1):
+        a, p = _actions(rng, E, ns)
+        o.step(a, p)
+        tr.day(o, _oracle_got(o, np.arange(E)), "day %d" % k)
+    print("oracle, random config %d (eta %g):" % (seed, cfg["economic_reward_crra_eta"]))
+    tr.report()
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# GPU
+# ------------------------------------------------------------------------------------------------------------------
+def _dev_math(fn, x, y=None):
+    import torch
+
+    from ai_economist_amd import _native
+
+    lib = _native.lib(dev=True)
+    vp = ctypes.c_void_p
+    lib.aie_test_glibc_math.restype = ctypes.c_int
+    lib.aie_test_glibc_math.argtypes = [ctypes.c_int, vp, vp, vp, ctypes.c_int64, vp]
+    tx = torch.as_tensor(np.asarray(x, np.float64), device="cuda:0")
+    ty = torch.as_tensor(np.asarray(y, np.float64), device="cuda:0") if y is not None else None
+    out = torch.empty_like(tx)
+    rc = lib.aie_test_glibc_math(fn, tx.data_ptr(), ty.data_ptr() if ty is not None else None, out.data_ptr(), len(tx),
+                                 None)
+    assert rc == 0
+    torch.cuda.synchronize()
+    return out.cpu().numpy()
+
+
+@pytest.mark.gpu
+def test_device_math_ulp_error():
+    """The device powf / exp / log the COVID step calls (aie_test_glibc_math fn 3-5) against mpmath over the CRRA
+    input range at every eta of the sweep and over the softplus range: within covid_exact's K.  Measured on MI355X:
+    see DESIGN (COVID-19 (C4), Numerics)."""
+    ax = _powf_inputs(4000, 3)
+    worst = 0
+    for eta in ETAS + [0.5, 3.5, 19.0]:
+        ome = F32(1) - F32(eta)
+        got = _dev_math(3, ax.astype(np.float64), np.full(len(ax), float(ome))).astype(F32)
+        w, frac = _ulp_report(got, cx.cr_powf(ax, ome))
+        print("device powf eta=%g: max %d ulp, %.3f of results not correctly rounded" % (eta, w, frac))
+        worst = max(worst, w)
+    x = _softplus_inputs(6000, 4)
+    e = _dev_math(4, x)
+    w_exp, f_exp = _ulp_report(e, cx.cr_exp(x))
+    arg = 1 + cx.cr_exp(x)
+    w_log, f_log = _ulp_report(_dev_math(5, arg), cx.cr_log(arg))
+    print("device exp: max %d ulp (%.3f inexact), log: max %d ulp (%.3f inexact)" % (w_exp, f_exp, w_log, f_log))
+    assert worst <= cx.K_POWF and w_exp <= cx.K_EXP and w_log <= cx.K_LOG
+
+
+def _hip_env(cfg, E):
+    from test_covid_golden import hip_env
+
+    return hip_env(cfg, n_envs=E)
+
+
+EXACT = ("susceptible", "infected", "recovered", "deaths", "vaccinated", "health_index", "cooldown_until",
+         "subsidy_level")
+
+
+def _hip_got(t, reps):
+    return {"unemployed": t["unemployed"][reps].cpu().numpy(),
+            "postsubsidy_productivity": t["postsubsidy_productivity"][reps].cpu().numpy(),
+            "rewards_a": t["rewards_a"][reps].cpu().numpy(), "rewards_p": t["rewards_p"][reps].cpu().numpy(),
+            "economic_index": t["economic_index"][reps].cpu().numpy(),
+            "planner_economic_index": t["planner_health_economic_index"][reps, 1].cpu().numpy()}
+
+
+def _check_exact(env, o, where):
+    t, st = env.tensors, o.state()
+    for k in EXACT:
+        got, want = t[k].cpu().numpy(), np.asarray(st[k])
+        assert np.array_equal(got, want.astype(got.dtype)) and np.array_equal(got.astype(want.dtype), want), \
+            "%s: %s is not the oracle's bit for bit (max |diff| %.3g)" % (
+                where, k, float(np.abs(got.astype(np.float64) - want.astype(np.float64)).max()))
+    p = t["planner_health_economic_index"][:, 0].cpu().numpy()
+    assert np.array_equal(p, o.planner_index[:, 0]), "%s: planner health index" % where
+    L = int(env.model["filter_len"])
+    ts = int(t["timestep"][0].item())
+    assert np.array_equal(t["stringency_ring"][:, (L + ts) % 32].cpu().numpy(), o.stringency[:, o.t]), where
+    obs = o.observe()
+    for k in ("obs_a_action_mask", "obs_p_action_mask"):
+        assert np.array_equal(t[k].cpu().numpy().reshape(obs[k].shape), obs[k]), "%s: %s" % (where, k)
+    assert np.array_equal(t["done"].cpu().numpy(), o.done), where
+
+
+def _rollout(cfg, E, T, reps, seed, label):
+    import torch
+
+    env, o = _hip_env(cfg, E), _make_oracle(cfg, E)
+    env.reset()
+    o.reset()
+    t = env.tensors
+    rng = np.random.RandomState(seed)
+    ns = dict(cfg["components"])["FederalGovernmentSubsidy"]["num_subsidy_levels"]
+    tr = BandTracker(reps, label)
+    with np.errstate(all="ignore"):
+        for k in range(1, T + 1):
+            a, p = _actions(rng, E, ns)
+            env.step({"a": torch.as_tensor(a, device="cuda"), "p": torch.as_tensor(p[:, None], device="cuda")})
+            o.step(a, p)
+            _check_exact(env, o, "%s day %d" % (label, k))
+            tr.day(o, _hip_got(t, np.asarray(reps)), "day %d" % k)
+    print("%s:" % label)
+    tr.report()
+    return tr
+
+
+ROLLOUTS = [("golden", name) for name in ("c4_covid_51ag", "c4_covid_variant")] + [("random", s) for s in (0, 3, 6)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,which", ROLLOUTS, ids=["%s-%s" % r for r in ROLLOUTS])
+def test_hip_rollout_exact_state_and_banded_rewards(kind, which):
+    """64 replicas (random configs: 16) under random actions, window sums: the basic-operation fields equal the oracle
+    bit for bit every day, the rest lie inside the bands (replicas 0, 1, E - 1 every day)."""
+    if kind == "golden":
+        cfg, E, T = load_covid_golden(which)["cfg"], 64, 130
+        T = min(T, cfg["episode_length"])
+    else:
+        cfg, E = random_covid_config(which), 16
+        T = cfg["episode_length"]
+    _rollout(cfg, E, T, [0, 1, E - 1], 11, "%s %s (eta %g)" % (kind, which, cfg["economic_reward_crra_eta"]))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("eta", ETAS)
+def test_hip_rewards_inside_bands_across_eta(eta):
+    """The CRRA term (ax^(1-eta) - 1) / (1-eta) cancels near eta = 1: one ulp of powf is magnified by 1 / |1 - eta|.
+    At eta = 1 the reference divides 0 by 0 (covid19_env.py:307-308 allows it: NaN
+    rewards); the library refuses that configuration with a clear error instead of producing NaN rewards."""
+    cfg = dict(load_covid_golden("c4_covid_variant")["cfg"], economic_reward_crra_eta=eta)
+    E = 8
+    if eta == 1.0:
+        env = _hip_env(cfg, E)
+        with pytest.raises(ValueError, match="divides by zero"):
+            env.reset()  # (the device configuration is built with the first reset)
+        return
+    _rollout(cfg, E, 40, list(range(E)), 5, "eta %g" % eta)
+
+
+EDGES = {
+    "reward_normalization_7.5": dict(reward_normalization_factor=7.5),
+    "health_priority_0": dict(health_priority_scaling_agents=0.0, health_priority_scaling_planner=0.0),
+    "health_priority_200": dict(health_priority_scaling_agents=200.0, health_priority_scaling_planner=200.0),
+    "too_sick_0": dict(infection_too_sick_to_work_rate=0.0),
+    "too_sick_1": dict(infection_too_sick_to_work_rate=1.0),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("edge", sorted(EDGES))
+def test_hip_config_edges(edge):
+    cfg = dict(load_covid_golden("c4_covid_variant")["cfg"], **EDGES[edge])
+    E = 8
+    _rollout(cfg, E, 30, list(range(E)), 7, edge)
+
+
+@pytest.mark.gpu
+def test_hip_injected_states():
+    """States written into the device tensors and the oracle's arrays, then one day stepped, each case in a replica of
+    its own: S = 0 with vaccines due, S below / equal to the day's vaccines, I = 0, a day without new deaths,
+    production wiped out under the largest subsidy (the planner's CRRA input negative: the lower clamp), and many new
+    deaths (a health term far from zero, where a float32 rounding of it is not absorbed by the normalisation)."""
+    import torch
+
+    cfg = load_covid_golden("c4_covid_variant")["cfg"]
+    E = 8
+    env, o = _hip_env(cfg, E), _make_oracle(cfg, E)
+    env.reset()
+    o.reset()
+    t = env.tensors
+    c, m = o.c, o.m
+    di, tw = o.delivery_interval, int(c["time_when_vaccine_delivery_begins"])
+    day = next(d for d in range(max(tw, 2), 200) if d % di == 0 and (d - 1) % o.subsidy_interval != 0)
+    rng = np.random.RandomState(2)
+    ns = o.num_subsidy_levels
+    for k in range(1, day):
+        a, p = _actions(rng, E, ns)
+        env.step({"a": torch.as_tensor(a, device="cuda"), "p": torch.as_tensor(p[:, None], device="cuda")})
+        o.step(a, p)
+    _check_exact(env, o, "before the injection")
+    tc = day - 1
+    vac = np.asarray(c["num_vaccines_per_delivery"], np.float64)
+    S, I, R, V, D = (np.array(x[:, tc]) for x in (o.S, o.I, o.R, o.V, o.D))  # noqa: E741
+    S[0, :] = 0.0
+    S[1, :17] = (vac[:17] * 0.5).astype(F32)
+    S[1, 17:34] = vac[17:34].astype(F32)
+    S[1, 34:] = np.maximum(vac[34:] - 1, 0).astype(F32)
+    I[2, :] = 0.0
+    I[3, :] = 0.0
+    R[3, :] = 1000.0
+    V[3, :] = 0.0
+    D[3, :] = m["death_rate"] * (R[3] - V[3])
+    pop = np.asarray(m["us_state_population"], F32)
+    R[4, :] = pop * F32(60)  # deaths beyond the population: no one works
+    R[5, :] = R[5] + pop * F32(0.01)  # new deaths large enough for the health term to show every bit
+    sub_level = o.subsidy_level.copy()
+    sub_level[4] = ns
+    for name, arr, mine in (("susceptible", o.S, S), ("infected", o.I, I), ("recovered", o.R, R),
+                            ("vaccinated", o.V, V), ("deaths", o.D, D)):
+        arr[:, tc] = mine
+        t[name].copy_(torch.as_tensor(mine, device="cuda"))
+    o.subsidy_level[:] = sub_level
+    t["subsidy_level"].copy_(torch.as_tensor(sub_level.astype(np.int32), device="cuda"))
+    torch.cuda.synchronize()
+    a = np.zeros((E, 51), np.int32)
+    p = np.zeros(E, np.int32)
+    env.step({"a": torch.as_tensor(a, device="cuda"), "p": torch.as_tensor(p[:, None], device="cuda")})
+    o.step(a, p)
+    assert o.t == day and int(_vaccines(c, day, o.n, di).min()) > 0
+    _check_exact(env, o, "injected day")
+    got = _hip_got(t, np.arange(E))
+    pre, lvl, vacc, window, sub = _oracle_inputs(o, np.arange(E))
+    r = cx.day(m, pre, lvl, vacc, window, sub)
+    for k, arr in (("susceptible", o.S), ("infected", o.I), ("recovered", o.R), ("vaccinated", o.V),
+                   ("deaths", o.D)):
+        assert np.array_equal(r[k], arr[:, o.t]), k
+    for k, key in (("unemployed", "unemployed"), ("postsubsidy_productivity", "postsubsidy_productivity"),
+                   ("rewards_a", "rew_a"), ("rewards_p", "rew_p")):
+        band = r[key]
+        if k in ("unemployed", "rewards_p"):
+            band = _as(band, F32)
+        cx.inside(got[k], band, "injected %s" % k)
+    # the cases were hit
+    assert np.all(o.S[0, day] == 0) and np.all(o.S[1, day] == 0), "S = 0 / S <= vaccines"
+    assert np.all(o.D[3, day] == o.D[3, day - 1]), "no new deaths"
+    cost = (1 + m["risk_free_interest_rate"]) * np.sum(o.subsidy[4, day])
+    assert np.sum(o.postprod[4, day]) - cost < 0, "planner CRRA input not negative"
+
+
+@pytest.mark.gpu
+def test_hip_extreme_filter_responses():
+    """Filter sums at both ends of the softplus: every state of replicas 0-3 jumps from the pre-episode level to 10 on
+    day 1 (x up to ~30: the linear branch x > 20 where the weights are large) and back to 1 on day 26 (x down to ~-3;
+    levels within 1 .. 10 cannot take it to where exp(x) underflows); replicas 4-7 keep their levels."""
+    import torch
+
+    cfg = load_covid_golden("c4_covid_variant")["cfg"]
+    E = 8
+    env, o = _hip_env(cfg, E), _make_oracle(cfg, E)
+    env.reset()
+    o.reset()
+    t = env.tensors
+    rng = np.random.RandomState(8)
+    tr = BandTracker(range(E), "extreme filter responses")
+    xs = []
+    with np.errstate(all="ignore"):
+        for k in range(1, 31):
+            _, p = _actions(rng, E, o.num_subsidy_levels)
+            a = np.zeros((E, 51), np.int32)
+            a[:4] = 10 if k == 1 else (1 if k == 26 else 0)
+            env.step({"a": torch.as_tensor(a, device="cuda"), "p": torch.as_tensor(p[:, None], device="cuda")})
+            o.step(a, p)
+            _check_exact(env, o, "day %d" % k)
+            tr.day(o, _hip_got(t, np.arange(E)), "day %d" % k)
+            xs.append(cx.filter_sum_band(o.m, o.slh)[0])
+    xs = np.stack(xs)
+    print("extreme filter responses: x from %.1f to %.1f" % (xs.min(), xs.max()))
+    tr.report()
+    assert xs[:, :4].max() > 20 and xs[:, :4].min() < -2, "the actions did not reach both sides of the softplus"

@@ -134,7 +134,7 @@ def test_c4_full_batch_matches_oracle(recurrence):
     import torch
     from covid_pool import run_blocks
     from helpers import load_covid_golden
-    from test_covid_golden import STATE_TOL, hip_env
+    from test_covid_golden import assert_state_vs_oracle, hip_env
 
     E, T, B = 8192, 64, 8
     cfg = load_covid_golden("c4_covid_51ag")["cfg"]
@@ -162,9 +162,7 @@ def test_c4_full_batch_matches_oracle(recurrence):
         err_p.append(np.abs(t["rewards_p"].cpu().numpy().astype(np.float64) - want["rew_p"][k - 1]).ravel())
         if k in check_at:
             st = want["state"][k]
-            for name, tol in STATE_TOL.items():
-                np.testing.assert_allclose(t[name].cpu().numpy().astype(np.float64), st[name], rtol=tol, atol=1e-3,
-                                           err_msg="C4 day %d %s" % (k, name))
+            assert_state_vs_oracle(t, st, "C4 day %d" % k)
             assert np.array_equal(t["cooldown_until"].cpu().numpy(), st["cooldown_until"]), "day %d" % k
             assert np.array_equal(t["subsidy_level"].cpu().numpy(), st["subsidy_level"]), "day %d" % k
             for name, v in want["obs"][k].items():
