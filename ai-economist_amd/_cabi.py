@@ -5,10 +5,13 @@ by env.py purely as the owner of device memory / streams.
 """
 import ctypes as C
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 MAX_AGENTS = 64
 MAX_AGENTS_WIDE = 128
 MAX_COMPONENTS = 8
+MAX_SUBSPACES = 16
+MAX_HOST_SUBSPACES = 8
+MAX_MASK = 544  # csrc/aie_layout.h: AIE_MAX_MASK
 MAX_BRACKETS = 16
 MAX_RATES = 64
 N_RES = 2
@@ -142,6 +145,12 @@ class AieConfig(C.Structure):
         ("mz_cols", C.c_int32),
         ("mz_zones", C.c_int32 * 3),
         ("layout_pad_", C.c_int32),
+        ("host_a_n", C.c_int32),
+        ("host_p_n", C.c_int32),
+        ("host_a_dim", C.c_int32 * MAX_HOST_SUBSPACES),
+        ("host_a_before", C.c_int32 * MAX_HOST_SUBSPACES),
+        ("host_p_dim", C.c_int32 * MAX_HOST_SUBSPACES),
+        ("host_p_before", C.c_int32 * MAX_HOST_SUBSPACES),
     ]
 
 

@@ -600,6 +600,7 @@ int aie_step_sample_next(aie_env* env, const int32_t* d_actions_a, const int32_t
     snprintf(env->err, sizeof(env->err), "aie_step_sample_next: the next-action buffers must differ from the current ones");
     return AIE_E_INVALID;
   }
+  if (aie_sampler_check(&env->P, env->err, sizeof(env->err)) != AIE_OK) return AIE_E_UNSUPPORTED;
   NextActions next{};
   next.a = d_next_a;
   next.p = d_next_p;
@@ -707,7 +708,7 @@ static int aie_step_impl(aie_env* env, const int32_t* d_actions_a, const int32_t
   }
 #endif
   else if (env->P.saez_stride || env->P.M > AIE_NT || env->P.regen_general || env->P.dev_skip_mask != 0 ||
-           env->P.dev_trace != nullptr)
+           env->P.dev_trace != nullptr || env->P.n_host_a || env->P.n_host_p)  // (foreign action subspaces: decoded by this kernel only)
     hipLaunchKernelGGL(aie_step_kernel_log, dim3((unsigned)env->P.E), dim3(2 * AIE_NT), env->lds,
                        static_cast<hipStream_t>(stream), env->d_params, env->arena, d_actions_a, d_actions_p, next);
   else if (env->spec == AIE_KERNEL_INSTANCE_JIT) {
@@ -794,6 +795,7 @@ int aie_set_auto_reset(aie_env* env, int on) {
 int aie_sample_random_actions(aie_env* env, uint64_t seed, int64_t global_env_offset, int32_t* d_actions_a,
                               int32_t* d_actions_p, void* stream) {
   if (!env) return AIE_E_INVALID;
+  if (aie_sampler_check(&env->P, env->err, sizeof(env->err)) != AIE_OK) return AIE_E_UNSUPPORTED;
   AIE_HIP_CHECK(env, hipSetDevice(env->device));
   const aie_params& P = env->P;
   const int64_t tot = (int64_t)P.E * (P.n * P.act_a_width + P.act_p_width);
@@ -808,6 +810,7 @@ int aie_sample_random_actions(aie_env* env, uint64_t seed, int64_t global_env_of
 int aie_sample_masked_actions(aie_env* env, uint64_t seed, int64_t global_env_offset, int32_t* d_actions_a,
                               int32_t* d_actions_p, void* stream) {
   if (!env) return AIE_E_INVALID;
+  if (aie_sampler_check(&env->P, env->err, sizeof(env->err)) != AIE_OK) return AIE_E_UNSUPPORTED;
   AIE_HIP_CHECK(env, hipSetDevice(env->device));
   const aie_params& P = env->P;
   const int64_t tot = (int64_t)P.E * (P.n * P.act_a_width + P.act_p_width);
@@ -826,6 +829,7 @@ int aie_sample_policy_actions(aie_env* env, const float* d_logits_a, const float
     snprintf(env->err, sizeof(env->err), "aie_sample_policy_actions: an action buffer without its logits");
     return AIE_E_INVALID;
   }
+  if (aie_sampler_check(&env->P, env->err, sizeof(env->err)) != AIE_OK) return AIE_E_UNSUPPORTED;
   AIE_HIP_CHECK(env, hipSetDevice(env->device));
   // waves per replica (1, 2 or 4 of a workgroup's four); AIE_SAMPLER_WAVES_LOG2 in the environment is a development knob
   static const int wpr_log2 = [] {
@@ -861,7 +865,7 @@ int aie_step_kernel_instance(aie_env* env) { return env ? env->spec : -2; }
 static bool aie_jit_eligible(const aie_env* env) {
   const aie_params& P = env->P;
   const bool ose = P.c.scenario == AIE_SCN_ONE_STEP_ECONOMY;
-  return !(P.c.scenario == AIE_SCN_COVID || P.saez_stride || (!ose && (P.M > AIE_NT || P.regen_general)));
+  return !(P.c.scenario == AIE_SCN_COVID || P.saez_stride || P.n_host_a || P.n_host_p || (!ose && (P.M > AIE_NT || P.regen_general)));
 }
 // starts (or joins) the background job that compiles / fetches the code object of this environment's family
 static int aie_jit_request(aie_env* env) {

@@ -332,7 +332,7 @@ __device__ __forceinline__ void sample_action_slot(const aie_params& P, uint64_t
     act_a[(int64_t)e * P.n * P.act_a_width + j] = (int32_t)(((uint64_t)u * (uint64_t)range) >> 32);
   } else {
     if (!act_p) return;
-    const int range = P.c.multi_action_mode_planner ? P.sub_p_dim + 1 : 1 + P.n_sub_p * P.sub_p_dim;
+    const int range = P.c.multi_action_mode_planner ? P.p_row_dim + 1 : P.AP;  // (rows of one length: aie_sampler_check)
     act_p[(int64_t)e * P.act_p_width + (j - P.n * P.act_a_width)] = (int32_t)(((uint64_t)u * (uint64_t)range) >> 32);
   }
 }
@@ -969,27 +969,56 @@ __device__ __forceinline__ void agents_store(const Ctx& c, const Agents& A) {
 // action into its packed per-subspace word; lane b decodes planner bracket b.
 // Returns the AIE_ERR_* bits of out-of-range indices (wave-uniform); the caller ORs them into the record's error_flags
 // once the record is in LDS -- the action loads themselves leave ahead of it (step_body).
+//
+// Subspaces of host components (slot AIE_SUB_HOST; the planner's rows hp_*, aie_layout.h) have no place in the packed
+// word: in the full-featured kernel (Ctx::full; the only one such an environment runs) lane i stores agent i's foreign
+// sub-actions as int32 [n_host_a] into the tensor host_actions_a and lane k the planner's k-th into host_actions_p --
+// plain vector stores to the arena, outside the record; without a buffer (aa / ap null: a launch that only observes)
+// the tensors keep what the step's first launch wrote.  No other kernel ever runs an environment with such subspaces
+// (aie_capi.hip: aie_step_impl sends it to the full-featured kernel, aie_jit_eligible keeps it off the run-time
+// instances); elsewhere the decode is the plain one, which leaves foreign slots out of the packed word.
 __device__ __forceinline__ int decode_actions(const Ctx& c, Agents& A, const int32_t* __restrict__ aa,
-                               const int32_t* __restrict__ ap) {
+                               const int32_t* __restrict__ ap, uint8_t* __restrict__ arena = nullptr) {
   const aie_params& P = c.P;
+  const bool host = c.full && arena;  // (compile-time false in the common step kernel, see Ctx::full)
   const int i = c.tid;
   uint32_t act = 0;
   bool bad_a = false, bad_p = false;  // out-of-range indices: NO-OP here, an exception in the reference (AIE_ERR_*)
   if (i < P.n && aa) {
     const int32_t* a = aa + ((int64_t)c.e * P.n + i) * P.act_a_width;
-    static const int shift[AIE_N_SUB_SLOTS] = {0, 4, 11, 18, 25, 1, 0};
-    if (P.c.multi_action_mode_agents) {
+    static const int shift[AIE_N_SUB_SLOTS] = {0, 4, 11, 18, 25, 1, 0, 0};  // ([AIE_SUB_HOST]: never shifted by, both paths skip the slot)
+    int32_t* ha = (host && P.n_host_a) ? reinterpret_cast<int32_t*>(arena + c.R.a_host_act_a) + ((int64_t)c.e * P.n + i) * P.n_host_a : nullptr;
+    int h = 0;  // (uniform: the foreign slots so far)
+    if (!ha) {
+      if (P.c.multi_action_mode_agents) {
+        for (int s = 0; s < P.n_sub_a; ++s) {
+          const int v = a[s];
+          if (v < 0 || v > P.sub_a_dim[s]) bad_a = true;
+          else if (P.sub_a_slot[s] != AIE_SUB_HOST) act |= (uint32_t)v << shift[P.sub_a_slot[s]];
+        }
+      } else {
+        const int v = a[0];
+        bad_a = v < 0 || v >= P.A;
+        for (int s = 0; s < P.n_sub_a; ++s)
+          if (P.sub_a_slot[s] != AIE_SUB_HOST && v >= P.sub_a_base[s] && v < P.sub_a_base[s] + P.sub_a_dim[s])
+            act |= (uint32_t)(v - P.sub_a_base[s] + 1) << shift[P.sub_a_slot[s]];
+      }
+    } else if (P.c.multi_action_mode_agents) {
       for (int s = 0; s < P.n_sub_a; ++s) {
         const int v = a[s];
-        if (v >= 0 && v <= P.sub_a_dim[s]) act |= (uint32_t)v << shift[P.sub_a_slot[s]];
-        else bad_a = true;
+        const bool ok = v >= 0 && v <= P.sub_a_dim[s];
+        if (P.sub_a_slot[s] == AIE_SUB_HOST) ha[h++] = ok ? v : 0;
+        else if (ok) act |= (uint32_t)v << shift[P.sub_a_slot[s]];
+        if (!ok) bad_a = true;
       }
     } else {
       const int v = a[0];
       bad_a = v < 0 || v >= P.A;
-      for (int s = 0; s < P.n_sub_a; ++s)
-        if (v >= P.sub_a_base[s] && v < P.sub_a_base[s] + P.sub_a_dim[s])
-          act |= (uint32_t)(v - P.sub_a_base[s] + 1) << shift[P.sub_a_slot[s]];
+      for (int s = 0; s < P.n_sub_a; ++s) {
+        const bool in = v >= P.sub_a_base[s] && v < P.sub_a_base[s] + P.sub_a_dim[s];
+        if (P.sub_a_slot[s] == AIE_SUB_HOST) ha[h++] = in ? v - P.sub_a_base[s] + 1 : 0;
+        else if (in) act |= (uint32_t)(v - P.sub_a_base[s] + 1) << shift[P.sub_a_slot[s]];
+      }
     }
   }
   A.act = act;
@@ -997,17 +1026,32 @@ __device__ __forceinline__ int decode_actions(const Ctx& c, Agents& A, const int
     int v = 0;
     if (ap && i < P.n_sub_p) {
       const int32_t* a = ap + (int64_t)c.e * P.act_p_width;
+      // (the tax block's first row / first single-action index: 0 / 1 without foreign planner rows ahead of it)
+      const int row0 = (host && P.n_host_p) ? P.tax_p_row0 : 0, x0 = (host && P.n_host_p) ? P.tax_p_base : 1;
       if (P.c.multi_action_mode_planner) {
-        v = a[i];
+        v = a[row0 + i];
         bad_p = v < 0 || v > P.sub_p_dim;  // (the tax component ignores what its mask forbids; out of range is an error)
         if (bad_p) v = 0;
       } else {
         const int x = a[0];
-        bad_p = x < 0 || x >= 1 + P.n_sub_p * P.sub_p_dim;
-        if (x >= 1 && x < 1 + P.n_sub_p * P.sub_p_dim && (x - 1) / P.sub_p_dim == i) v = (x - 1) % P.sub_p_dim + 1;
+        bad_p = x < 0 || x >= ((host && P.n_host_p) ? P.AP : 1 + P.n_sub_p * P.sub_p_dim);
+        if (x >= x0 && x < x0 + P.n_sub_p * P.sub_p_dim && (x - x0) / P.sub_p_dim == i) v = (x - x0) % P.sub_p_dim + 1;
       }
     }
     c.act_p[i] = v;
+  }
+  if (host && P.n_host_p && ap && i < P.n_host_p) {  // the planner's foreign rows: lane k decodes row hp_row[k]
+    const int32_t* a = ap + (int64_t)c.e * P.act_p_width;
+    int v;
+    if (P.c.multi_action_mode_planner) {
+      v = a[P.hp_row[i]];
+      if (v < 0 || v > P.hp_dim[i]) { bad_p = true; v = 0; }
+    } else {
+      const int x = a[0];
+      if (x < 0 || x >= P.AP) bad_p = true;
+      v = (x >= P.hp_base[i] && x < P.hp_base[i] + P.hp_dim[i]) ? x - P.hp_base[i] + 1 : 0;
+    }
+    reinterpret_cast<int32_t*>(arena + c.R.a_host_act_p)[(int64_t)c.e * P.n_host_p + i] = v;
   }
   return (__ballot(bad_a) ? AIE_ERR_AGENT_ACTION : 0) | (__ballot(bad_p) ? AIE_ERR_PLANNER_ACTION : 0);
 }
@@ -2616,8 +2660,14 @@ __device__ __forceinline__ void write_action_masks(const Ctx& c, uint8_t* __rest
     }
     for (int q = tid; q < P.MP; q += AIE_NT) {
       float v;
-      int j = -1;  // index of the discretised rate this entry stands for (-1: a NO-OP entry)
+      int j = -1;  // index of the discretised rate this entry stands for (-1: a NO-OP entry, or a foreign row's)
       if (P.n_sub_p == 0) j = -1;
+      else if (c.full && P.n_host_p) {
+        // the tax block sits at tax_p_moff among foreign rows (aie_layout.h): everything outside it is written as 1.0
+        // (the host puts its components' masks there behind the launch)
+        const int w = pmulti ? 1 + P.sub_p_dim : P.sub_p_dim, tq = q - P.tax_p_moff;
+        if (tq >= 0 && tq < P.n_sub_p * w) j = tq - udiv(tq, w, pmulti ? P.mg_sub_p : P.mg_sub_p_dim) * w - (pmulti ? 1 : 0);
+      }
       else if (pmulti) j = q - udiv(q, 1 + P.sub_p_dim, P.mg_sub_p) * (1 + P.sub_p_dim) - 1;
       else if (q > 0) j = (q - 1) - udiv(q - 1, P.sub_p_dim, P.mg_sub_p_dim) * P.sub_p_dim;
       if (j < 0) v = 1.0f;
@@ -2826,7 +2876,7 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
     // ---------------- first wave: actions, components, flat vectors, rewards ----------------
     Agents A;
     int act_err = 0;
-    if (!(skip & (1 << 18))) act_err = decode_actions(c, A, act_a, act_p);  // (c.act_p is LDS scratch)
+    if (!(skip & (1 << 18))) act_err = decode_actions(c, A, act_a, act_p, arena);  // (c.act_p is LDS scratch)
     else A.act = 0;
     if (TRACE && R.dev_trace && c.tid == 0) R.dev_trace[12 * blockIdx.x] = wall_clock64();
     if (TRACE && R.dev_trace && c.tid == 0) R.dev_trace[12 * blockIdx.x + 9] = wall_clock64();
@@ -3979,8 +4029,8 @@ extern "C" __global__ void aie_sample_masked_actions_kernel(const aie_params P, 
     if (covid) mask = reinterpret_cast<const float*>(arena + P.a_cv_obs_p) + (int64_t)e * (4 + P.MP) + 4;
     else mask = reinterpret_cast<const float*>(arena + P.a_obs_p_mask) + (int64_t)e * P.MP;
     if (P.c.multi_action_mode_planner) {
-      lo = s * (1 + P.sub_p_dim);
-      len = P.n_sub_p ? 1 + P.sub_p_dim : 1;
+      lo = s * (1 + P.p_row_dim);  // (rows of one length, foreign ones included: aie_sampler_check)
+      len = 1 + P.p_row_dim;
     } else {
       lo = 0;
       len = P.MP;

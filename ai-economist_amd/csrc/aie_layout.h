@@ -47,7 +47,9 @@ enum {
   AIE_SUB_SELL1 = 4, /* Sell_Wood  */
   AIE_SUB_GATHER = 5,
   AIE_SUB_LABOR = 6, /* SimpleLabor (one-step-economy) */
-  AIE_N_SUB_SLOTS = 7
+  AIE_SUB_HOST = 7,  /* a host component's subspace (aie_config.host_a_*): no bits in the packed action word, no mask
+                      * test (always 1) -- its sub-action goes to the tensor host_actions_a, in the order of the slots */
+  AIE_N_SUB_SLOTS = 8
 };
 
 /* Everything a kernel needs, passed BY VALUE as the kernel argument. */
@@ -74,6 +76,9 @@ typedef struct aie_params {
   int32_t A;                            /* single-action mode: total actions incl NO-OP */
   int32_t n_sub_p;                      /* planner subspaces (NB or 0)                 */
   int32_t sub_p_dim;
+  int32_t AP;                           /* planner, single-action mode: total actions incl NO-OP */
+  int32_t p_row_dim;                    /* entries (NO-OP not counted) of a multi-action planner's rows where they are equally
+                                         * long (p_rows_uniform, below): sub_p_dim without foreign rows                  */
   int32_t act_a_width;                  /* ints per agent in d_actions_a               */
   int32_t act_p_width;                  /* ints per replica in d_actions_p             */
 
@@ -257,6 +262,22 @@ typedef struct aie_params {
   int32_t o_sample_t, o_rew_slot, o_rew_epoch;
   int32_t dev_draw_window; /* development (tests): capacity of the components' draw window in words, 0 = stage_window_words();
                             * honoured by aie_step_kernel_log only */
+  /* ---- action subspaces of host components (aie_config.host_*; all zero without them) ----
+   * Agents: slots AIE_SUB_HOST among sub_a_*; the k-th such slot is column k of host_actions_a.
+   * Planner: its rows are the n_sub_p tax rows (one block: PeriodicBracketTax is one component) with the foreign rows
+   * listed ahead of that component in front of the block and the others behind it.  Row r is column r of d_actions_p
+   * in multi-action mode; in single-action mode the one index runs over NO-OP and then the rows' entries in order. */
+  int32_t n_host_a, n_host_p;
+  int32_t tax_p_row0;    /* row (multi-action column) of the first tax bracket                                  */
+  int32_t tax_p_base;    /* single-action index of the first tax entry (1 without foreign rows ahead)            */
+  int32_t tax_p_moff;    /* flattened planner mask: offset of the tax block (multi-action: of its first row's NO-OP
+                          * entry; single-action: of its first rate entry == tax_p_base)                         */
+  int32_t p_rows_uniform;/* 1: every planner row has p_row_dim entries + NO-OP (what the samplers' planner group needs) */
+  int32_t hp_dim[AIE_MAX_HOST_SUBSPACES];  /* foreign planner row k: choices,                                    */
+  int32_t hp_row[AIE_MAX_HOST_SUBSPACES];  /* its row,                                                           */
+  int32_t hp_base[AIE_MAX_HOST_SUBSPACES]; /* its first single-action index,                                     */
+  int32_t hp_moff[AIE_MAX_HOST_SUBSPACES]; /* the offset of its first entry in the flattened mask (multi-action: its NO-OP) */
+  int64_t a_host_act_a, a_host_act_p;      /* arena: int32 [E][n][n_host_a], int32 [E][n_host_p]                 */
 } aie_params;
 
 /* Compile-time instances of the step kernel (aie_spec_generated.h) bake a CONSTANT image of aie_params into the code.
@@ -290,6 +311,7 @@ static inline void aie_spec_normalize(aie_params* p) {
   p->a_layout_prob = 0;
   p->a_layout_stage = p->a_layout_tag = p->a_layout_ctl = 0;
   p->a_src_list = 0;
+  p->a_host_act_a = p->a_host_act_p = 0;
   p->dev_skip_mask = 0;
   p->dev_trace = 0;
   p->rew_log = 0;
@@ -515,6 +537,8 @@ static inline int aie__build_covid(const aie_config* c, aie_params* p, aie_tenso
   p->A = 1 + p->cv_NL;  p->MA = p->A;  p->act_a_width = 1;  p->n_sub_a = 1;
   p->sub_a_dim[0] = p->cv_NL; p->sub_a_base[0] = 1;
   p->n_sub_p = 1; p->sub_p_dim = p->cv_NS; p->MP = 1 + p->cv_NS; p->act_p_width = 1;
+  p->AP = 1 + p->cv_NS; p->p_row_dim = p->cv_NS; p->p_rows_uniform = 1; p->tax_p_base = 1; p->tax_p_moff = 1;
+  if (c->host_a_n || c->host_p_n) AIE__FAIL("host components' action subspaces: gather-trade-build scenarios only");
   p->planner_acts = 1;
 
   int32_t cur = 0;
@@ -1040,9 +1064,31 @@ static inline int aie_build_params(const aie_config* c, aie_params* p, aie_tenso
   }
 
   /* ---- action subspaces, registration order = component order ----------------- */
-  int ns = 0, base = 1;
-  for (int i = 0; i < c->n_components; ++i) {
-    switch (c->components[i]) {
+  if (c->host_a_n < 0 || c->host_a_n > AIE_MAX_HOST_SUBSPACES || c->host_p_n < 0 || c->host_p_n > AIE_MAX_HOST_SUBSPACES)
+    AIE__FAIL("host components: at most %d action subspaces per agent class (%d for the agents, %d for the planner)",
+              AIE_MAX_HOST_SUBSPACES, c->host_a_n, c->host_p_n);
+  if ((c->host_a_n || c->host_p_n) && !gtb)
+    AIE__FAIL("host components' action subspaces: gather-trade-build scenarios only");
+  for (int k = 0; k < c->host_a_n + c->host_p_n; ++k) {
+    const int pl = k >= c->host_a_n, q = pl ? k - c->host_a_n : k;
+    const int32_t* dim = pl ? c->host_p_dim : c->host_a_dim;
+    const int32_t* bef = pl ? c->host_p_before : c->host_a_before;
+    if (dim[q] < 1 || dim[q] > AIE_MAX_MASK) AIE__FAIL("host components: %s subspace %d has %d choices", pl ? "planner" : "agent", q, dim[q]);
+    if (bef[q] < 0 || bef[q] > c->n_components || (q > 0 && bef[q] < bef[q - 1]))
+      AIE__FAIL("host components: %s subspace %d sits behind %d built-in components (of %d; non-decreasing)",
+                pl ? "planner" : "agent", q, bef[q], c->n_components);
+  }
+  p->n_host_a = c->host_a_n;
+  p->n_host_p = c->host_p_n;
+  int ns = 0, base = 1, hk = 0;
+  for (int i = 0; i <= c->n_components; ++i) {
+    /* the foreign subspaces listed ahead of built-in component i (i == n_components: behind the last one) */
+    for (; hk < c->host_a_n && c->host_a_before[hk] == i; ++hk) {
+      if (ns >= AIE_MAX_SUBSPACES) AIE__FAIL("more than %d agent action subspaces", AIE_MAX_SUBSPACES);
+      p->sub_a_slot[ns] = AIE_SUB_HOST; p->sub_a_dim[ns] = c->host_a_dim[hk]; ns++;
+    }
+    if (i == c->n_components) break;
+    switch (c->components[i]) {  /* (at most 7 built-in slots + AIE_MAX_HOST_SUBSPACES <= AIE_MAX_SUBSPACES) */
       case AIE_COMP_BUILD:
         p->sub_a_slot[ns] = AIE_SUB_BUILD; p->sub_a_dim[ns] = 1; ns++; break;
       case AIE_COMP_CDA:
@@ -1069,8 +1115,31 @@ static inline int aie_build_params(const aie_config* c, aie_params* p, aie_tenso
   }
   p->n_sub_p = p->planner_acts ? p->NB : 0;
   p->sub_p_dim = p->planner_acts ? c->tax_n_disc_rates : 0;
-  if (c->multi_action_mode_planner) p->act_p_width = p->n_sub_p ? p->n_sub_p : 1;
-  else p->act_p_width = 1;
+  {
+    /* the planner's rows: the foreign ones listed ahead of the tax component, the tax brackets, the other foreign ones */
+    int tax_at = c->n_components;  /* (no acting tax component: every foreign row counts as "ahead", the block is empty) */
+    for (int i = 0; i < c->n_components; ++i)
+      if (c->components[i] == AIE_COMP_TAX && p->n_sub_p) tax_at = i;
+    const int multi = c->multi_action_mode_planner ? 1 : 0;
+    int row = 0, sbase = 1, moff = multi ? 0 : 1, placed = 0;
+    p->p_rows_uniform = 1;
+    p->p_row_dim = p->n_sub_p ? p->sub_p_dim : (c->host_p_n ? c->host_p_dim[0] : 0);
+    for (int k = 0; k <= c->host_p_n; ++k) {
+      if (!placed && (k == c->host_p_n || c->host_p_before[k] > tax_at)) {
+        p->tax_p_row0 = row; p->tax_p_base = sbase; p->tax_p_moff = moff;
+        row += p->n_sub_p; sbase += p->n_sub_p * p->sub_p_dim; moff += p->n_sub_p * (multi + p->sub_p_dim);
+        placed = 1;
+      }
+      if (k == c->host_p_n) break;
+      p->hp_dim[k] = c->host_p_dim[k]; p->hp_row[k] = row; p->hp_base[k] = sbase; p->hp_moff[k] = moff;
+      if (p->hp_dim[k] != p->p_row_dim) p->p_rows_uniform = 0;
+      row += 1; sbase += p->hp_dim[k]; moff += multi + p->hp_dim[k];
+    }
+    p->AP = sbase;
+    /* (at most AIE_MAX_BRACKETS + AIE_MAX_HOST_SUBSPACES rows; no table on the planner's side is sized by a row count) */
+    if (multi) { p->act_p_width = row ? row : 1; p->MP = row ? moff : 1; }
+    else { p->act_p_width = 1; p->MP = moff; }
+  }
 
   /* ---- flattened masks (base_agent.py:440-460) -------------------------------- */
   if (c->multi_action_mode_agents) {
@@ -1080,9 +1149,14 @@ static inline int aie_build_params(const aie_config* c, aie_params* p, aie_tenso
   } else {
     p->MA = p->A;
   }
-  if (c->multi_action_mode_planner) p->MP = p->n_sub_p ? p->n_sub_p * (1 + p->sub_p_dim) : 1;
-  else p->MP = 1 + p->n_sub_p * p->sub_p_dim;
   if (p->MA > AIE_MAX_MASK) AIE__FAIL("flattened action mask too long (%d > %d)", p->MA, AIE_MAX_MASK);
+  /* (nothing on the planner's side is sized by AIE_MAX_MASK -- the tax rows alone may reach 16 x 65 entries; the bound
+   * only keeps foreign subspaces within what the agents' side accepts) */
+  if (p->n_host_p) {
+    const int foreign = p->MP - p->n_sub_p * ((c->multi_action_mode_planner ? 1 : 0) + p->sub_p_dim);
+    if (foreign > AIE_MAX_MASK)
+      AIE__FAIL("flattened planner action mask too long (%d entries outside the tax brackets' > %d)", foreign, AIE_MAX_MASK);
+  }
   {
     /* mask bits (kernel): 0 build | 1..4 move L,R,U,D | 5,6 sell Stone,Wood | 8..15, 16..23:
      * number of affordable bid prices for Stone, Wood */
@@ -1255,6 +1329,9 @@ static inline int aie_build_params(const aie_config* c, aie_params* p, aie_tenso
   }
   p->a_src_list = a;
   if (aie__shared_src_list(c)) a = aie__align(a + 16 + 2 * AIE_SRC_CAP, 256);
+  p->a_host_act_a = p->a_host_act_p = a;
+  if (p->n_host_a) { p->a_host_act_a = a; a = aie__align(a + E * n * p->n_host_a * 4, 256); }
+  if (p->n_host_p) { p->a_host_act_p = a; a = aie__align(a + E * p->n_host_p * 4, 256); }
   p->arena_bytes = a;
 
   /* ---- tensor table ------------------------------------------------------------ */
@@ -1352,6 +1429,8 @@ static inline int aie_build_params(const aie_config* c, aie_params* p, aie_tenso
     if (c->layout_gen != AIE_LAYOUT_FIXED)
       aie__add_shared(tt, "layout_source_prob", AIE_F64, p->a_layout_prob, 2, AIE_N_RES, HW);
     if (aie__layout_staged(c)) aie__add_shared(tt, "layout_stage_ctl", AIE_I32, p->a_layout_ctl, 1, 4, 0);
+    if (p->n_host_a) DENSE("host_actions_a", AIE_I32, p->a_host_act_a, 2, n, p->n_host_a, 0, 0);
+    if (p->n_host_p) DENSE("host_actions_p", AIE_I32, p->a_host_act_p, 1, p->n_host_p, 0, 0, 0);
 #undef DENSE
   }
   return AIE_OK;
@@ -1434,6 +1513,16 @@ typedef struct aie_sampler_args {
   const aie_params* params;   /* the device copy: read for multi-action agents only (rows of different lengths) */
   int32_t E, ragged, act_a_width, pad_;
 } aie_sampler_args;
+/* The samplers' planner group is rows of ONE length.  A multi-action planner with a foreign row (aie_config.host_p_*) of
+ * another length than the tax rows' is refused (the choice stated in include/aie.h): 0 = fine, else the message is in err. */
+static inline int aie_sampler_check(const aie_params* p, char* err, size_t errlen) {
+  if (p->c.multi_action_mode_planner && p->n_host_p && !p->p_rows_uniform) {
+    if (err) snprintf(err, errlen, "samplers: a multi-action planner whose foreign action subspaces differ in size from its other "
+                      "rows (%d entries) is not supported: sample the planner's actions on the host", 1 + p->p_row_dim);
+    return AIE_E_UNSUPPORTED;
+  }
+  return AIE_OK;
+}
 static inline aie_sampler_args aie_sampler_args_of(const aie_params* p, const aie_params* d_params) {
   aie_sampler_args S;
   memset(&S, 0, sizeof(S));
@@ -1458,10 +1547,12 @@ static inline aie_sampler_args aie_sampler_args_of(const aie_params* p, const ai
     A->mks = 1;
     A->mrs = p->MA;
   }
-  Q->len = p->c.multi_action_mode_planner ? (p->n_sub_p ? 1 + p->sub_p_dim : 1) : p->MP;
+  /* a multi-action planner's rows are 1 + p_row_dim entries each (the tax brackets' 1 + sub_p_dim without foreign rows);
+   * rows of different lengths (p_rows_uniform == 0) do not reach this function: aie_sampler_check refuses them */
+  Q->len = p->c.multi_action_mode_planner ? 1 + p->p_row_dim : p->MP;
   Q->lsh = aie_sampler_segment(Q->len) == 16 ? 4 : aie_sampler_segment(Q->len) == 32 ? 5 : 6;
   Q->rows = p->act_p_width;
-  Q->lrs = Q->mrs = p->c.multi_action_mode_planner ? 1 + p->sub_p_dim : p->MP; /* (a multi-action planner's rows: 1 + sub_p_dim apart) */
+  Q->lrs = Q->mrs = p->c.multi_action_mode_planner ? 1 + p->p_row_dim : p->MP; /* (a multi-action planner's rows: 1 + p_row_dim apart) */
   Q->mks = 1;
   Q->lg_estride = (uint32_t)p->MP;
   Q->mk_off = covid ? p->a_cv_obs_p + 16 : p->a_obs_p_mask;

@@ -333,7 +333,7 @@ class DeviceBackend:
     def _n_sub_a(self):
         comps = list(self.cfg.components)[: self.cfg.n_components]
         return sum({_cabi.COMP_BUILD: 1, _cabi.COMP_CDA: 4, _cabi.COMP_GATHER: 1,
-                    _cabi.COMP_SIMPLE_LABOR: 1}.get(c, 0) for c in comps)
+                    _cabi.COMP_SIMPLE_LABOR: 1}.get(c, 0) for c in comps) + int(self.cfg.host_a_n)
 
     def _act_p_width(self):
         return self._act_p_width_for(self.cfg)
@@ -343,8 +343,8 @@ class DeviceBackend:
         has_planner_actions = (
             _cabi.COMP_TAX in list(cfg.components)[: cfg.n_components]
             and cfg.tax_model == 0 and not cfg.tax_disable)
-        if cfg.multi_action_mode_planner and has_planner_actions:
-            return cfg.tax_n_brackets
+        if cfg.multi_action_mode_planner:  # one column per row: the tax brackets and the host components' subspaces
+            return max(1, (cfg.tax_n_brackets if has_planner_actions else 0) + int(cfg.host_p_n))
         return 1
 
     def upload(self, name, array):

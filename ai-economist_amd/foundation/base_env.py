@@ -137,17 +137,37 @@ class BaseEnvironment:
             self._shorthand_lookup[obj.shorthand] = obj
         # host components: (built-in components listed before it, component), in list order
         self._host_components = []
+        # action subspaces of host components (foundation.ActingComponent): per actor class
+        # [(built-in components listed before it, component, sub-action name or None, choices)], in list order
+        self._host_subspaces = {"a": [], "p": []}
         n_builtin = 0
         for obj in self._components:
             if getattr(obj, "is_batched_host_component", False):
-                if obj.get_n_actions("BasicMobileAgent") or obj.get_n_actions("BasicPlanner"):
-                    raise NotImplementedError("host component {!r}: action subspaces are the kernels' (get_n_actions must "
-                                              "return None)".format(obj.name))
+                acting = getattr(obj, "owns_action_subspaces", False)
+                cols = {"a": {}, "p": {}}
+                for who, cls in (("a", "BasicMobileAgent"), ("p", "BasicPlanner")):
+                    subs = self._subspaces_of(obj, cls)
+                    if subs and not acting:
+                        raise NotImplementedError("host component {!r}: action subspaces are the kernels' for a plain "
+                                                  "BatchedComponent (its get_n_actions must return None); a component that "
+                                                  "acts subclasses foundation.ActingComponent".format(obj.name))
+                    for sub, k in subs:
+                        cols[who][sub] = len(self._host_subspaces[who])
+                        self._host_subspaces[who].append((n_builtin, obj, sub, k))
+                if acting:
+                    obj._action_columns = cols
                 self._host_components.append((n_builtin, obj))
             else:
                 n_builtin += 1
+        for who, what in (("a", "agents"), ("p", "planner")):
+            if len(self._host_subspaces[who]) > _cabi.MAX_HOST_SUBSPACES:
+                raise ValueError("too many action subspaces of host components for the {}: {} (at most {})".format(
+                    what, len(self._host_subspaces[who]), _cabi.MAX_HOST_SUBSPACES))
+        self._acting_components = [c for _, c in self._host_components if getattr(c, "owns_action_subspaces", False)
+                                   and (c._action_columns["a"] or c._action_columns["p"])]
         self._n_builtin_components = n_builtin
         self._host_obs_tables = None
+        self._host_mask_slots = None
 
         self._completions = 0
         self._last_ep_metrics = None
@@ -242,6 +262,11 @@ class BaseEnvironment:
             cfg.components[i] = c.comp_id
             c.fill_config(cfg)
         self.fill_scenario_config(cfg)
+        # the action subspaces of host components: where they sit among the built-in ones (include/aie.h: host_*)
+        cfg.host_a_n, cfg.host_p_n = len(self._host_subspaces["a"]), len(self._host_subspaces["p"])
+        for who, dims, before in (("a", cfg.host_a_dim, cfg.host_a_before), ("p", cfg.host_p_dim, cfg.host_p_before)):
+            for k, (n_before, _comp, _sub, size) in enumerate(self._host_subspaces[who]):
+                dims[k], before[k] = size, n_before
         return cfg
 
     # ---- device backend ----
@@ -450,6 +475,7 @@ class BaseEnvironment:
             if edited_ahead or edited_behind:  # the reset kernel's observations no longer show the state: rewrite them
                 retax = _cabi.STEP_RETAX if (tax_at is not None and edited_ahead and not retaken) else 0
                 self.backend.step_range(None, None, 0, 0, _cabi.STEP_OBSERVE | _cabi.STEP_REBASE | retax, mask=env_mask)
+            self._write_host_masks(env_mask)
         if log_replica_resets:
             self._dense_log = {"world": [], "states": [], "actions": [], "rewards": []}
             if self._dense_log_this_episode:
@@ -475,24 +501,86 @@ class BaseEnvironment:
         """Dense log of the logged replica's most recent completed, logged episode."""
         return self._last_ep_dense_log
 
+    @staticmethod
+    def _subspaces_of(comp, cls):
+        """[(sub-action name or None, choices)] a component registers for actor class `cls`: the reference's reading of
+        get_n_actions (base_agent.py:116-153) -- None / 0: nothing, an int: one subspace, a list of (name, n): one each
+        (n == 0 skipped, a "." in a name is a NameError), anything else a TypeError."""
+        n = comp.get_n_actions(cls)
+        if n is None:
+            return []
+        if isinstance(n, (int, np.integer)) and not isinstance(n, bool):
+            return [(None, int(n))] if n != 0 else []
+        if isinstance(n, (tuple, list)):
+            out = []
+            for sub, k in n:
+                if k == 0:
+                    continue
+                if "." in sub:
+                    raise NameError("Sub-action {} of component {} is illegally named.".format(sub, comp.name))
+                out.append((sub, int(k)))
+            return out
+        raise TypeError("Received unexpected type ({}) from {}.get_n_actions('{}')".format(type(n), comp.name, cls))
+
     def action_subspace_names(self):
         """([(name, n_actions)] of the mobile agents, [...] of the planner), in action-index
-        order (base_agent.py:116-171: "<Component>" or "<Component>.<sub-action>")."""
+        order (base_agent.py:116-171: "<Component>" or "<Component>.<sub-action>"), the subspaces of host components
+        (foundation.ActingComponent) at their place in the component list.  Every component's get_n_actions is read the
+        way the reference reads it (_subspaces_of: a wrong type is a TypeError, a dotted sub-name a NameError, where values
+        used to be passed through), and an ActingComponent is asked for both actor classes whatever its agent_subclasses
+        lists, as the reference asks every component (base_env.py:341-346)."""
         out = []
         for cls in ("BasicMobileAgent", "BasicPlanner"):
             names = []
             for comp in self._components:
-                if cls not in comp.agent_subclasses:
+                # (the reference asks every component, whatever its agent_subclasses: base_env.py:341-346)
+                if cls not in comp.agent_subclasses and not getattr(comp, "owns_action_subspaces", False):
                     continue
-                n = comp.get_n_actions(cls)
-                if n is None or n == 0:
-                    continue
-                if isinstance(n, int):
-                    names.append((comp.name, n))
-                else:
-                    names.extend(("%s.%s" % (comp.name, sub), int(k)) for sub, k in n)
+                for sub, k in self._subspaces_of(comp, cls):
+                    names.append((comp.name if sub is None else "%s.%s" % (comp.name, sub), k))
             out.append(names)
         return out[0], out[1]
+
+    def _write_host_masks(self, env_mask=None):
+        """The acting host components' masks -> their entries of the arena's flattened mask tensors (the kernels leave
+        1.0 there whenever they rewrite a row), on the state as it stands: behind the launch that ends a step and
+        behind a reset's last launch (base_env.py:700-703: _generate_masks follows scenario_step).  env_mask: the rows
+        a masked reset touched; the others keep what they show."""
+        if not self._acting_components:
+            return
+        import torch
+
+        if self._host_mask_slots is None:  # per acting component: [(actor class, sub-action name, offset, size)], once
+            from .obs_keys import mask_keys
+
+            if self._mask_key_views is None:
+                self._mask_key_views = mask_keys(self)
+            table = {who: {key: (off, size) for key, off, size in self._mask_key_views[who]} for who in ("a", "p")}
+            self._host_mask_slots = [
+                (comp, [(who, sub) + table[who][comp.name if sub is None else "%s.%s" % (comp.name, sub)]
+                        for who in ("a", "p") for sub in comp._action_columns[who]])
+                for comp in self._acting_components]
+        t = self.backend.tensors
+        rows = None if env_mask is None else env_mask.to(torch.bool)
+        for comp, slots in self._host_mask_slots:
+            masks = comp.generate_masks(t, completions=t["completions"]) or {}
+            for who, sub, off, size in slots:
+                tensor, lead = (t["obs_a_action_mask"], 2) if who == "a" else (t["obs_p_action_mask"], 1)
+                got = masks.get(who)
+                m = got.get(sub) if isinstance(got, dict) else (got if sub is None else None)
+                dst = tensor.narrow(-1, off, size)
+                if m is None:  # a missing entry: everything allowed
+                    m = torch.ones_like(dst)
+                else:
+                    m = torch.as_tensor(m, device=dst.device)
+                    if tuple(m.shape) != tuple(dst.shape):
+                        raise ValueError("{}.generate_masks: the {} mask{} has shape {}, expected {}".format(
+                            comp.name, "agents'" if who == "a" else "planner's", "" if sub is None else " " + repr(sub),
+                            tuple(m.shape), tuple(dst.shape)))
+                    m = (m != 0).to(dst.dtype)
+                if rows is not None:
+                    m = torch.where(rows.view((-1,) + (1,) * lead), m, dst)
+                dst.copy_(m)
 
     def host_pre_reset(self, env_mask):
         """Hook for scenarios whose reset has a host-side part (e.g. uniform/...: a fresh
@@ -574,6 +662,7 @@ class BaseEnvironment:
             comp.component_step(be.tensors)
             lo = hi
         be.step_range(a, p, lo, self._n_builtin_components, _cabi.STEP_TAIL | (_cabi.STEP_HEAD if first else 0))
+        self._write_host_masks()
 
     def _host_observations(self, obs):
         """Adds the host components' observations to the raw observation dict: under "<Component>-<key>" and, with

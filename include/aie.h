@@ -49,7 +49,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define AIE_ABI_VERSION 10
+#define AIE_ABI_VERSION 11
 
 #define AIE_MAX_AGENTS 64      /* mobile agents per replica, spatial scenarios (one lane each) */
 #define AIE_MAX_AGENTS_WIDE 128 /* mobile agents per replica, map-less one-step-economy        */
@@ -57,6 +57,7 @@ extern "C" {
 #define AIE_MAX_BRACKETS 16
 #define AIE_MAX_RATES 64       /* discretised tax rates per bracket                     */
 #define AIE_MAX_SUBSPACES 16   /* action subspaces per agent class                      */
+#define AIE_MAX_HOST_SUBSPACES 8 /* of them: subspaces of host components per agent class (aie_config.host_*) */
 #define AIE_N_RES 2            /* collectible resources, sorted: 0 = Stone, 1 = Wood    */
 #define AIE_MT_N 624
 /* aie_config.rng_mode: which generator feeds the replicas' np.random.* draws (agent orders, pick-up bonus, resource
@@ -301,6 +302,28 @@ typedef struct aie_config {
   int32_t mz_rows, mz_cols;          /* multi_zone: num_partitions_row / _col                                        */
   int32_t mz_zones[3];               /* multi_zone: number of Wood, Stone, Wood+Stone zones                          */
   int32_t layout_pad_;
+
+  /* Action subspaces of HOST components (ABI 11; foundation.ActingComponent): a component of the user's that runs as
+   * host code between two aie_step_range launches may own action subspaces the way the reference's components do
+   * (get_n_actions, F/base/base_component.py:159-176; F/base/base_agent.py:97-180 lays the subspaces of every listed
+   * component out in registration order).  The library knows nothing of such a component but where its subspaces sit:
+   * subspace k of the mobile agents has host_a_dim[k] >= 1 choices (NO-OP not counted) and host_a_before[k] of the
+   * built-in `components` are listed ahead of it (0 .. n_components, non-decreasing in k; equal values keep the order
+   * of k); host_p_* likewise for the planner.  All zero: the layout of ABI 10.  Such subspaces take their single-action
+   * indices, multi-action columns and flattened-mask entries in that order; the step kernel decodes their sub-actions
+   * (0 = NO-OP, 1 .. dim = the choice; out of range: AIE_ERR_*_ACTION and NO-OP) into the tensors
+   *   host_actions_a  int32 [E, n_agents, host_a_n]      host_actions_p  int32 [E, host_p_n]
+   * (present when the count is > 0; plain arena regions, outside the replicas' records) in the step's first launch
+   * (AIE_STEP_HEAD) and writes 1.0 into their mask entries whenever it rewrites a mask row; the host overwrites those
+   * entries with the component's own masks (generate_masks, F/base/base_component.py:262-290) behind every launch that
+   * writes observations.  Gather-trade-build scenarios; such an environment always runs the full-featured kernel.
+   * Samplers: the agents' rows follow the layout in both action modes, and so does a single-action planner's one row.
+   * A multi-action planner's rows must be equally long for the samplers (aie_sample_random_actions,
+   * aie_sample_masked_actions, aie_sample_policy_actions): with a foreign planner subspace whose dimension differs from
+   * the tax rows' (or from another foreign one's) they return AIE_E_UNSUPPORTED and aie_last_error says so. */
+  int32_t host_a_n, host_p_n;
+  int32_t host_a_dim[AIE_MAX_HOST_SUBSPACES], host_a_before[AIE_MAX_HOST_SUBSPACES];
+  int32_t host_p_dim[AIE_MAX_HOST_SUBSPACES], host_p_before[AIE_MAX_HOST_SUBSPACES];
 } aie_config;
 #define AIE_LAYOUT_FIXED 0
 #define AIE_LAYOUT_UNIFORM 1
@@ -362,7 +385,9 @@ const char* aie_last_error(const aie_env* env /* NULL: last create error */);
  *   Saez          saez_buffer, saez_buffer_len, saez_reached_min_samples, saez_elas, saez_running_avg_tax_rates,
  *                 saez_next_rates
  *   dense log     log_event_count [L], log_events [L, cap, AIE_EV_WORDS]
- *   COVID         susceptible ... economic_index state rows, stringency_history_chunks, model_* constants */
+ *   COVID         susceptible ... economic_index state rows, stringency_history_chunks, model_* constants
+ *   host actions  host_actions_a [E, n, host_a_n], host_actions_p [E, host_p_n]: the decoded sub-actions of host
+ *                 components' action subspaces (aie_config.host_*), written by the first launch of a step */
 int aie_num_tensors(const aie_env* env);
 int aie_tensor_at(const aie_env* env, int index, aie_tensor_desc* out);
 int aie_get_tensor(const aie_env* env, const char* name, aie_tensor_desc* out);
