@@ -243,6 +243,7 @@ EXPORTED_SYMBOLS = [
     "aie_arena_info", "aie_step_range",
 ]
 STEP_HEAD, STEP_TAIL, STEP_OBSERVE, STEP_REBASE, STEP_RETAX = 1, 2, 4, 8, 16  # AIE_STEP_*
+STEP_REGEN, STEP_EMIT, STEP_CLOSE = 64, 128, 256  # the end of a step in three parts (scenario hooks run between them)
 ARENA_ALLOCATORS = ["caller", "hipMalloc", "vmm"]  # AIE_ARENA_*
 KERNEL_AUTO, KERNEL_GENERIC = 0, 1
 KERNEL_INSTANCE_JIT = 1000

@@ -572,11 +572,26 @@ int aie_step_range(aie_env* env, const int32_t* d_actions_a, const int32_t* d_ac
              "dense-log replica records");
     return AIE_E_UNSUPPORTED;
   }
-  if (comp_lo < 0 || comp_hi < comp_lo || comp_hi > P.c.n_components || phases < 0 || phases > 31 ||
-      ((phases & AIE_STEP_OBSERVE) && (phases & ~(AIE_STEP_OBSERVE | AIE_STEP_REBASE | AIE_STEP_RETAX))) ||
+  const int32_t split = AIE_STEP_REGEN | AIE_STEP_EMIT | AIE_STEP_CLOSE;
+  const int32_t known = AIE_STEP_HEAD | AIE_STEP_TAIL | AIE_STEP_OBSERVE | AIE_STEP_REBASE | AIE_STEP_RETAX | split;
+  if (comp_lo < 0 || comp_hi < comp_lo || comp_hi > P.c.n_components || phases < 0 || (phases & ~known) ||
+      (!(phases & split) && (phases & AIE_STEP_OBSERVE) && (phases & ~(AIE_STEP_OBSERVE | AIE_STEP_REBASE | AIE_STEP_RETAX))) ||
       ((phases & (AIE_STEP_REBASE | AIE_STEP_RETAX)) && !(phases & AIE_STEP_OBSERVE))) {
     snprintf(env->err, sizeof(env->err), "aie_step_range: components [%d, %d) of %d, phases %d", comp_lo, comp_hi, P.c.n_components, phases);
     return AIE_E_INVALID;
+  }
+  if (phases & split) {  // the split tail (include/aie.h): what may share a launch
+    const bool regen = phases & AIE_STEP_REGEN, emit = phases & AIE_STEP_EMIT, close = phases & AIE_STEP_CLOSE;
+    const char* bad = nullptr;
+    if (phases & (AIE_STEP_TAIL | AIE_STEP_OBSERVE)) bad = "REGEN / EMIT / CLOSE exclude TAIL and OBSERVE";
+    else if (close && comp_hi > comp_lo) bad = "CLOSE takes no component range";
+    else if (close && regen && !emit) bad = "REGEN | CLOSE without EMIT";
+    else if (close && !emit && (phases & AIE_STEP_HEAD)) bad = "HEAD | CLOSE without EMIT";
+    else if (emit && !regen && (comp_hi > comp_lo || (phases & AIE_STEP_HEAD))) bad = "EMIT with components or HEAD but without REGEN";
+    if (bad) {
+      snprintf(env->err, sizeof(env->err), "aie_step_range: %s (components [%d, %d), phases %d)", bad, comp_lo, comp_hi, phases);
+      return AIE_E_INVALID;
+    }
   }
   AIE_HIP_CHECK(env, hipSetDevice(env->device));
   NextActions next{};
@@ -587,7 +602,7 @@ int aie_step_range(aie_env* env, const int32_t* d_actions_a, const int32_t* d_ac
   next.mask = d_env_mask;
   hipLaunchKernelGGL(aie_step_kernel_log, dim3((unsigned)P.E), dim3(2 * AIE_NT), env->lds, static_cast<hipStream_t>(stream),
                      env->d_params, env->arena, d_actions_a, d_actions_p, next);
-  if ((phases & AIE_STEP_TAIL) && P.auto_reset)  // as behind aie_step: the replicas this step finished restart right behind it
+  if ((phases & (AIE_STEP_TAIL | AIE_STEP_CLOSE)) && P.auto_reset)  // as behind aie_step: the replicas this step finished restart right behind it
     aie_launch_gtb_reset(env, env->arena + P.a_done, 1, stream);
   AIE_HIP_CHECK(env, hipGetLastError());
   return AIE_OK;

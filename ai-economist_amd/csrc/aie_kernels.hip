@@ -2773,8 +2773,8 @@ struct NextActions {  // aie_step_sample_next: where and how to sample the next 
   int64_t env_offset;  // (the draw index `t` of the counter RNG is the replica's own record field o_sample_t)
   // aie_step_range (custom host components, include/aie.h): the built-in components [comp_lo, comp_hi) of the list and
   // the parts of a step this launch performs -- AIE_STEP_HEAD (timestep += 1), AIE_STEP_TAIL (regeneration, observations,
-  // masks, rewards, done), AIE_STEP_OBSERVE (observations and masks of the state as it stands, nothing else); phase == 0:
-  // a whole step.  Honoured by the full-featured kernel only (aie_step_kernel_log); everybody else steps whole steps.
+  // masks, rewards, done; or its three parts AIE_STEP_REGEN / EMIT / CLOSE, which scenario hooks run between),
+  // AIE_STEP_OBSERVE (observations and masks of the state as it stands, nothing else); phase == 0: a whole step.  Honoured by the full-featured kernel only (aie_step_kernel_log); everybody else steps whole steps.
   int32_t comp_lo, comp_hi, phase;
   // aie_step_range: the replicas the launch touches (uint8 [E], nonzero = yes), nullptr = all of them -- a masked reset's
   // follow-up launches leave the replicas it did not reset alone.  The full-featured kernel only, like the ranges above.
@@ -2799,12 +2799,22 @@ __device__ __forceinline__ float* rew_log_claim(const aie_params& R, int32_t* sl
 }
 // rewards of the step (compute_reward, layout_from_file.py:519-559), the reward log's slot, `done` and the completed-episode
 // count: one wave
-__device__ __forceinline__ void step_rewards_and_done(const aie::Ctx& c, uint8_t* __restrict__ arena, const NextActions& next, int skip) {
+// (emit / close: the halves of a split tail, include/aie.h AIE_STEP_EMIT / AIE_STEP_CLOSE -- both true in a whole step.  EMIT
+// alone computes the rewards into the arena and claims nothing; CLOSE alone fills the slot from the arena's rewards as
+// they stand, which the host may have edited in between)
+__device__ __forceinline__ void step_rewards_and_done(const aie::Ctx& c, uint8_t* __restrict__ arena, const NextActions& next, int skip,
+                                                      bool emit = true, bool close = true) {
   using namespace aie;
-  float* const rew_log = rew_log_claim(c.R, R_I32(c, o_rew_slot), R_I32(c, o_rew_epoch), c.R.E, c.P.n, c.tid == 0);
-  if (!(skip & 16)) compute_rewards(c, arena, rew_log);
+  float* const rew_log = close ? rew_log_claim(c.R, R_I32(c, o_rew_slot), R_I32(c, o_rew_epoch), c.R.E, c.P.n, c.tid == 0) : nullptr;
+  if (emit) {
+    if (!(skip & 16)) compute_rewards(c, arena, rew_log);
+  } else if (rew_log && c.tid <= c.P.n) {
+    const int n = c.P.n, i = c.tid;
+    rew_log[(int64_t)c.e * (n + 2) + i] = i < n ? reinterpret_cast<const float*>(arena + c.R.a_rew_a)[(int64_t)c.e * n + i]
+                                                : reinterpret_cast<const float*>(arena + c.R.a_rew_p)[c.e];
+  }
   AIE_WSYNC();
-  if (c.tid == 0) {
+  if (close && c.tid == 0) {
     const int done = *R_I32(c, o_timestep) >= c.R.c.episode_length;
     (arena + c.R.a_done)[c.e] = (uint8_t)done;
     if (rew_log) rew_log[(int64_t)c.e * (c.P.n + 2) + c.P.n + 1] = done ? 1.0f : 0.0f;
@@ -2867,6 +2877,9 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
   const bool HEAD = ph == 0 || (ph & 1), TAIL = ph == 0 || (ph & 2), OBSERVE = ph != 0 && (ph & 4) && !(ph & 2);
   const bool REBASE = OBSERVE && (ph & 8);  // utilities := current (the reward baseline a reset leaves, layout_from_file.py:347-349)
   const bool RETAX = OBSERVE && (ph & 16);  // PeriodicBracketTax's reset-time snapshot of the agents' coin (redistribution.py:1106-1110)
+  // the split tail (AIE_STEP_REGEN / EMIT / CLOSE): TAIL is all three
+  const bool REGEN = TAIL || (ph & 64), EMIT = TAIL || (ph & 128), CLOSE = TAIL || (ph & 256);
+  const bool CLOSE_ONLY = CLOSE && !EMIT;  // (aie_step_range: then without HEAD, REGEN or components -- the state stays as it is)
   const int c_lo = ph ? next.comp_lo : 0, c_hi = ph ? next.comp_hi : P.c.n_components;
   // The two waves run two separate ARMS from here to the end, each with its own copy of the four workgroup barriers
   // (the branch is wave-uniform, every wave passes the same number of them): a value that only one wave carries --
@@ -2938,9 +2951,9 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
       if (c.tid < P.n) R_F64(c, o_tax_last_coin)[c.tid] = R_F64(c, o_inv_coin)[c.tid] + R_F64(c, o_esc_coin)[c.tid];
       AIE_WSYNC();
     }
-    if (!(skip & 8) && (TAIL || OBSERVE)) write_flat_observations(c, arena);
+    if (!(skip & 8) && (EMIT || OBSERVE)) write_flat_observations(c, arena);
     if (TRACE && R.dev_trace && c.tid == 0) R.dev_trace[12 * blockIdx.x + 10] = wall_clock64();
-    if (!REW_ON_W1 && TAIL) step_rewards_and_done(c, arena, next, skip);
+    if (!REW_ON_W1 && (EMIT || CLOSE)) step_rewards_and_done(c, arena, next, skip, EMIT, CLOSE);
     if (REBASE) {  // (reset_body's last lines: the metrics of the state as the host's reset hooks left it)
       AIE_WSYNC();
       current_metrics(c);
@@ -3024,7 +3037,7 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
       mt_rows_from_hbm(m, gkey, c.tid);
     }
     m.pos = uni(*R_I32(c, o_mt_pos));
-    if (TAIL) {
+    if (REGEN) {
       if (!(skip & 2)) scenario_step_regen(c, m, src);
       if (c.tid == 0) {
         *R_I32(c, o_mt_pos) = m.pos;
@@ -3036,18 +3049,18 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
     AIE_WSYNC();
     // (the masks follow the map observations' rule: in place unless something outside the kernels touched the state)
     const bool masks_all = OBSERVE || !uni(*R_I32(c, o_obs_valid)) || (skip & (4 | 32768)) != 0;
-    if (!(skip & 4) && (TAIL || OBSERVE)) {
+    if (!(skip & 4) && (EMIT || OBSERVE)) {
       // the map observations of the previous step are still in the arena: update them in place,
       // unless something outside the kernels touched the state (obs_valid == 0; an AIE_STEP_OBSERVE launch: always)
       if (uni(*R_I32(c, o_obs_valid)) && !(skip & 32768) && !OBSERVE) update_spatial_observations(c, arena);
       else write_spatial_observations(c, arena);
       if (c.tid == 0) *R_I32(c, o_obs_valid) = 1;
-    } else if (!TAIL && !OBSERVE && c.tid == 0) {
+    } else if (!EMIT && !OBSERVE && !CLOSE_ONLY && c.tid == 0) {
       *R_I32(c, o_obs_valid) = 0;  // a partial step changed the state and wrote no observations: the launch that does starts over
     }
-    if (!(skip & 8) && (TAIL || OBSERVE)) write_action_masks(c, arena, /*all=*/masks_all);
+    if (!(skip & 8) && (EMIT || OBSERVE)) write_action_masks(c, arena, /*all=*/masks_all);
     if (TRACE && R.dev_trace && c.tid == 0) R.dev_trace[12 * blockIdx.x + 11] = wall_clock64();
-    if (REW_ON_W1 && TAIL) step_rewards_and_done(c, arena, next, skip);
+    if (REW_ON_W1 && (EMIT || CLOSE)) step_rewards_and_done(c, arena, next, skip, EMIT, CLOSE);
     __builtin_amdgcn_s_setprio(0);
     __syncthreads();  // (5)
     if (!(skip & 32)) store_record_step(c, arena, 1, NW);

@@ -212,7 +212,8 @@ class DeviceBackend:
 
     def step_range(self, actions_a, actions_p, comp_lo, comp_hi, phases, mask=None):
         """aie_step_range: the built-in components [comp_lo, comp_hi) and the named parts of a step (_cabi.STEP_HEAD /
-        STEP_TAIL / STEP_OBSERVE) -- what foundation.BatchedComponent hooks run between.  mask: uint8 [E] device tensor
+        STEP_TAIL / STEP_OBSERVE, or the end of a step in its parts STEP_REGEN / STEP_EMIT / STEP_CLOSE) -- what
+        foundation.BatchedComponent hooks and scenario hooks run between.  mask: uint8 [E] device tensor
         of the replicas the launch touches (a masked reset's follow-up launches), None = all."""
         torch = _torch()
         a = self._ptr(actions_a, torch.int32, "actions_a", self.act_a_numel)

@@ -9,7 +9,11 @@ Same entry points as the reference package (F/__init__.py:7-18):
 
 `foundation.scenarios / components / agents / resources / landmarks / endogenous`
 are the registries; register your own Scenario/Component spec classes with
-`@foundation.scenarios.add` / `@foundation.components.add`.
+`@foundation.scenarios.add` / `@foundation.components.add`.  A component of your own subclasses
+`foundation.BatchedComponent` / `foundation.ActingComponent`; a scenario of your own subclasses one of the
+gather-trade-build scenarios (`foundation.scenarios.get("layout_from_file/simple_wood_and_stone")`, `uniform/...`, ...) and
+overrides the scenario hooks `scenario_step`, `generate_observations`, `compute_reward`, `additional_reset_steps` and
+`scenario_metrics` (foundation/base_env.py) as torch code over the batch.
 """
 from .components import ActingComponent, BaseComponent, BatchedComponent  # noqa: F401  (base classes of user-registered components)
 from .components import component_registry as components

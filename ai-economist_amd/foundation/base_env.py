@@ -32,6 +32,11 @@ class BaseEnvironment:
     supports_unflattened_observations = False
     # host components (foundation.BatchedComponent) run between launches of aie_step_range: gather-trade-build scenarios
     supports_batched_components = False
+    # scenario hooks (below: scenario_step, generate_observations, compute_reward, additional_reset_steps).  False: the
+    # built-in scenario_step -- the resource regeneration -- is skipped altogether, the user's scenario_step that does not
+    # call super(); the replicas' random streams then do not advance at the end of a step
+    builtin_regeneration = True
+    SCENARIO_HOOKS = ("scenario_step", "generate_observations", "compute_reward", "additional_reset_steps")
 
     def __init__(self, components=None, n_agents=None, world_size=None, episode_length=1000,
                  multi_action_mode_agents=False, multi_action_mode_planner=True,
@@ -167,6 +172,18 @@ class BaseEnvironment:
                                    and (c._action_columns["a"] or c._action_columns["p"])]
         self._n_builtin_components = n_builtin
         self._host_obs_tables = None
+        # the scenario hooks this class overrides (a registered subclass that overrides none steps exactly as its parent)
+        self._scenario_hooks = tuple(h for h in self.SCENARIO_HOOKS
+                                     if getattr(type(self), h) is not getattr(BaseEnvironment, h))
+        if not self.builtin_regeneration:
+            self._scenario_hooks += ("builtin_regeneration=False",)
+        if self._scenario_hooks:
+            if not self.supports_batched_components:
+                raise NotImplementedError("scenario hooks ({}) run in the gather-trade-build scenarios only; {} derives from "
+                                          "the {} scenario".format(", ".join(self._scenario_hooks), type(self).__name__, self.name))
+            if dense_log_frequency is not None:
+                raise NotImplementedError("scenario hooks and dense logs do not combine yet (the logged replica's "
+                                          "event rows are per launch)")
         self._host_mask_slots = None
 
         self._completions = 0
@@ -278,6 +295,8 @@ class BaseEnvironment:
             self._backend = DeviceBackend(self.build_config(), self.layout_planes(),
                                           device=self._device)
             self._backend.host_components = tuple(comp.name for _, comp in self._host_components)
+            if self._scenario_hooks:  # refused what host components are refused, by the same mechanism
+                self._backend.host_components += ("the scenario hooks of %s: %s" % (type(self).__name__, ", ".join(self._scenario_hooks)),)
             self.upload_model_constants(self._backend)
             if self._pending_seed is not None:
                 self._backend.seed(self._pending_seed + self.env_offset)
@@ -317,9 +336,9 @@ class BaseEnvironment:
     def _obs(self):
         obs = self._obs_raw()
         host = None
-        if self._host_components:
+        if self._host_components or "generate_observations" in self._scenario_hooks:
             merged = self._host_observations(obs)
-            host = {who: merged[who].pop("_host_keys", {}) for who in ("a", "p")}
+            host = {who: dict(merged[who].pop("_host_keys", {}), **merged[who].pop("_host_multi", {})) for who in ("a", "p")}
             if self._flatten_observations or self.supports_unflattened_observations:
                 obs = merged
         if not self._flatten_observations and not self.supports_unflattened_observations:
@@ -453,7 +472,7 @@ class BaseEnvironment:
             self._replay_log = {"reset": dict(seed_state=self.rng_state(0) if self._dense_log_this_episode else None),
                                 "step": []}
         self.host_pre_reset(env_mask)
-        if self._host_components and env_mask is not None:
+        if (self._host_components or self._scenario_hooks) and env_mask is not None:
             env_mask = env_mask.clone()  # (often the live `done` tensor, which the reset clears; the hooks need it afterwards)
         self.backend.reset(env_mask)
         if self._host_components:
@@ -475,6 +494,13 @@ class BaseEnvironment:
             if edited_ahead or edited_behind:  # the reset kernel's observations no longer show the state: rewrite them
                 retax = _cabi.STEP_RETAX if (tax_at is not None and edited_ahead and not retaken) else 0
                 self.backend.step_range(None, None, 0, 0, _cabi.STEP_OBSERVE | _cabi.STEP_REBASE | retax, mask=env_mask)
+        if "additional_reset_steps" in self._scenario_hooks:
+            # the scenario's own reset steps come last (base_env.py:905-911); the built-in ones -- the baseline the first
+            # rewards are measured from (layout_from_file.py:564-600) -- and the tax component's snapshot were taken ahead of
+            # them: the observations are rewritten, the baseline and the snapshot are not
+            if bool(self.additional_reset_steps(self.backend.tensors, env_mask)):
+                self.backend.step_range(None, None, 0, 0, _cabi.STEP_OBSERVE, mask=env_mask)
+        if self._host_components:
             self._write_host_masks(env_mask)
         if log_replica_resets:
             self._dense_log = {"world": [], "states": [], "actions": [], "rewards": []}
@@ -630,7 +656,7 @@ class BaseEnvironment:
             self._dense_logger.before_step(a, p)
             self._replay_log["step"].append(dict(actions=self._dense_logger.reference_actions(a, p),
                                                  seed_state=self.rng_state(0)))
-        if self._host_components:
+        if self._host_components or self._scenario_hooks:
             self._step_with_host_components(a, p)
         else:
             self.backend.step(a, p)
@@ -646,23 +672,113 @@ class BaseEnvironment:
         info = {"a": {}, "p": {}}
         return self._obs(), rew, done, info
 
+    @property
+    def scenario_hooks(self):
+        """Names of the scenario hooks this environment's class overrides ("builtin_regeneration=False" among them when
+        the attribute is off); empty: the environment steps with whole-step launches, exactly as its parent class."""
+        return self._scenario_hooks
+
+    def step_plan(self):
+        """What one env.step does, in order, decided at construction (no device needed): ("launch", comp_lo, comp_hi,
+        phases) -- one aie_step_range call -- ("component", name), ("scenario_step",) and ("compute_reward",) -- host
+        hooks.  Without host components and scenario hooks: [] (a whole-step aie_step launch on the configuration's
+        own kernel).  As few launches as the hooks allow: the regeneration joins the last stretch of components,
+        observations, rewards and the end of the step share a launch unless compute_reward runs between them."""
+        if not self._host_components and not self._scenario_hooks:
+            return []
+        H, T = _cabi.STEP_HEAD, _cabi.STEP_TAIL
+        plan, lo, first = [], 0, True
+        for hi, comp in self._host_components:
+            if first or hi > lo:
+                plan.append(("launch", lo, hi, H if first else 0))  # (0: a plain middle stretch)
+            first = False
+            plan.append(("component", comp.name))
+            lo = hi
+        nb, head = self._n_builtin_components, (H if first else 0)
+        regen = _cabi.STEP_REGEN if self.builtin_regeneration else 0
+        between_a, between_b = "scenario_step" in self._scenario_hooks, "compute_reward" in self._scenario_hooks
+        if regen and not between_a and not between_b:  # nothing runs inside the end of the step
+            plan.append(("launch", lo, nb, T | head))
+            return plan
+        if between_a or not regen:  # the last stretch (and the regeneration) on its own, if there is anything in it
+            if first or nb > lo or regen:
+                plan.append(("launch", lo, nb, head | regen))
+            if between_a:
+                plan.append(("scenario_step",))
+            lo, head, regen = nb, 0, 0
+        if between_b:
+            plan.append(("launch", lo, nb, head | regen | _cabi.STEP_EMIT))
+            plan.append(("compute_reward",))
+            plan.append(("launch", nb, nb, _cabi.STEP_CLOSE))
+        else:
+            plan.append(("launch", nb, nb, _cabi.STEP_EMIT | _cabi.STEP_CLOSE))
+        return plan
+
+    def planned_launches(self):
+        """The (comp_lo, comp_hi, phases) sequence of aie_step_range calls one env.step makes (step_plan without the hooks)."""
+        return [tuple(item[1:]) for item in self.step_plan() if item[0] == "launch"]
+
     def _step_with_host_components(self, a, p):
-        """One step with foundation.BatchedComponent hooks: the built-in components in stretches (aie_step_range), the
-        hooks between them in list order (base_env.py:985-987), the end of the step in the last launch."""
+        """One step with foundation.BatchedComponent hooks and scenario hooks (step_plan): the built-in components in
+        stretches (aie_step_range), the components' hooks between them in list order (base_env.py:985-987), then the end
+        of the step -- in one launch, or in the parts the scenario's hooks run between."""
         be = self.backend
         if a is None or p is None:  # every launch of the step decodes the same buffers
             za, zp = be._action_buffers(0)
             a = za.zero_() if a is None else a
             p = zp.zero_() if p is None else p
-        lo, first = 0, True
-        for hi, comp in self._host_components:
-            if first or hi > lo:
-                be.step_range(a, p, lo, hi, _cabi.STEP_HEAD if first else 0)  # (0: a plain middle stretch)
-            first = False
-            comp.component_step(be.tensors)
-            lo = hi
-        be.step_range(a, p, lo, self._n_builtin_components, _cabi.STEP_TAIL | (_cabi.STEP_HEAD if first else 0))
+        t = be.tensors
+        for item in self.step_plan():
+            if item[0] == "launch":
+                be.step_range(a, p, item[1], item[2], item[3])
+            elif item[0] == "component":
+                self._components_dict[item[1]].component_step(t)
+            elif item[0] == "scenario_step":
+                self.scenario_step(t)
+            else:  # compute_reward: the built-in rewards are in the arena; the hook edits them or returns replacements
+                rew = {"a": t["rewards_a"], "p": t["rewards_p"]}
+                out = self.compute_reward(t, rew)
+                if out is not None:
+                    for who in ("a", "p"):
+                        if out.get(who) is not None and out[who] is not rew[who]:
+                            rew[who].copy_(out[who])
         self._write_host_masks()
+
+    # ---- scenario hooks: the reference's scenario contract (F/base/base_env.py:1037-1141) over the batch ----
+    def scenario_step(self, tensors):
+        """Hook: the user's part of the reference's `scenario_step` (called between the components and the observations,
+        F/base/base_env.py:1005), as torch code on the zero-copy state tensors of all replicas (`tensors`, as
+        BatchedComponent.component_step gets them).  It runs AFTER the built-in scenario_step -- the resource regeneration
+        -- and before anybody observes: the reference user's `super().scenario_step(); <own code>`.  A class that sets
+        `builtin_regeneration = False` skips the built-in part (a scenario_step that does not call super()); the replicas'
+        random streams then do not advance at the end of a step.  Code that should run AHEAD of the regeneration is a
+        host component (foundation.BatchedComponent) listed last.  Gather-trade-build scenarios only; cannot draw from
+        a replica's NumPy stream."""
+        return None
+
+    def generate_observations(self, tensors):
+        """Hook: additional scenario observations, {"a": {key: [n_envs, n_agents(, k)]}, "p": {key: [n_envs(, k)]}}.
+        They enter as "world-<key>": scalars and vectors at their sorted-key position of the flat vectors (F/base/
+        base_env.py:644-663, 587), or under that name with flatten_observations=False; values with more than one
+        dimension per actor stay under their own key in both forms (F/base/base_env.py:572-583).  A key a built-in
+        observation already has is a ValueError; per-agent planner blocks ("p<i>") are not supported."""
+        return {"a": {}, "p": {}}
+
+    def compute_reward(self, tensors, rew):
+        """Hook: `rew = super().compute_reward(); <own code>`.  rew = {"a": rewards_a [n_envs, n_agents], "p": rewards_p
+        [n_envs]} (float32, the arena's own tensors) holds the built-in rewards of this step; edit them in place or return
+        {"a": ..., "p": ...} replacements.  Runs after the observations were written and before the step closes: the
+        reward log's slot and the rewards env.step returns show the edited values.  The built-in utility baseline and the
+        auto-warmup count follow the built-in rewards, as they do behind super() in the reference."""
+        return None
+
+    def additional_reset_steps(self, tensors, env_mask=None):
+        """Hook: `super().additional_reset_steps(); <own code>` -- runs after the reset kernel and after every host
+        component's reset hook; env_mask: uint8 [n_envs] of the replicas that were reset (None: all), leave the others
+        alone.  Return True when state tensors were edited: the observations are then rewritten.  The baseline the first
+        rewards are measured from and PeriodicBracketTax's coin snapshot were taken before it (layout_from_file.py:564-600,
+        base_env.py:903-911) and stay."""
+        return False
 
     def _host_observations(self, obs):
         """Adds the host components' observations to the raw observation dict: under "<Component>-<key>" and, with
@@ -671,42 +787,87 @@ class BaseEnvironment:
         import torch
 
         be = self.backend
-        extra = {"a": {}, "p": {}}
-        for _, comp in self._host_components:
-            o = comp.generate_observations(be.tensors) or {}
-            for who in ("a", "p"):
-                for k, v in (o.get(who) or {}).items():
-                    extra[who]["%s-%s" % (comp.name, k)] = v
+        extra = self.host_observation_values(be.tensors)
         if not extra["a"] and not extra["p"]:
             return obs
         if self._host_obs_tables is None:
-            from .obs_keys import flat_keys
-
-            base = flat_keys(self)
-            tables = {}
-            for who, lead in (("a", 2), ("p", 1)):  # leading dims: [E, n] / [E]
-                items = [(key, size, ("k", off)) for key, off, size, _ in base[who]]
-                col = base["sizes"][who]
-                for key in sorted(extra[who]):
-                    v = extra[who][key]
-                    size = 1 if v.dim() == lead else int(v.shape[-1])
-                    items.append((key, size, ("x", col)))
-                    col += size
-                perm = []
-                for key, size, (_src, off) in sorted(items, key=lambda it: it[0]):
-                    perm.extend(range(off, off + size))
-                tables[who] = torch.as_tensor(perm, dtype=torch.int64, device=be.device)
-            self._host_obs_tables = tables
+            perm = self.host_flat_keys(extra)["perm"]
+            self._host_obs_tables = {who: torch.as_tensor(perm[who], dtype=torch.int64, device=be.device) for who in ("a", "p")}
         out = {who: dict(d) for who, d in obs.items()}
         for who, lead in (("a", 2), ("p", 1)):
             if not extra[who]:
                 continue
-            parts = [obs[who]["flat"]]
+            parts, kept, multi = [obs[who]["flat"]], {}, {}
             for key in sorted(extra[who]):
-                v = extra[who][key].to(torch.float32)
+                v = extra[who][key]
+                if v.dim() > lead + 1:  # more than one dimension per actor: its own key, in both forms
+                    out[who][key] = multi[key] = v
+                    continue
+                kept[key] = v
+                v = v.to(torch.float32)
                 parts.append(v.unsqueeze(-1) if v.dim() == lead else v)
-            out[who]["flat"] = torch.cat(parts, dim=-1).index_select(-1, self._host_obs_tables[who])
-            out[who]["_host_keys"] = {k: extra[who][k] for k in extra[who]}
+            if len(parts) > 1:
+                out[who]["flat"] = torch.cat(parts, dim=-1).index_select(-1, self._host_obs_tables[who])
+            out[who]["_host_keys"], out[who]["_host_multi"] = kept, multi
+        return out
+
+    def host_observation_values(self, tensors):
+        """{"a": {full key: tensor}, "p": {...}} of what the host components ("<Component>-<key>") and the scenario's
+        generate_observations hook ("world-<key>") add to the observations, checked: a key that a built-in observation
+        or another hook already has is a ValueError, per-agent planner blocks ("p<i>") are refused."""
+        from .obs_keys import flat_keys
+
+        sources = [(comp.name, comp.generate_observations) for _, comp in self._host_components]
+        if "generate_observations" in self._scenario_hooks:
+            sources.append(("world", self.generate_observations))
+        base = flat_keys(self)
+        taken = {who: {key for key, _, _, _ in base[who]} | {"world-map", "world-idx_map", "action_mask", "flat"}
+                 for who in ("a", "p")}
+        extra = {"a": {}, "p": {}}
+        for name, fn in sources:
+            o = fn(tensors) or {}
+            for who in o:
+                if who not in ("a", "p"):
+                    if isinstance(who, str) and who[:1] == "p" and who[1:].isdigit():
+                        raise NotImplementedError(
+                            "{}: per-agent planner observation blocks ({!r}) are not supported; return {{'a': ..., 'p': ...}} "
+                            "(a planner observation over all agents is a vector under 'p')".format(name, who))
+                    raise ValueError("{}: observations are keyed 'a' (all mobile agents) and 'p' (planner), got {!r}".format(name, who))
+            for who in ("a", "p"):
+                for k, v in (o.get(who) or {}).items():
+                    key = "%s-%s" % (name, k)
+                    if key in taken[who]:
+                        raise ValueError("observation key {!r} is already taken ({} observations)".format(
+                            key, "agents'" if who == "a" else "planner's"))
+                    taken[who].add(key)
+                    extra[who][key] = v
+        return extra
+
+    def host_flat_keys(self, extra):
+        """The key tables of the flat vectors (obs_keys.flat_keys) with the additional scalar / vector keys of `extra`
+        (host_observation_values) at their sorted-key position: {"a": [(key, offset, size, scalar)], "p": [...],
+        "sizes": {...}, "perm": {who: for every merged column its column in [kernel's flat vector | extras in key order]}}.
+        Values with more than one dimension per actor are not part of the flat vectors."""
+        from .obs_keys import flat_keys
+
+        base = flat_keys(self)
+        out = {"pa": base["pa"], "sizes": dict(base["sizes"]), "perm": {}}
+        for who, lead in (("a", 2), ("p", 1)):  # leading dims: [E, n] / [E]
+            items = [(key, size, scalar, off) for key, off, size, scalar in base[who]]
+            col = base["sizes"][who]
+            for key in sorted(extra[who]):
+                v = extra[who][key]
+                if v.dim() > lead + 1:
+                    continue
+                size = 1 if v.dim() == lead else int(v.shape[-1])
+                items.append((key, size, v.dim() == lead, col))
+                col += size
+            table, perm, off = [], [], 0
+            for key, size, scalar, src in sorted(items, key=lambda it: it[0]):
+                table.append((key, off, size, scalar))
+                perm.extend(range(src, src + size))
+                off += size
+            out[who], out["perm"][who], out["sizes"][who] = table, perm, off
         return out
 
     def check_errors(self):
@@ -733,7 +894,9 @@ class BaseEnvironment:
     # ---- metrics (base_env.py:420-432) ----
     def scenario_metrics(self, tensors):
         """{metric key: ndarray [E]} from host copies of the state tensors; None if the
-        scenario reports nothing (reference: BaseEnvironment.scenario_metrics)."""
+        scenario reports nothing (reference: BaseEnvironment.scenario_metrics).  The fifth scenario hook: a
+        registered subclass extends it as in the reference (`m = super().scenario_metrics(tensors); m["mine"] = ...`);
+        it runs on the host whenever env.metrics is read and needs no launch of its own."""
         return None
 
     @property

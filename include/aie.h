@@ -458,8 +458,21 @@ int aie_step_sample_next_masked(aie_env* env, const int32_t* d_actions_a, const 
  *   AIE_STEP_OBSERVE  observations and masks of the state as it stands, nothing else (after a host-side edit, e.g. a
  *                     component's additional_reset_steps); with AIE_STEP_REBASE also the utilities the next rewards are
  *                     measured from, as a reset leaves them (layout_from_file.py:347-349 runs behind the components' resets)
+ * The end of a step in three parts, for scenario hooks that run INSIDE it (the reference's scenario_step,
+ * generate_observations and compute_reward, F/base/base_env.py:1005-1011):
+ *   AIE_STEP_REGEN    the built-in scenario_step: resource regeneration (the replica's generator advances and is stored).
+ *                     May share a launch with HEAD and a component range; it runs behind that launch's components.
+ *   AIE_STEP_EMIT     flat and spatial observations, action masks, and the built-in rewards into rewards_a / rewards_p
+ *                     (utility baseline and auto-warmup integrator included).  No reward-log slot, no done, no completions.
+ *   AIE_STEP_CLOSE    claims the reward-log slot and fills it from rewards_a / rewards_p AS THEY STAND in the arena (the host
+ *                     may have edited them behind EMIT), writes done, completions and the slot's done flag (+ auto-reset).
+ * REGEN, EMIT, CLOSE in one, two or three calls with no host edit in between leave every tensor bit-identical to TAIL;
+ * EMIT | CLOSE in one call is TAIL without regeneration.  They exclude TAIL and OBSERVE; CLOSE takes no component range and
+ * goes with REGEN or HEAD only when EMIT is set too; EMIT and CLOSE take an empty range unless REGEN rides along.
+ * obs_valid: a call that changes state without EMIT clears it (the EMIT that follows rewrites maps and masks in full), EMIT
+ * sets it, a CLOSE-only call leaves it alone.
  * (phases == 0: components only, a stretch in the middle of a step.)
- * One step = any sequence of calls whose first carries HEAD, whose last carries TAIL and whose ranges tile the list;
+ * One step = any sequence of calls whose first carries HEAD, whose last carries TAIL (or CLOSE) and whose ranges tile the list;
  * aie_step(a, p) == aie_step_range(a, p, 0, n_components, HEAD | TAIL).  Every call takes the same action buffers.
  * Between two calls of a step the caller may edit state tensors; the TAIL call rewrites all observations.  Always the
  * full-featured kernel (no compile-time / run-time instance).  Gather-trade-build scenarios; AIE_E_UNSUPPORTED elsewhere,
@@ -471,6 +484,9 @@ int aie_step_sample_next_masked(aie_env* env, const int32_t* d_actions_a, const 
 #define AIE_STEP_TAIL 2
 #define AIE_STEP_OBSERVE 4
 #define AIE_STEP_REBASE 8
+#define AIE_STEP_REGEN 64  /* (32 is taken: the library marks ranged launches with it) */
+#define AIE_STEP_EMIT 128
+#define AIE_STEP_CLOSE 256
 #define AIE_STEP_RETAX 16 /* with OBSERVE: PeriodicBracketTax's reset-time snapshot of the agents' coin (redistribution.py:1106-1110) taken
                            * again -- a host component listed AHEAD of the tax component edited coin in its reset hook */
 int aie_step_range(aie_env* env, const int32_t* d_actions_a, const int32_t* d_actions_p, int32_t comp_lo, int32_t comp_hi,
