@@ -837,11 +837,17 @@ int aie_sample_masked_actions(aie_env* env, uint64_t seed, int64_t global_env_of
   return AIE_OK;
 }
 
-int aie_sample_policy_actions(aie_env* env, const float* d_logits_a, const float* d_logits_p, uint64_t seed,
-                              int64_t global_env_offset, int32_t* d_actions_a, int32_t* d_actions_p, void* stream) {
+// aie_sample_policy_actions and aie_sample_policy_actions_logp: the same launch, the second on the LOGP instances
+static int aie_sample_policy_launch(aie_env* env, const float* d_logits_a, const float* d_logits_p, uint64_t seed,
+                                    int64_t global_env_offset, int32_t* d_actions_a, int32_t* d_actions_p, bool with_logp,
+                                    float* d_logp_a, float* d_logp_p, void* stream) {
   if (!env) return AIE_E_INVALID;
   if ((d_actions_a && !d_logits_a) || (d_actions_p && !d_logits_p)) {
     snprintf(env->err, sizeof(env->err), "aie_sample_policy_actions: an action buffer without its logits");
+    return AIE_E_INVALID;
+  }
+  if (with_logp && ((d_actions_a && d_logits_a && !d_logp_a) || (d_actions_p && d_logits_p && !d_logp_p))) {
+    snprintf(env->err, sizeof(env->err), "aie_sample_policy_actions_logp: an action buffer without its log-probability buffer");
     return AIE_E_INVALID;
   }
   if (aie_sampler_check(&env->P, env->err, sizeof(env->err)) != AIE_OK) return AIE_E_UNSUPPORTED;
@@ -858,17 +864,163 @@ int aie_sample_policy_actions(aie_env* env, const float* d_logits_a, const float
   }();
   const int rpb = 4 >> (wpr_log2 & 255);
   const aie_sampler_args S = aie_sampler_args_of(&env->P, env->d_params);
-  using sampler_fn = void (*)(const aie_sampler_args, uint8_t*, const float*, const float*, uint64_t, int64_t, int32_t*, int32_t*, int);
-  sampler_fn fn = aie_sample_policy_actions_kernel;  // rows of any shape
+  using sampler_fn = void (*)(const aie_sampler_args, uint8_t*, const float*, const float*, uint64_t, int64_t, int32_t*, int32_t*, int,
+                              const SamplerLogp<false>);
+  sampler_fn fn = aie_sample_policy_actions_kernel<false>;  // rows of any shape
   if (!S.ragged && S.agents.len <= 64 && S.planner.len <= 64) {  // every row one aligned lane segment: the fast instances
     static const sampler_fn fast[3][3] = {
-        {aie_sample_policy_fast_kernel<4, 4>, aie_sample_policy_fast_kernel<4, 5>, aie_sample_policy_fast_kernel<4, 6>},
-        {aie_sample_policy_fast_kernel<5, 4>, aie_sample_policy_fast_kernel<5, 5>, aie_sample_policy_fast_kernel<5, 6>},
-        {aie_sample_policy_fast_kernel<6, 4>, aie_sample_policy_fast_kernel<6, 5>, aie_sample_policy_fast_kernel<6, 6>}};
+        {aie_sample_policy_fast_kernel<4, 4, false>, aie_sample_policy_fast_kernel<4, 5, false>, aie_sample_policy_fast_kernel<4, 6, false>},
+        {aie_sample_policy_fast_kernel<5, 4, false>, aie_sample_policy_fast_kernel<5, 5, false>, aie_sample_policy_fast_kernel<5, 6, false>},
+        {aie_sample_policy_fast_kernel<6, 4, false>, aie_sample_policy_fast_kernel<6, 5, false>, aie_sample_policy_fast_kernel<6, 6, false>}};
     fn = fast[S.agents.lsh - 4][S.planner.lsh - 4];
   }
-  hipLaunchKernelGGL(fn, dim3((unsigned)((env->P.E + rpb - 1) / rpb)), dim3(256), 0, static_cast<hipStream_t>(stream), S,
-                     env->arena, d_logits_a, d_logits_p, seed, global_env_offset, d_actions_a, d_actions_p, wpr_log2);
+  const bool fast_rows = !S.ragged && S.agents.len <= 64 && S.planner.len <= 64;
+  const dim3 grid((unsigned)((env->P.E + rpb - 1) / rpb));
+  if (with_logp) {
+    using logp_fn = void (*)(const aie_sampler_args, uint8_t*, const float*, const float*, uint64_t, int64_t, int32_t*, int32_t*, int,
+                             const SamplerLogp<true>);
+    logp_fn lfn = aie_sample_policy_actions_kernel<true>;
+    if (fast_rows) {
+      static const logp_fn fast[3][3] = {
+          {aie_sample_policy_fast_kernel<4, 4, true>, aie_sample_policy_fast_kernel<4, 5, true>, aie_sample_policy_fast_kernel<4, 6, true>},
+          {aie_sample_policy_fast_kernel<5, 4, true>, aie_sample_policy_fast_kernel<5, 5, true>, aie_sample_policy_fast_kernel<5, 6, true>},
+          {aie_sample_policy_fast_kernel<6, 4, true>, aie_sample_policy_fast_kernel<6, 5, true>, aie_sample_policy_fast_kernel<6, 6, true>}};
+      lfn = fast[S.agents.lsh - 4][S.planner.lsh - 4];
+    }
+    SamplerLogp<true> LP;
+    LP.a = d_logp_a;
+    LP.p = d_logp_p;
+    hipLaunchKernelGGL(lfn, grid, dim3(256), 0, static_cast<hipStream_t>(stream), S, env->arena, d_logits_a, d_logits_p, seed,
+                       global_env_offset, d_actions_a, d_actions_p, wpr_log2, LP);
+  } else {
+    hipLaunchKernelGGL(fn, grid, dim3(256), 0, static_cast<hipStream_t>(stream), S, env->arena, d_logits_a, d_logits_p, seed,
+                       global_env_offset, d_actions_a, d_actions_p, wpr_log2, SamplerLogp<false>());
+  }
+  AIE_HIP_CHECK(env, hipGetLastError());
+  return AIE_OK;
+}
+
+int aie_sample_policy_actions(aie_env* env, const float* d_logits_a, const float* d_logits_p, uint64_t seed,
+                              int64_t global_env_offset, int32_t* d_actions_a, int32_t* d_actions_p, void* stream) {
+  return aie_sample_policy_launch(env, d_logits_a, d_logits_p, seed, global_env_offset, d_actions_a, d_actions_p, false, nullptr,
+                                  nullptr, stream);
+}
+
+int aie_sample_policy_actions_logp(aie_env* env, const float* d_logits_a, const float* d_logits_p, uint64_t seed,
+                                   int64_t global_env_offset, int32_t* d_actions_a, int32_t* d_actions_p, float* d_logp_a,
+                                   float* d_logp_p, void* stream) {
+  return aie_sample_policy_launch(env, d_logits_a, d_logits_p, seed, global_env_offset, d_actions_a, d_actions_p, true, d_logp_a,
+                                  d_logp_p, stream);
+}
+
+// The evaluation kernels' argument: the sampler's row shapes (aie_sampler_args_of), the caller's pointers, B batch elements.
+static int aie_policy_eval_args_of(aie_env* env, const char* who, int64_t B, const float* lg_a, const float* lg_p, const float* mk_a,
+                                   const float* mk_p, aie_policy_eval_args* out) {
+  if (aie_sampler_check(&env->P, env->err, sizeof(env->err)) != AIE_OK) return AIE_E_UNSUPPORTED;
+  if (B < 1 || (((lg_a && !mk_a) || (lg_p && !mk_p)) && B != env->P.E)) {
+    snprintf(env->err, sizeof(env->err), "%s: B = %lld; without the caller's masks (the arena's current ones) B must be the "
+             "environment's %d replicas", who, (long long)B, env->P.E);
+    return AIE_E_INVALID;
+  }
+  const aie_sampler_args S = aie_sampler_args_of(&env->P, env->d_params);
+  aie_policy_eval_args A;
+  memset(&A, 0, sizeof(A));
+  const aie_sampler_group* sg[2] = {&S.agents, &S.planner};
+  aie_policy_eval_group* eg[2] = {&A.agents, &A.planner};
+  const float* lg[2] = {lg_a, lg_p};
+  const float* mk[2] = {mk_a, mk_p};
+  for (int c = 0; c < 2; ++c) {
+    aie_policy_eval_group& G = *eg[c];
+    const aie_sampler_group& s = *sg[c];
+    G.lg = lg[c];
+    G.lg_bstride = s.lg_estride;
+    G.len = s.len;
+    G.lrs = s.lrs;
+    G.lsh = s.lsh;
+    G.rows = s.rows;
+    G.generic = (c == 0 && S.ragged) || s.len > 64;
+    if (mk[c]) {  // the caller's masks: the logits' layout
+      G.mk = mk[c];
+      G.mk_bstride = s.lg_estride;
+      G.mrs = s.lrs;
+      G.mks = 1;
+    } else {      // the arena's current masks
+      G.mk = reinterpret_cast<const float*>(env->arena + s.mk_off);
+      G.mk_bstride = s.mk_estride;
+      G.mrs = s.mrs;
+      G.mks = s.mks;
+    }
+    const int rpw = G.generic ? 1 : 64 >> s.lsh;
+    G.items = lg[c] ? (s.rows + rpw - 1) / rpw : 0;
+  }
+  A.params = env->d_params;
+  A.B = (uint32_t)B;
+  A.items = (uint32_t)(A.agents.items + A.planner.items);
+  A.act_a_width = S.act_a_width;
+  A.ragged = S.ragged;
+  if (A.items && B * (int64_t)A.items > 0x7fffff00ll) {
+    snprintf(env->err, sizeof(env->err), "%s: B = %lld is more than one launch takes (%u wavefronts per batch element)", who,
+             (long long)B, A.items);
+    return AIE_E_INVALID;
+  }
+  *out = A;
+  return AIE_OK;
+}
+
+int aie_policy_evaluate(aie_env* env, int64_t B, const float* d_logits_a, const float* d_logits_p, const float* d_masks_a,
+                        const float* d_masks_p, const int32_t* d_actions_a, const int32_t* d_actions_p, float* d_logp_a,
+                        float* d_logp_p, float* d_entropy_a, float* d_entropy_p, void* stream) {
+  if (!env) return AIE_E_INVALID;
+  if ((d_logp_a && !(d_logits_a && d_actions_a)) || (d_logp_p && !(d_logits_p && d_actions_p)) || (d_entropy_a && !d_logits_a) ||
+      (d_entropy_p && !d_logits_p)) {
+    snprintf(env->err, sizeof(env->err), "aie_policy_evaluate: an output without its logits (logp: and its stored actions)");
+    return AIE_E_INVALID;
+  }
+  aie_policy_eval_args A;
+  // (an actor class none of whose outputs is asked for is left out of the launch)
+  const int rc = aie_policy_eval_args_of(env, "aie_policy_evaluate", B, (d_logp_a || d_entropy_a) ? d_logits_a : nullptr,
+                                         (d_logp_p || d_entropy_p) ? d_logits_p : nullptr, d_masks_a, d_masks_p, &A);
+  if (rc != AIE_OK) return rc;
+  if (!A.items) return AIE_OK;
+  A.agents.act = d_actions_a;
+  A.planner.act = d_actions_p;
+  A.agents.logp = d_logp_a;
+  A.planner.logp = d_logp_p;
+  A.agents.ent = d_entropy_a;
+  A.planner.ent = d_entropy_p;
+  AIE_HIP_CHECK(env, hipSetDevice(env->device));
+  hipLaunchKernelGGL(aie_policy_eval_kernel, dim3((unsigned)((B * A.items + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), A);
+  AIE_HIP_CHECK(env, hipGetLastError());
+  return AIE_OK;
+}
+
+int aie_policy_evaluate_backward(aie_env* env, int64_t B, const float* d_logits_a, const float* d_logits_p, const float* d_masks_a,
+                                 const float* d_masks_p, const int32_t* d_actions_a, const int32_t* d_actions_p,
+                                 const float* d_glogp_a, const float* d_glogp_p, const float* d_gentropy_a,
+                                 const float* d_gentropy_p, float* d_grad_logits_a, float* d_grad_logits_p, void* stream) {
+  if (!env) return AIE_E_INVALID;
+  if ((d_grad_logits_a && !d_logits_a) || (d_grad_logits_p && !d_logits_p) || (d_glogp_a && !d_actions_a) ||
+      (d_glogp_p && !d_actions_p)) {
+    snprintf(env->err, sizeof(env->err), "aie_policy_evaluate_backward: a gradient buffer without its logits, or a logp gradient "
+             "without the stored actions");
+    return AIE_E_INVALID;
+  }
+  aie_policy_eval_args A;
+  const int rc = aie_policy_eval_args_of(env, "aie_policy_evaluate_backward", B, d_grad_logits_a ? d_logits_a : nullptr,
+                                         d_grad_logits_p ? d_logits_p : nullptr, d_masks_a, d_masks_p, &A);
+  if (rc != AIE_OK) return rc;
+  if (!A.items) return AIE_OK;
+  A.agents.act = d_actions_a;
+  A.planner.act = d_actions_p;
+  A.agents.g_logp = d_glogp_a;
+  A.planner.g_logp = d_glogp_p;
+  A.agents.g_ent = d_gentropy_a;
+  A.planner.g_ent = d_gentropy_p;
+  A.agents.grad = d_grad_logits_a;
+  A.planner.grad = d_grad_logits_p;
+  AIE_HIP_CHECK(env, hipSetDevice(env->device));
+  hipLaunchKernelGGL(aie_policy_eval_bwd_kernel, dim3((unsigned)((B * A.items + 3) / 4)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), A);
   AIE_HIP_CHECK(env, hipGetLastError());
   return AIE_OK;
 }

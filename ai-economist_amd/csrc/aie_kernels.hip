@@ -4121,6 +4121,19 @@ __device__ __forceinline__ float sampler_scan(float v, int seg) {
   return v;
 }
 // One work item in scalars: its first row; the other rows of a packed item follow at fixed strides.
+// The LOGP instances' extra kernel argument (aie_sample_policy_actions_logp): where the log-probability of every pick
+// goes, [E, rows] per actor class like the actions.  Nothing at all in the plain instances, whose code stays what it was.
+template <bool LOGP>
+struct SamplerLogp {
+  float *a, *p;
+};
+template <>
+struct SamplerLogp<false> {};
+template <bool LOGP>
+__device__ __forceinline__ float* sampler_logp_of(const SamplerLogp<LOGP>& lp, bool planner) {
+  if constexpr (LOGP) return planner ? lp.p : lp.a;
+  else return nullptr;
+}
 struct SamplerItem {
   const float *lg, *mk;  // the first row's logits and mask entries
   int32_t* dst;          // its action
@@ -4189,7 +4202,9 @@ __device__ __forceinline__ void sampler_item_load(const SamplerItem& d, int lane
   x = d.lg[inb ? __mul24(sub, d.lrs) + kk : 0];
   mv = d.mk[inb ? __mul24(sub, d.mrs) + __mul24(kk, d.mks) : 0];
 }
-__device__ __forceinline__ void sampler_item_run(const SamplerItem& d, int lane, const float x0, const float mv0, uint32_t base) {
+template <bool LOGP>
+__device__ __forceinline__ void sampler_item_run(const SamplerItem& d, int lane, const float x0, const float mv0, uint32_t base,
+                                                 float* __restrict__ lp) {  // lp: where the item's first row's logp goes (LOGP)
   const int lsh = d.lsh, segw = 1 << lsh, rpw = 64 >> lsh, len = d.len;
   const int sub = lane >> lsh, kk = lane & (segw - 1);
   // a lone row's length may differ from row to row (multi-action agents) and exceed 64 (chunks); packed rows fit their segment
@@ -4215,6 +4230,7 @@ __device__ __forceinline__ void sampler_item_run(const SamplerItem& d, int lane,
   // ---- weights, prefix sums, the first entry whose sum passes u T ----
   int choice = -1, last_ok = -1, outv = 0;
   float T = 0.0f;
+  bool had_ok = false;  // (LOGP, packed rows: my row has an allowed entry)
   for (int pass = (nch > 1 ? 0 : 1); pass < 2; ++pass) {  // (rows of more than 64 entries: a first pass for T)
     float carry = 0.0f;
     for (int ch = 0; ch < nch; ++ch) {
@@ -4246,12 +4262,14 @@ __device__ __forceinline__ void sampler_item_run(const SamplerItem& d, int lane,
           const float tot = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, c), (s << lsh) + segw - 1));
           Ts = sub == s ? tot : Ts;
         }
+        if (LOGP) T = Ts;
         const uint64_t oks = __ballot(ok), hits = __ballot(ok && c > u * Ts);
         const uint64_t sm = (1ull << segw) - 1ull;
         for (int s = 0; s < rpw; ++s) {
           const uint64_t h = (hits >> (s << lsh)) & sm, o = (oks >> (s << lsh)) & sm;
           const int pick = h ? __ffsll((unsigned long long)h) - 1 : (o ? 63 - __clzll((long long)o) : 0);
           outv = sub == s ? pick : outv;
+          if (LOGP) had_ok = sub == s ? o != 0ull : had_ok;
         }
       }
     }
@@ -4259,12 +4277,21 @@ __device__ __forceinline__ void sampler_item_run(const SamplerItem& d, int lane,
   }
   if (rpw == 1) outv = choice < 0 ? (last_ok < 0 ? 0 : last_ok) : choice;
   if (sub < d.rows && kk == 0) d.dst[sub] = outv;
+  if constexpr (LOGP) {  // log pi of the pick: y - aie_sampler_logf(T); 0 where nothing is allowed (or T = 0)
+    if (rpw == 1) had_ok = last_ok >= 0;
+    if (sub < d.rows && kk == 0) {
+      float lpv = 0.0f;
+      if (had_ok && T > 0.0f) lpv = (d.lg[__mul24(sub, d.lrs) + outv] - M) - aie_sampler_logf(T);
+      lp[sub] = lpv;
+    }
+  }
 }
 #define AIE_SAMPLER_GROUP 4  // items whose loads a wave has in flight together
-extern "C" __global__ void __launch_bounds__(256)
+template <bool LOGP>
+__global__ void __launch_bounds__(256)
 aie_sample_policy_actions_kernel(const aie_sampler_args S, uint8_t* __restrict__ arena, const float* __restrict__ logits_a,
                                  const float* __restrict__ logits_p, uint64_t seed, int64_t env_offset,
-                                 int32_t* __restrict__ act_a, int32_t* __restrict__ act_p, int wpr_log2) {
+                                 int32_t* __restrict__ act_a, int32_t* __restrict__ act_p, int wpr_log2, const SamplerLogp<LOGP> LP) {
   const int lane = (int)threadIdx.x & 63, wave = aie::uni((int)threadIdx.x >> 6);
 #ifdef AIE_DEV  // development: bits 8.. of the argument switch parts of the kernel off (what is the launch made of?)
   const int dev_skip = wpr_log2 >> 8;
@@ -4308,7 +4335,12 @@ aie_sample_policy_actions_kernel(const aie_sampler_args S, uint8_t* __restrict__
           if (dev_skip & 4) {
             if (x0[g] + mv0[g] == 12345.0f) d[g].dst[0] = 1;
           } else {
-            sampler_item_run(d[g], lane, x0[g], mv0[g], base);
+            float* lp = nullptr;
+            if constexpr (LOGP) {  // the logp of the item's first row: beside its action
+              const bool ag = it0 + g * wpr < A.items;
+              lp = sampler_logp_of<LOGP>(LP, !ag) + (d[g].dst - (ag ? act_a : act_p));
+            }
+            sampler_item_run<LOGP>(d[g], lane, x0[g], mv0[g], base, lp);
           }
         }
     }
@@ -4319,6 +4351,10 @@ aie_sample_policy_actions_kernel(const aie_sampler_args S, uint8_t* __restrict__
     *tfield = *tfield + 1;
   }
 }
+template __global__ void aie_sample_policy_actions_kernel<false>(const aie_sampler_args, uint8_t*, const float*, const float*, uint64_t,
+                                                                 int64_t, int32_t*, int32_t*, int, const SamplerLogp<false>);
+template __global__ void aie_sample_policy_actions_kernel<true>(const aie_sampler_args, uint8_t*, const float*, const float*, uint64_t,
+                                                                int64_t, int32_t*, int32_t*, int, const SamplerLogp<true>);
 // ---- the sampler's fast instances: every row of both groups is one aligned lane segment --------------------------------
 // (no rows of more than 64 entries, no multi-action agents: every BASELINE configuration and COVID.)  A SIMD issues one
 // scalar and one vector instruction every fourth clock whichever of its waves they come from, so the launch costs what the
@@ -4376,8 +4412,9 @@ __device__ __forceinline__ void sampler_fast_load(const SamplerFast<LSH>& G, int
   x = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(G.lg) + (lg0 + (in ? G.lgo : 0u)));
   mv = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(G.mk) + (mk0 + (in ? G.mko : 0u)));
 }
-template <int LSH>
-__device__ __forceinline__ void sampler_fast_run(const SamplerFast<LSH>& G, int it, int lane, const float x, const float mv, uint32_t base) {
+template <int LSH, bool LOGP>
+__device__ __forceinline__ void sampler_fast_run(const SamplerFast<LSH>& G, int it, int lane, const float x, const float mv, uint32_t base,
+                                                 float* __restrict__ lp) {  // lp: the replica's log-probabilities of this group (LOGP)
   constexpr int SEG = 1 << LSH, RPW = 64 >> LSH;
   const int r0 = it << (6 - LSH);
   const int rows = G.rows - r0 < RPW ? G.rows - r0 : RPW;
@@ -4386,32 +4423,46 @@ __device__ __forceinline__ void sampler_fast_run(const SamplerFast<LSH>& G, int 
   const float w = ok ? aie_sampler_expf(x - M) : 0.0f;
   const float c = sampler_scan(w, SEG);
   const uint32_t slot = (uint32_t)(G.slot0 + r0);
-  float thr;
+  float thr, Tl = 0.0f;  // (Tl: the row's total in every lane of it -- the LOGP instances' only)
   if (LSH == 6) {  // one row: its uniform and its total are scalars
     const float T = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, c), 63));
     thr = aie_sampler_uniform(aie_sampler_entry_rng(base, slot)) * T;
+    if (LOGP) Tl = T;
   } else {         // the segment's last lane to all of it: a swizzle through the LDS crossbar, no memory
     const float T = __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, c), LSH == 5 ? 0x3E0 : 0x1F0));
     thr = aie_sampler_uniform(aie_sampler_entry_rng(base, slot + (uint32_t)G.sub)) * T;
+    if (LOGP) Tl = T;
   }
   const bool hit = ok && c > thr;
   const uint64_t hits = __ballot(hit);
   const bool first = hit && (((uint32_t)hits & G.below_lo) | ((uint32_t)(hits >> 32) & G.below_hi)) == 0u;
   if (first) *reinterpret_cast<int32_t*>(reinterpret_cast<char*>(G.dst) + 4u * (uint32_t)(r0 + G.sub)) = G.kk;
+  // log pi of the pick, by the lane that stores the pick: y - aie_sampler_logf(T) (aie_layout.h; a hit means T > 0)
+  float lpv = 0.0f;
+  if constexpr (LOGP) {
+    lpv = (x - M) - aie_sampler_logf(Tl > 0.0f ? Tl : 1.0f);
+    if (first) *reinterpret_cast<float*>(reinterpret_cast<char*>(lp) + 4u * (uint32_t)(r0 + G.sub)) = lpv;
+  }
   if (__popcll(__ballot(first)) != rows) {  // rows without a pick: nothing allowed (NO-OP), or no sum above u T (the last allowed entry)
     const uint64_t oks = __ballot(ok), sm = LSH == 6 ? ~0ull : (1ull << SEG) - 1ull;
     for (int s = 0; s < rows; ++s)
       if (((hits >> (s << LSH)) & sm) == 0ull) {
         const uint64_t o = (oks >> (s << LSH)) & sm;
         if (lane == 0) G.dst[r0 + s] = o ? 63 - __clzll((long long)o) : 0;
+        if constexpr (LOGP) {  // the last allowed entry's y - log T; 0 where nothing is allowed or the total is 0
+          const int src = (s << LSH) + (o ? 63 - __clzll((long long)o) : 0);
+          const float lv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, lpv), src));
+          const float tv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, Tl), src));
+          if (lane == 0) lp[r0 + s] = (o && tv > 0.0f) ? lv : 0.0f;
+        }
       }
   }
 }
-template <int LA, int LQ>
+template <int LA, int LQ, bool LOGP>
 __global__ void __launch_bounds__(256)
 aie_sample_policy_fast_kernel(const aie_sampler_args S, uint8_t* __restrict__ arena, const float* __restrict__ logits_a,
                               const float* __restrict__ logits_p, uint64_t seed, int64_t env_offset,
-                              int32_t* __restrict__ act_a, int32_t* __restrict__ act_p, int wpr_log2) {
+                              int32_t* __restrict__ act_a, int32_t* __restrict__ act_p, int wpr_log2, const SamplerLogp<LOGP> LP) {
   const int lane = (int)threadIdx.x & 63, wave = aie::uni((int)threadIdx.x >> 6);
   // every kernel argument is requested here, in one batch: fetched where first used (behind branches) they arrived in
   // four to five dependent trips to the scalar cache, cold at the start of a launch
@@ -4420,6 +4471,12 @@ aie_sample_policy_fast_kernel(const aie_sampler_args S, uint8_t* __restrict__ ar
                "s"(S.planner.lg_estride), "s"(S.planner.len), "s"(S.planner.lrs), "s"(S.planner.mrs), "s"(S.planner.mks),
                "s"(S.planner.rows), "s"(S.t_off), "s"(S.rec_bytes), "s"(S.E), "s"(arena), "s"(logits_a), "s"(logits_p), "s"(seed),
                "s"(env_offset), "s"(act_a), "s"(act_p), "s"(wpr_log2));
+  float *lp_a = nullptr, *lp_p = nullptr;
+  if constexpr (LOGP) {
+    asm volatile("" ::"s"(LP.a), "s"(LP.p));
+    lp_a = LP.a;
+    lp_p = LP.p;
+  }
 #ifdef AIE_DEV  // development: bits 8.. of the argument switch parts of the kernel off (what is the launch made of?)
   const int dev_skip = wpr_log2 >> 8;
   wpr_log2 &= 255;
@@ -4430,6 +4487,10 @@ aie_sample_policy_fast_kernel(const aie_sampler_args S, uint8_t* __restrict__ ar
   const int wpr = 1 << wpr_log2;
   const int e = (int)blockIdx.x * (4 >> wpr_log2) + (wave >> wpr_log2), w_in = wave & (wpr - 1);
   if (e < S.E) {
+    if constexpr (LOGP) {  // this replica's rows
+      lp_a += (uint64_t)(uint32_t)e * (uint32_t)S.agents.rows;
+      lp_p += (uint64_t)(uint32_t)e * (uint32_t)S.planner.rows;
+    }
     const SamplerFast<LA> A = sampler_fast_group<LA>(S.agents, arena, logits_a, act_a, e, 0, lane);
     const SamplerFast<LQ> Q = sampler_fast_group<LQ>(S.planner, arena, logits_p, act_p, e, S.agents.rows, lane);
     const int per_env = S.agents.rows + S.planner.rows;
@@ -4460,8 +4521,8 @@ aie_sample_policy_fast_kernel(const aie_sampler_args S, uint8_t* __restrict__ ar
       }
 #pragma unroll
       for (int g = 0; g < 2; ++g) {
-        if (it + g * wpr < A.items) sampler_fast_run<LA>(A, it + g * wpr, lane, xa[g], ma[g], base);
-        if (it + g * wpr < Q.items) sampler_fast_run<LQ>(Q, it + g * wpr, lane, xq[g], mq[g], base);
+        if (it + g * wpr < A.items) sampler_fast_run<LA, LOGP>(A, it + g * wpr, lane, xa[g], ma[g], base, lp_a);
+        if (it + g * wpr < Q.items) sampler_fast_run<LQ, LOGP>(Q, it + g * wpr, lane, xq[g], mq[g], base, lp_p);
       }
     }
   }
@@ -4472,11 +4533,183 @@ aie_sample_policy_fast_kernel(const aie_sampler_args S, uint8_t* __restrict__ ar
   }
 }
 #define AIE_SAMPLER_FAST(LA, LQ) \
-  template __global__ void aie_sample_policy_fast_kernel<LA, LQ>(const aie_sampler_args, uint8_t*, const float*, const float*, \
-                                                                 uint64_t, int64_t, int32_t*, int32_t*, int);
+  template __global__ void aie_sample_policy_fast_kernel<LA, LQ, false>(const aie_sampler_args, uint8_t*, const float*, const float*, \
+                                                                        uint64_t, int64_t, int32_t*, int32_t*, int, const SamplerLogp<false>); \
+  template __global__ void aie_sample_policy_fast_kernel<LA, LQ, true>(const aie_sampler_args, uint8_t*, const float*, const float*, \
+                                                                       uint64_t, int64_t, int32_t*, int32_t*, int, const SamplerLogp<true>);
 AIE_SAMPLER_FAST(4, 4) AIE_SAMPLER_FAST(4, 5) AIE_SAMPLER_FAST(4, 6)
 AIE_SAMPLER_FAST(5, 4) AIE_SAMPLER_FAST(5, 5) AIE_SAMPLER_FAST(5, 6)
 AIE_SAMPLER_FAST(6, 4) AIE_SAMPLER_FAST(6, 5) AIE_SAMPLER_FAST(6, 6)
+
+// ---- policy evaluation: log pi(a|s), entropy and their logit gradient under stored masks (include/aie.h:
+// aie_policy_evaluate, aie_policy_evaluate_backward) ---------------------------------------------------------------------
+// The learning-time half of the sampler: for B stored replica-steps (any B) the log-probability of the stored sub-action
+// and the entropy of every action slot, from new logits under the stored masks, in the sampler's own arithmetic
+// (aie_layout.h: M, y, w, T in the scan's order, aie_sampler_logf, S, H, the backward's operation order), so that what is
+// evaluated is the distribution that was drawn from -- bit for bit the CPU twin's values.  The layout is the fast
+// sampler's: a lane per entry, as many whole rows to a wave as fit in aligned segments of 16 / 32 / 64 lanes (the shape is
+// a wave-uniform switch to compile-time instances), the row maximum and both sums (T and S) by the DPP steps above, the
+// totals to the row's lanes by a swizzle or a readlane: no LDS, no barrier.  One wave = one work item (a batch element's
+// agents' items, then its planner's); all of the item's loads (entry, mask, stored action, the backward's two incoming
+// gradients) issue before any arithmetic.  The backward recomputes M, T and S (two scans) instead of reading stored
+// probabilities and every lane writes its own entry's gradient: the stores of a wave cover its rows back to back.
+// Rows of multi-action agents (ragged) and rows of more than 64 entries take the generic path: one row per wave in chunks
+// of 64 with the scan's carries, the same values.  The argument is the small struct the host fills (the sampler's lesson:
+// DESIGN section 3), requested in one batch.
+template <int LSH>
+__device__ __forceinline__ float policy_segment_total(float c) {  // the segment's last lane to all of it
+  if (LSH == 6) return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, c), 63));
+  return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, c), LSH == 5 ? 0x3E0 : 0x1F0));
+}
+template <int LSH, bool BWD>
+__device__ __forceinline__ void policy_eval_fast(const aie_policy_eval_group& G, uint32_t b, uint32_t gi, int lane) {
+  constexpr int SEG = 1 << LSH, RPW = 64 >> LSH;
+  const int sub = lane >> LSH, kk = lane & (SEG - 1);
+  const uint32_t r0 = gi << (6 - LSH);
+  const int rows = (int)((uint32_t)G.rows - r0) < RPW ? (int)((uint32_t)G.rows - r0) : RPW;
+  const bool in = sub < rows && kk < G.len;
+  // scalar bases (the item's first row), 32-bit lane offsets; a lane without an entry reads the item's first one
+  const float* lgb = G.lg + ((uint64_t)b * G.lg_bstride + (uint64_t)r0 * (uint32_t)G.lrs);
+  const float* mkb = G.mk + ((uint64_t)b * G.mk_bstride + (uint64_t)r0 * (uint32_t)G.mrs);
+  const uint64_t row0 = (uint64_t)b * (uint32_t)G.rows + r0;
+  const uint32_t lgo = in ? (uint32_t)(__mul24(sub, G.lrs) + kk) : 0u;
+  const uint32_t mko = in ? (uint32_t)(__mul24(sub, G.mrs) + __mul24(kk, G.mks)) : 0u;
+  const uint32_t ro = sub < rows ? (uint32_t)sub : 0u;
+  const float x = lgb[lgo];
+  const float mv = mkb[mko];
+  int a = 0;
+  if (G.act) a = G.act[row0 + ro];
+  float gl = 0.0f, gh = 0.0f;
+  if (BWD) {
+    if (G.g_logp) gl = G.g_logp[row0 + ro];
+    if (G.g_ent) gh = G.g_ent[row0 + ro];
+  }
+  // ---- the row's shared values ----
+  const bool ok = in && mv > 0.5f && x == x;
+  const float M = sampler_segment_max(ok ? x : -INFINITY, SEG);
+  const float y = x - M;
+  const float w = ok ? aie_sampler_expf(y) : 0.0f;
+  const bool live = ok && y > -80.0f;
+  const float v = live ? w * y : 0.0f;
+  const float T = policy_segment_total<LSH>(sampler_scan(w, SEG));
+  const float S = policy_segment_total<LSH>(sampler_scan(v, SEG));
+  const bool any = T > 0.0f;
+  const float Ts = any ? T : 1.0f;
+  const float L = aie_sampler_logf(Ts);
+  const float H = any ? L - __fdiv_rn(S, Ts) : 0.0f;
+  const bool a_in = a >= 0 && a < G.len;
+  if (!BWD) {
+    // one lane per row writes: the stored action's (lane 0 of the segment for an action outside the row)
+    if (G.logp && sub < rows && kk == (a_in ? a : 0))
+      G.logp[row0 + sub] = !any ? 0.0f : (a_in && ok) ? y - L : -INFINITY;
+    if (G.ent && sub < rows && kk == 0) G.ent[row0 + sub] = H;
+  } else {
+    // is the stored action allowed?  (its lane's `ok`, to the lanes of its segment)
+    const uint64_t hit = __ballot(ok && kk == a);
+    const bool a_ok = LSH == 6 ? hit != 0ull : ((hit >> (lane & ~(SEG - 1))) & ((1ull << (SEG & 63)) - 1ull)) != 0ull;
+    float g = 0.0f;
+    if (ok && any) g = aie_policy_entry_grad(y, w, Ts, L, H, kk == a, a_ok ? gl : 0.0f, gh);
+    if (in) (G.grad + ((uint64_t)b * G.lg_bstride + (uint64_t)r0 * (uint32_t)G.lrs))[lgo] = g;
+  }
+}
+// one row per wave, any length: chunks of 64 entries with the scan's carries (and multi-action agents' rows)
+template <bool BWD>
+__device__ __forceinline__ void policy_eval_generic(const aie_policy_eval_args& A, const aie_policy_eval_group& G, bool agents,
+                                                    uint32_t b, uint32_t row, int lane) {
+  int len = G.len;
+  uint32_t lo = row * (uint32_t)G.lrs, mlo = row * (uint32_t)G.mrs;
+  if (agents && A.ragged) {  // lrs / mrs: from agent to agent
+    const int i = (int)row / A.act_a_width, s = (int)row - i * A.act_a_width;
+    int off = 0;
+    for (int k = 0; k < s; ++k) off += 1 + A.params->sub_a_dim[k];
+    len = A.params->n_sub_a ? 1 + A.params->sub_a_dim[s] : 1;
+    lo = (uint32_t)(i * G.lrs + off);
+    mlo = (uint32_t)(i * G.mrs + off * G.mks);
+  }
+  const float* lg = G.lg + ((uint64_t)b * G.lg_bstride + lo);
+  const float* mk = G.mk + ((uint64_t)b * G.mk_bstride + mlo);
+  const uint64_t ri = (uint64_t)b * (uint32_t)G.rows + row;
+  const int nch = (len + 63) >> 6, seg = nch > 1 ? 64 : aie_sampler_segment(len);
+  const int a = G.act ? G.act[ri] : 0;
+  const bool a_in = a >= 0 && a < len;
+  const float xa = lg[a_in ? a : 0], ma = mk[(a_in ? a : 0) * G.mks];
+  const bool a_ok = a_in && ma > 0.5f && xa == xa;
+  float m = -INFINITY;
+  for (int ch = 0; ch < nch; ++ch) {
+    const int k = 64 * ch + lane;
+    if (k < len) {
+      const float x = lg[k];
+      if (mk[k * G.mks] > 0.5f && x > m) m = x;  // (x > m: not a NaN)
+    }
+  }
+  const float M = sampler_segment_max(m, 64);
+  float T = 0.0f, S = 0.0f;
+  for (int ch = 0; ch < nch; ++ch) {
+    const int k = 64 * ch + lane;
+    float w = 0.0f, v = 0.0f;
+    if (k < len) {
+      const float x = lg[k];
+      if (mk[k * G.mks] > 0.5f && x == x) {
+        const float y = x - M;
+        w = aie_sampler_expf(y);
+        v = y > -80.0f ? w * y : 0.0f;
+      }
+    }
+    const float c = T + sampler_scan(w, seg), cs = S + sampler_scan(v, seg);
+    T = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, c), seg - 1));
+    S = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cs), seg - 1));
+  }
+  const bool any = T > 0.0f;
+  const float Ts = any ? T : 1.0f;
+  const float L = aie_sampler_logf(Ts);
+  const float H = any ? L - __fdiv_rn(S, Ts) : 0.0f;
+  if (!BWD) {
+    if (lane == 0) {
+      if (G.logp) G.logp[ri] = !any ? 0.0f : a_ok ? (xa - M) - L : -INFINITY;
+      if (G.ent) G.ent[ri] = H;
+    }
+  } else {
+    const float gl = (G.g_logp && a_ok) ? G.g_logp[ri] : 0.0f, gh = G.g_ent ? G.g_ent[ri] : 0.0f;
+    float* gr = G.grad + ((uint64_t)b * G.lg_bstride + lo);
+    for (int ch = 0; ch < nch; ++ch) {
+      const int k = 64 * ch + lane;
+      if (k < len) {
+        const float x = lg[k];
+        float g = 0.0f;
+        if (any && mk[k * G.mks] > 0.5f && x == x) {
+          const float y = x - M;
+          g = aie_policy_entry_grad(y, aie_sampler_expf(y), Ts, L, H, k == a, gl, gh);
+        }
+        gr[k] = g;
+      }
+    }
+  }
+}
+template <bool BWD>
+__device__ __forceinline__ void policy_eval_body(const aie_policy_eval_args& A) {
+  const int lane = (int)threadIdx.x & 63;
+  const uint32_t wv = (uint32_t)aie::uni((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+  // every kernel argument is requested here, in one batch (the fast sampler's finding)
+  asm volatile("" ::"s"(A.agents.lg), "s"(A.agents.mk), "s"(A.agents.act), "s"(A.agents.logp), "s"(A.agents.ent), "s"(A.agents.grad),
+               "s"(A.agents.g_logp), "s"(A.agents.g_ent), "s"(A.agents.lg_bstride), "s"(A.agents.mk_bstride), "s"(A.agents.len),
+               "s"(A.agents.lrs), "s"(A.agents.mrs), "s"(A.agents.mks), "s"(A.agents.lsh), "s"(A.agents.rows), "s"(A.agents.items),
+               "s"(A.agents.generic));
+  asm volatile("" ::"s"(A.planner.lg), "s"(A.planner.mk), "s"(A.planner.act), "s"(A.planner.logp), "s"(A.planner.ent),
+               "s"(A.planner.grad), "s"(A.planner.g_logp), "s"(A.planner.g_ent), "s"(A.planner.lg_bstride), "s"(A.planner.mk_bstride),
+               "s"(A.planner.len), "s"(A.planner.lrs), "s"(A.planner.mrs), "s"(A.planner.mks), "s"(A.planner.lsh), "s"(A.planner.rows),
+               "s"(A.planner.items), "s"(A.planner.generic), "s"(A.B), "s"(A.items));
+  const uint32_t b = wv / A.items, it = wv - b * A.items;
+  if (b >= A.B) return;  // (whole waves: no barrier below)
+  const bool ag = it < (uint32_t)A.agents.items;
+  const aie_policy_eval_group G = ag ? A.agents : A.planner;  // (by value: its fields are scalar selects)
+  const uint32_t gi = ag ? it : it - (uint32_t)A.agents.items;
+  if (G.generic) policy_eval_generic<BWD>(A, G, ag, b, gi, lane);
+  else if (G.lsh == 4) policy_eval_fast<4, BWD>(G, b, gi, lane);
+  else if (G.lsh == 5) policy_eval_fast<5, BWD>(G, b, gi, lane);
+  else policy_eval_fast<6, BWD>(G, b, gi, lane);
+}
+extern "C" __global__ void __launch_bounds__(256) aie_policy_eval_kernel(const aie_policy_eval_args A) { policy_eval_body<false>(A); }
+extern "C" __global__ void __launch_bounds__(256) aie_policy_eval_bwd_kernel(const aie_policy_eval_args A) { policy_eval_body<true>(A); }
 #endif  // !AIE_JIT
 
 #if defined(AIE_JIT) && !defined(AIE_JIT_OSE)

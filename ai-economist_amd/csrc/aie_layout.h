@@ -1468,7 +1468,26 @@ AIE_HD static inline double aie_annealed_tax_limit(int completions, double warmu
  * Per entry: one exponential of 14 vector instructions, a row maximum and a prefix sum of 6 - 10 data-parallel-primitive
  * instructions each (DPP row rotates / shifts / broadcasts and gfx950's permlane swaps: no LDS), one comparison -- where
  * round 5's Gumbel-max spent two float64 logarithms (each with an IEEE division) and a 64-bit key per entry.  float32
- * resolves a probability to 2^-24 of the row's total; u itself has 23 bits. */
+ * resolves a probability to 2^-24 of the row's total; u itself has 23 bits.
+ *
+ * The same row, evaluated (aie_sample_policy_actions_logp, aie_policy_evaluate and its backward; the row helpers below are
+ * the CPU twin): with the allowed set, M, w_k and T of above, y_k = x_k - M and "live" = allowed with y_k > -80 (w_k > 0),
+ *     L = aie_sampler_logf(T);   logp_k = y_k - L;   p_k = w_k / T (IEEE division, rounded to nearest);
+ *     S = sum of v_k, v_k = w_k * y_k (the product rounded) for live k and 0 otherwise, in the scan's order (the same
+ *         steps and carries as T: the total is the scan's last value);   H = L - S / T.
+ *   * aie_sampler_logf(T), T >= 2^-116 (the smallest non-zero total; a total that counts an allowed maximum is >= 1):
+ *     T = m 2^e exactly with m in (sqrt(1/2), sqrt(2)] (mantissa field > 0x3504f3: m = mantissa / 2, e + 1);
+ *     f = m - 1 (exact); h = the polynomial of degree 9 below by Horner in fma, highest coefficient first
+ *     (log(1 + f) = f + f^2 h(f) to 1.5e-9 on the interval); t = f * f; lp = fma(t, h, f);
+ *     L = fma(e, ln2_hi, fma(e, ln2_lo, lp)) with aie_sampler_expf's two-part ln 2 (e ln2_hi is exact).  T = 1 gives 0.
+ *   * backward, the gradient of (g_logp logp_a + g_H H) with respect to x_k, a = the stored action:
+ *     allowed k:  t1 = [k = a] - p_k;  a1 = g_logp * t1;  lh = logp_k + H;  t2 = p_k * lh for live k, 0 otherwise;
+ *                 t3 = g_H * t2;  g_k = a1 - t3   (every operation rounded, nothing fused);
+ *     k not allowed: exactly 0.
+ *   * edges: a row where nothing is allowed, or whose total is 0 (every allowed logit -inf), has logp 0 whatever the
+ *     stored action, H 0 and a zero gradient row (the sampler's choice there is NO-OP or the last allowed entry); a stored
+ *     action the mask does not allow (or outside 0 .. len - 1) has logp -INFINITY and its g_logp counts as 0; an allowed
+ *     entry with y <= -80 has w = 0 and the finite logp y - L (-INFINITY for a logit of -inf). */
 AIE_HD static inline uint32_t aie_sampler_entry_rng(uint32_t base, uint32_t k) {  /* "lowbias32", C. Wellons' hash prospector */
   uint32_t h = base + k * 0x9E3779B1u;
   h ^= h >> 16;
@@ -1499,6 +1518,151 @@ AIE_HD static inline float aie_sampler_expf(float y) {
 /* the aligned lane segment a row of `len` entries is scanned in, and how many such rows share a wavefront */
 AIE_HD static inline int aie_sampler_segment(int len) { return len <= 16 ? 16 : len <= 32 ? 32 : 64; }
 AIE_HD static inline int aie_sampler_rows_per_wave(int len) { return 64 / aie_sampler_segment(len); }
+/* products are rounded before they are added, wherever this header is included from (gcc: -ffp-contract=off) */
+#if defined(__clang__)
+#define AIE_NOCONTRACT _Pragma("clang fp contract(off)")
+#else
+#define AIE_NOCONTRACT
+#endif
+#if defined(__HIP_DEVICE_COMPILE__)
+#define AIE_FDIV_RN(a, b) __fdiv_rn((a), (b)) /* the correctly rounded sequence whatever the compiler's flags */
+#else
+#define AIE_FDIV_RN(a, b) ((a) / (b))
+#endif
+AIE_HD static inline float aie_sampler_logf(float T) {
+  AIE_NOCONTRACT
+  uint32_t b;
+  memcpy(&b, &T, 4);
+  const uint32_t mant = b & 0x7fffffu;
+  const int big = mant > 0x3504f3u;               /* m > sqrt(2): halve it */
+  const int e = (int)(b >> 23) - 127 + big;
+  const uint32_t mb = (big ? 0x3f000000u : 0x3f800000u) | mant;
+  float m;
+  memcpy(&m, &mb, 4);
+  const float f = m - 1.0f;                       /* exact */
+  float h = 0x1.07826ep-4f;
+  h = fmaf(h, f, -0x1.dbcd16p-4f);
+  h = fmaf(h, f, 0x1.ec6694p-4f);
+  h = fmaf(h, f, -0x1.fd3baep-4f);
+  h = fmaf(h, f, 0x1.22db42p-3f);
+  h = fmaf(h, f, -0x1.554b4ap-3f);
+  h = fmaf(h, f, 0x1.99a98p-3f);
+  h = fmaf(h, f, -0x1.000064p-2f);
+  h = fmaf(h, f, 0x1.55553cp-2f);
+  h = fmaf(h, f, -0x1.fffffep-2f);
+  const float t = f * f;
+  const float lp = fmaf(t, h, f);
+  const float fe = (float)e;
+  return fmaf(fe, 0x1.62e4p-1f, fmaf(fe, 0x1.7f7d1cp-20f, lp));
+}
+/* One 64-entry chunk's inclusive prefix sums in the sampler's fixed order, in place (the CPU twin of the kernels' scan). */
+AIE_HD static inline void aie_sampler_scan64(float* v, int seg) {
+  float u[64];
+  for (int d = 1; d <= 8; d <<= 1) {
+    for (int r = 0; r < 64; ++r) u[r] = v[r] + ((r & 15) >= d ? v[r - d] : 0.0f);  /* (+ 0: what the kernel's row shift adds) */
+    for (int r = 0; r < 64; ++r) v[r] = u[r];
+  }
+  if (seg >= 32) {
+    for (int r = 0; r < 64; ++r) u[r] = ((r >> 4) & 1) ? v[r] + v[(r & ~15) - 1] : v[r];
+    for (int r = 0; r < 64; ++r) v[r] = u[r];
+  }
+  if (seg >= 64)
+    for (int r = 63; r >= 32; --r) v[r] = v[r] + v[31];
+}
+/* What a row's evaluation shares between its entries (the comment block above).  any = 0: nothing allowed or T = 0. */
+typedef struct aie_policy_row {
+  float M, T, S, L, H;
+  int32_t any;
+} aie_policy_row;
+AIE_HD static inline int aie_policy_allowed(const float* x, const float* mask, int mks, int len, int k) {
+  return k >= 0 && k < len && mask[(int64_t)k * mks] > 0.5f && x[k] == x[k];
+}
+AIE_HD static inline aie_policy_row aie_policy_row_stats(const float* x, const float* mask, int mks, int len) {
+  AIE_NOCONTRACT
+  aie_policy_row R;
+  R.M = -INFINITY;
+  R.T = R.S = R.L = R.H = 0.0f;
+  R.any = 0;
+  int n_ok = 0;
+  for (int k = 0; k < len; ++k)
+    if (aie_policy_allowed(x, mask, mks, len, k)) {
+      if (!n_ok || x[k] > R.M) R.M = x[k];
+      ++n_ok;
+    }
+  if (!n_ok) return R;
+  const int nch = (len + 63) >> 6, seg = nch > 1 ? 64 : aie_sampler_segment(len);
+  float cT = 0.0f, cS = 0.0f;
+  for (int ch = 0; ch < nch; ++ch) {
+    float w[64], v[64];
+    for (int r = 0; r < 64; ++r) {
+      const int k = 64 * ch + r;
+      w[r] = v[r] = 0.0f;
+      if (aie_policy_allowed(x, mask, mks, len, k)) {
+        const float y = x[k] - R.M;
+        w[r] = aie_sampler_expf(y);
+        if (y > -80.0f) v[r] = w[r] * y;
+      }
+    }
+    aie_sampler_scan64(w, seg);
+    aie_sampler_scan64(v, seg);
+    cT = cT + w[seg - 1];
+    cS = cS + v[seg - 1];
+  }
+  R.T = cT;
+  R.S = cS;
+  if (!(R.T > 0.0f)) return R;
+  R.any = 1;
+  R.L = aie_sampler_logf(R.T);
+  R.H = R.L - AIE_FDIV_RN(R.S, R.T);
+  return R;
+}
+AIE_HD static inline float aie_policy_row_logp(const aie_policy_row* R, const float* x, const float* mask, int mks, int len, int a) {
+  if (!R->any) return 0.0f;
+  if (!aie_policy_allowed(x, mask, mks, len, a)) return -INFINITY;
+  return (x[a] - R->M) - R->L;
+}
+/* one entry's gradient: w, y of an ALLOWED entry k of a row with any = 1; ind = [k = a]; g_logp already 0 for a stored
+ * action that is not allowed */
+AIE_HD static inline float aie_policy_entry_grad(float y, float w, float T, float L, float H, int ind, float g_logp, float g_H) {
+  AIE_NOCONTRACT
+  const float p = AIE_FDIV_RN(w, T);
+  const float t1 = (ind ? 1.0f : 0.0f) - p;
+  const float a1 = g_logp * t1;
+  const float lh = (y - L) + H;
+  const float t2 = y > -80.0f ? p * lh : 0.0f;
+  const float t3 = g_H * t2;
+  return a1 - t3;
+}
+/* What the evaluation kernels need, as their kernel argument (aie_policy_evaluate fills it): per actor class the caller's
+ * pointers and the rows' shape.  Entry k of row r of batch element b: logit (and gradient) at b lg_bstride + r lrs + k, mask
+ * at mk[b mk_bstride + r mrs + k mks] (mk: the caller's masks in the logits' layout, or the arena's own), action, logp,
+ * entropy and their gradients at b rows + r.  items = wavefronts per batch element: as many whole rows as fit 64 lanes in
+ * aligned segments of 1 << lsh lanes, or (generic: multi-action agents, rows of more than 64 entries) one row each. */
+typedef struct aie_policy_eval_group {
+  const float *lg, *mk;
+  const int32_t* act;
+  const float *g_logp, *g_ent;
+  float *logp, *ent, *grad;
+  uint32_t lg_bstride, mk_bstride;
+  int32_t len, lrs, mrs, mks, lsh, rows, items, generic;
+} aie_policy_eval_group;
+typedef struct aie_policy_eval_args {
+  aie_policy_eval_group agents, planner;
+  const aie_params* params; /* the device copy: read for multi-action agents only */
+  uint32_t B, items;        /* batch elements; wavefronts per batch element (both classes) */
+  int32_t act_a_width, ragged; /* ragged: multi-action agents (rows of different lengths) */
+} aie_policy_eval_args;
+AIE_HD static inline void aie_policy_row_backward(const aie_policy_row* R, const float* x, const float* mask, int mks, int len,
+                                                  int a, float g_logp, float g_H, float* g) {
+  const float gl = aie_policy_allowed(x, mask, mks, len, a) ? g_logp : 0.0f;
+  for (int k = 0; k < len; ++k) {
+    g[k] = 0.0f;
+    if (R->any && aie_policy_allowed(x, mask, mks, len, k)) {
+      const float y = x[k] - R->M;
+      g[k] = aie_policy_entry_grad(y, aie_sampler_expf(y), R->T, R->L, R->H, k == a, gl, g_H);
+    }
+  }
+}
 /* What the sampler kernel needs of the parameter block, as its kernel argument (aie_sampler_args_of fills it).  A group
  * is a replica's agent rows or its planner rows: row r's entry k has its logit at logits[e lg_estride + r lrs + k] and its
  * mask at the arena's float mk_off / 4 + e mk_estride + r mrs + k mks (COVID's collated agent masks: mrs 1, mks n). */

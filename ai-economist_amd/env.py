@@ -293,24 +293,140 @@ class DeviceBackend:
             C.c_void_p(a.data_ptr()), C.c_void_p(p.data_ptr()), self._stream()))
         return a, p
 
-    def sample_policy_actions(self, logits_a, logits_p, seed, env_offset=0, slot=0, out=None):
+    def sample_policy_actions(self, logits_a, logits_p, seed, env_offset=0, slot=0, out=None, logp=False):
         """Categorical sampling from the caller's policy logits under the current action masks (aie_sample_policy_actions:
-        Gumbel-max in one launch, replayable from a captured graph).  logits_a: float32 [E, n, MA] in the layout of the
-        agents' flattened action mask (COVID: [E, n, 1 + levels]), logits_p: float32 [E, MP]; either may be None.
-        Returns the action buffers (int32 [E, n, width], [E, width_p]) -- `out=(a, p)` to fill the caller's own."""
+        inverse-CDF sampling in float32 -- weights exp(logit - max) of the allowed entries, prefix sums in a fixed order,
+        one counter-hash uniform per slot -- in one launch, replayable from a captured graph).  logits_a: float32
+        [E, n, MA] in the layout of the agents' flattened action mask (COVID: [E, n, 1 + levels]), logits_p: float32
+        [E, MP]; either may be None.
+        Returns the action buffers (int32 [E, n, width], [E, width_p]) -- `out=(a, p)` to fill the caller's own.
+        logp=True (aie_sample_policy_actions_logp: the same picks, the same launch count): returns (a, p, logp_a, logp_p),
+        float32 tensors of the actions' shapes with log pi(a|s) of every pick under the masks it was drawn under --
+        `out=(a, p, logp_a, logp_p)` to fill the caller's own.  The buffers of an actor class whose logits are None are
+        left alone."""
         torch = _torch()
-        a, p = out if out is not None else self._action_buffers(slot)
+        if out is not None:
+            a, p = out[0], out[1]
+        else:
+            a, p = self._action_buffers(slot)
         la = lp = None
         if logits_a is not None:
             per_agent = self.tensors["obs_a_action_mask"].numel() // (self.E * self.n)
             la = self._ptr(logits_a, torch.float32, "logits_a", self.E * self.n * per_agent)
         if logits_p is not None:
             lp = self._ptr(logits_p, torch.float32, "logits_p", self.tensors["obs_p_action_mask"].numel())
-        self._check(self.lib.aie_sample_policy_actions(
-            self.handle, la, lp, C.c_uint64(seed), C.c_int64(env_offset),
-            C.c_void_p(a.data_ptr()) if logits_a is not None else None,
-            C.c_void_p(p.data_ptr()) if logits_p is not None else None, self._stream()))
-        return a, p
+        pa = C.c_void_p(a.data_ptr()) if logits_a is not None else None
+        pp = C.c_void_p(p.data_ptr()) if logits_p is not None else None
+        if not logp:
+            self._check(self.lib.aie_sample_policy_actions(
+                self.handle, la, lp, C.c_uint64(seed), C.c_int64(env_offset), pa, pp, self._stream()))
+            return a, p
+        if out is not None and len(out) == 4:
+            ga, gp = out[2], out[3]
+        else:
+            ga, gp = self._logp_buffers(slot)
+        for t, like, what in ((ga, a, "logp_a"), (gp, p, "logp_p")):
+            if t.dtype != torch.float32 or t.numel() != like.numel() or not t.is_contiguous() or t.device != self.device:
+                raise ValueError("%s: a contiguous float32 device tensor of the action buffer's %d elements" % (what, like.numel()))
+        self._check(self.lib.aie_sample_policy_actions_logp(
+            self.handle, la, lp, C.c_uint64(seed), C.c_int64(env_offset), pa, pp,
+            C.c_void_p(ga.data_ptr()) if logits_a is not None else None,
+            C.c_void_p(gp.data_ptr()) if logits_p is not None else None, self._stream()))
+        return a, p, ga, gp
+
+    def _logp_buffers(self, slot):
+        torch = _torch()
+        if getattr(self, "_logp_bufs", None) is None:
+            a, p = self._action_buffers(0)
+            self._logp_bufs = [(torch.zeros(a.shape, dtype=torch.float32, device=self.device),
+                                torch.zeros(p.shape, dtype=torch.float32, device=self.device)) for _ in range(2)]
+        return self._logp_bufs[slot]
+
+    def action_masks(self, out=None):
+        """A snapshot (masks_a, masks_p) of the current action masks in the LOGITS' layout -- float32 [E, n, MA]
+        (COVID: [E, n, 1 + levels], a transposing copy of the arena's collated rows) and [E, MP] -- to store in a
+        trajectory beside the actions and evaluate later (policy_evaluate / rollout.masked_logp_entropy).  Plain device
+        copies on the current stream (capturable); `out=(masks_a, masks_p)` to fill the caller's own."""
+        torch = _torch()
+        ma, mp = self.tensors["obs_a_action_mask"], self.tensors["obs_p_action_mask"]
+        if int(self.cfg.scenario) == _cabi.SCN_COVID:
+            ma = ma.transpose(1, 2)  # [E, 1 + levels, n] -> [E, n, 1 + levels]
+        if out is None:
+            out = (torch.empty(ma.shape, dtype=torch.float32, device=self.device),
+                   torch.empty(mp.shape, dtype=torch.float32, device=self.device))
+        out[0].view(ma.shape).copy_(ma)
+        out[1].view(mp.shape).copy_(mp)
+        return out[0], out[1]
+
+    def _policy_eval_operands(self, logits_a, logits_p, masks_a, masks_p, actions_a, actions_p):
+        """Contiguous device operands of aie_policy_evaluate / _backward and the batch size B they agree on."""
+        torch = _torch()
+        per_a = self.tensors["obs_a_action_mask"].numel() // self.E
+        per_p = self.tensors["obs_p_action_mask"].numel() // self.E
+        aa, ap = self._action_buffers(0)
+        act_a, act_p = aa.numel() // self.E, ap.numel() // self.E
+
+        def dev(t, dtype):
+            if t is None:
+                return None
+            if not isinstance(t, torch.Tensor):
+                t = torch.as_tensor(np.asarray(t))
+            return t.to(device=self.device, dtype=dtype).contiguous()
+
+        ops = dict(la=dev(logits_a, torch.float32), lp=dev(logits_p, torch.float32), ma=dev(masks_a, torch.float32),
+                   mp=dev(masks_p, torch.float32), aa=dev(actions_a, torch.int32), ap=dev(actions_p, torch.int32))
+        per = dict(la=per_a, lp=per_p, ma=per_a, mp=per_p, aa=act_a, ap=act_p)
+        Bs = set()
+        for k, t in ops.items():
+            if t is not None:
+                if t.numel() == 0 or t.numel() % per[k]:
+                    raise ValueError("policy evaluation: operand %r has %d elements, not a multiple of the %d per batch element"
+                                     % (k, t.numel(), per[k]))
+                Bs.add(t.numel() // per[k])
+        if len(Bs) != 1:
+            raise ValueError("policy evaluation: the operands disagree on the batch size (%s)" % sorted(Bs))
+        return ops, Bs.pop(), (act_a, act_p, per_a, per_p)
+
+    def policy_evaluate(self, logits_a, logits_p, masks_a, masks_p, actions_a, actions_p, entropy=True):
+        """aie_policy_evaluate: (logp_a, logp_p, entropy_a, entropy_p) of stored actions under stored masks for the given
+        logits, B batch elements (any B: the operands' leading extent(s); with masks None -- the arena's current masks
+        -- B = E).  Layouts as sample_policy_actions / action_masks; either actor class may be None (its outputs are
+        None).  One launch on the current stream."""
+        torch = _torch()
+        ops, B, (act_a, act_p, _, _) = self._policy_eval_operands(logits_a, logits_p, masks_a, masks_p, actions_a, actions_p)
+        f = dict(dtype=torch.float32, device=self.device)
+        sa, sp = ((B,) + tuple(t.shape[1:]) for t in self._action_buffers(0))
+        out = [torch.empty(sa, **f) if ops["la"] is not None and ops["aa"] is not None else None,
+               torch.empty(sp, **f) if ops["lp"] is not None and ops["ap"] is not None else None,
+               torch.empty(sa, **f) if ops["la"] is not None and entropy else None,
+               torch.empty(sp, **f) if ops["lp"] is not None and entropy else None]
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        self._check(self.lib.aie_policy_evaluate(
+            self.handle, C.c_int64(B), ptr(ops["la"]), ptr(ops["lp"]), ptr(ops["ma"]), ptr(ops["mp"]), ptr(ops["aa"]), ptr(ops["ap"]),
+            ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), self._stream()))
+        return tuple(out)
+
+    def policy_evaluate_backward(self, logits_a, logits_p, masks_a, masks_p, actions_a, actions_p,
+                                 g_logp_a=None, g_logp_p=None, g_entropy_a=None, g_entropy_p=None):
+        """aie_policy_evaluate_backward: (grad_logits_a, grad_logits_p), the logits' shapes, of
+        sum(g_logp * logp + g_entropy * entropy); a None gradient counts as zeros.  One launch on the current stream."""
+        torch = _torch()
+        ops, B, (act_a, act_p, _, _) = self._policy_eval_operands(logits_a, logits_p, masks_a, masks_p, actions_a, actions_p)
+        gs = []
+        for g, per, what in ((g_logp_a, act_a, "g_logp_a"), (g_logp_p, act_p, "g_logp_p"), (g_entropy_a, act_a, "g_entropy_a"),
+                             (g_entropy_p, act_p, "g_entropy_p")):
+            if g is not None:
+                g = g.to(device=self.device, dtype=torch.float32).contiguous()
+                if g.numel() != B * per:
+                    raise ValueError("%s has %d elements, the batch needs %d" % (what, g.numel(), B * per))
+            gs.append(g)
+        grad_a = torch.empty_like(ops["la"]) if ops["la"] is not None else None
+        grad_p = torch.empty_like(ops["lp"]) if ops["lp"] is not None else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        self._check(self.lib.aie_policy_evaluate_backward(
+            self.handle, C.c_int64(B), ptr(ops["la"]), ptr(ops["lp"]), ptr(ops["ma"]), ptr(ops["mp"]), ptr(ops["aa"]), ptr(ops["ap"]),
+            ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gs[3]), ptr(grad_a), ptr(grad_p), self._stream()))
+        return grad_a, grad_p
 
     def _action_buffers(self, slot):
         torch = _torch()

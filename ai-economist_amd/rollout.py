@@ -79,17 +79,77 @@ class GraphedStep:
             self.graph.replay()
 
 
+def _masked_categorical():
+    """The autograd Function, built at first use (torch is imported lazily everywhere in this package)."""
+    global _MaskedCategorical
+    if _MaskedCategorical is not None:
+        return _MaskedCategorical
+    import torch
+
+    class MaskedCategorical(torch.autograd.Function):
+        """log pi(a|s) and entropy of stored actions under stored masks, differentiable in the logits: forward =
+        aie_policy_evaluate, backward = aie_policy_evaluate_backward (one launch each; the sampler's own float32
+        arithmetic, so the logp of an action evaluated under the logits and masks it was sampled from IS the logp
+        aie_sample_policy_actions_logp returned).  apply(be, logits_a, logits_p, masks_a, masks_p, actions_a, actions_p)
+        -> (logp_a, logp_p, entropy_a, entropy_p); gradients flow to the logits only.  Either actor class may be None."""
+
+        @staticmethod
+        def forward(ctx, be, logits_a, logits_p, masks_a, masks_p, actions_a, actions_p):
+            ctx.be = be
+            ctx.has = (logits_a is not None, logits_p is not None)
+            ctx.shapes = (None if logits_a is None else logits_a.shape, None if logits_p is None else logits_p.shape)
+            la = None if logits_a is None else logits_a.detach()
+            lp = None if logits_p is None else logits_p.detach()
+            ctx.operands = (la, lp, masks_a, masks_p, actions_a, actions_p)
+            out = be.policy_evaluate(la, lp, masks_a, masks_p, actions_a, actions_p)
+            return tuple(out)
+
+        @staticmethod
+        def backward(ctx, g_logp_a, g_logp_p, g_ent_a, g_ent_p):
+            ga, gp = ctx.be.policy_evaluate_backward(*ctx.operands, g_logp_a=g_logp_a, g_logp_p=g_logp_p,
+                                                     g_entropy_a=g_ent_a, g_entropy_p=g_ent_p)
+            if ga is not None:
+                ga = ga.view(ctx.shapes[0])
+            if gp is not None:
+                gp = gp.view(ctx.shapes[1])
+            return None, ga, gp, None, None, None, None
+
+    _MaskedCategorical = MaskedCategorical
+    return MaskedCategorical
+
+
+_MaskedCategorical = None
+
+
+def __getattr__(name):  # rollout.MaskedCategorical: the class itself, made when first asked for
+    if name == "MaskedCategorical":
+        return _masked_categorical()
+    raise AttributeError(name)
+
+
+def masked_logp_entropy(be, logits_a, logits_p, masks_a, masks_p, actions_a, actions_p):
+    """(logp_a, logp_p, entropy_a, entropy_p) of the stored actions under the stored masks for the given logits (layouts:
+    Backend.sample_policy_actions / Backend.action_masks, any batch size B in place of E; masks None = the environment's
+    current masks, B = E), differentiable in the logits: what a PPO / A2C loss is built from.  Two launches per
+    training step in all (forward, backward) where the torch formulation (masked_fill, log_softmax, gather, the entropy
+    sum and their autograd twins) takes 10 - 15 per actor class -- and the distribution is the sampler's, to the bit."""
+    return _masked_categorical().apply(be, logits_a, logits_p, masks_a, masks_p, actions_a, actions_p)
+
+
 class MaskedMLPPolicy:
     """A small policy network of the shape the reference's trainers use on the flat observations (fully connected
     trunk, one categorical head per action subspace, `action_mask` applied to the logits: base_env.py:141-145,
     tutorials/rllib/env_wrapper.py:50-211) with random-init weights: enough to put a real policy's launches between the
     environment steps.  The network is torch (three GEMMs with fused bias per actor class, two ReLUs); masking and
     sampling -- what every trainer does with its logits -- is ONE launch of the library (aie_sample_policy_actions:
-    Gumbel-max under the action masks, float64 scores, the draw index a record field, so the loop can be captured).
+    inverse-CDF sampling under the action masks in float32, fixed operation order, the draw index a record field, so the
+    loop can be captured).  record_logp=True: the same launch also fills `logp_a` / `logp_p` (float32, the action
+    buffers' shapes) with log pi(a|s) of every pick, in place -- a trainer copies them into its trajectory with the
+    actions and Backend.action_masks().
     `sampler="torch"` keeps the round-4 formulation (Gumbel noise, masked_fill and argmax as ~15 elementwise launches per
     actor class) for comparison."""
 
-    def __init__(self, be, hidden=128, seed=0, dtype=None, sampler="library", sample_seed=1234):
+    def __init__(self, be, hidden=128, seed=0, dtype=None, sampler="library", sample_seed=1234, record_logp=False):
         import torch
 
         self.torch = torch
@@ -123,6 +183,14 @@ class MaskedMLPPolicy:
         self.sample_seed = int(sample_seed)
         if self.multi_a and sampler == "torch":
             raise NotImplementedError("MaskedMLPPolicy(sampler='torch'): single-action agents (the BASELINE configurations)")
+        self.record_logp = bool(record_logp)
+        self.logp_a = self.logp_p = None
+        if self.record_logp:
+            if sampler != "library":
+                raise NotImplementedError("MaskedMLPPolicy(record_logp=True): the library's sampler")
+            aa, ap = be._action_buffers(0)
+            self.logp_a = torch.zeros(aa.shape, dtype=torch.float32, device=dev)
+            self.logp_p = torch.zeros(ap.shape, dtype=torch.float32, device=dev)
         self._fused_relu = None  # decided at the first call (outside any capture: GraphedStep warms the policy up first)
         self.counter = torch.zeros((), dtype=torch.float32, device=dev)
         if sampler == "torch":
@@ -169,7 +237,10 @@ class MaskedMLPPolicy:
         torch = self.torch
         la, lp = self.logits(tensors)
         if self.sampler == "library":
-            self.be.sample_policy_actions(la, lp, self.sample_seed, out=(actions_a, actions_p))
+            if self.record_logp:
+                self.be.sample_policy_actions(la, lp, self.sample_seed, out=(actions_a, actions_p, self.logp_a, self.logp_p), logp=True)
+            else:
+                self.be.sample_policy_actions(la, lp, self.sample_seed, out=(actions_a, actions_p))
             return
         la = la.view(self.be.E, self.be.n, self.MA) + self._gumbel(self.idx_a, 0.0)
         la = la.masked_fill(tensors["obs_a_action_mask"] < 0.5, -1e30)

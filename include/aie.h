@@ -593,6 +593,47 @@ int aie_specialize(aie_env* env);
 int aie_sample_policy_actions(aie_env* env, const float* d_logits_a, const float* d_logits_p, uint64_t seed,
                               int64_t global_env_offset, int32_t* d_actions_a, int32_t* d_actions_p, void* stream);
 
+/* aie_sample_policy_actions that also returns log pi(a|s) of every pick: the same picks and the same advance of
+ * `sample_t`, bit for bit (the same kernels with one more store per action slot), one launch, replayable from a hipGraph.
+ *   d_logp_a  float32 [E, n, width_a]   d_logp_p  float32 [E, width_p]   (the action buffers' shapes)
+ * logp = y_a - log T (aie_sampler_logf) with the sampler's own y = logit - max, weights and total T (csrc/aie_layout.h: a
+ * fixed sequence of float32 operations, no libm; the CPU twin aie_policy_row_logp gives the same bits); 0 for a slot
+ * where nothing is allowed (the pick there is NO-OP).  Either actor class (logits, actions, logp) may be NULL. */
+int aie_sample_policy_actions_logp(aie_env* env, const float* d_logits_a, const float* d_logits_p, uint64_t seed,
+                                   int64_t global_env_offset, int32_t* d_actions_a, int32_t* d_actions_p, float* d_logp_a,
+                                   float* d_logp_p, void* stream);
+
+/* Learning-time evaluation of STORED actions under STORED masks for new logits: what a policy-gradient trainer (PPO,
+ * A2C: training_script.py:88-133 builds one on masked logits) needs of the categorical distribution, in the sampler's own
+ * arithmetic -- evaluating the logits an action was sampled from under the masks it was sampled under returns the logp
+ * aie_sample_policy_actions_logp returned, bit for bit (importance ratio exactly 1).
+ *   B batch elements (replica-steps), any B >= 1, not tied to the environment's E;
+ *   d_logits_a [B, n, MA] / d_logits_p [B, MP]: aie_sample_policy_actions' layouts with B for E;
+ *   d_masks_a / d_masks_p: contiguous float32 in the LOGITS' layout (> 0.5 = allowed; COVID: [B, n, 1 + levels], not the
+ *       arena's collated rows); NULL = the arena's current masks, B == E only;
+ *   d_actions_a int32 [B, n, width_a] / d_actions_p int32 [B, width_p]: the stored sub-actions;
+ *   d_logp_* / d_entropy_*: float32, the actions' shapes: log pi of the stored sub-action and the entropy H of its slot.
+ * Per slot (csrc/aie_layout.h states every operation): allowed = mask > 0.5 and logit not NaN; logp_k = y_k - log T;
+ * H = log T - S / T, S = sum of w_k y_k in the scan's order.  A slot where nothing is allowed: logp 0, H 0.  A stored
+ * action its mask does not allow (or outside the row): logp -INFINITY.  An allowed entry 80 or more below the maximum has
+ * weight 0 and a finite logp.  Either actor class may be NULL, and so may any output.  One launch, asynchronous on
+ * `stream`, no synchronisation; aie_sample_policy_actions' refusals (AIE_E_UNSUPPORTED) apply. */
+int aie_policy_evaluate(aie_env* env, int64_t B, const float* d_logits_a, const float* d_logits_p, const float* d_masks_a,
+                        const float* d_masks_p, const int32_t* d_actions_a, const int32_t* d_actions_p, float* d_logp_a,
+                        float* d_logp_p, float* d_entropy_a, float* d_entropy_p, void* stream);
+
+/* Its backward: d_grad_logits_* (the logits' shapes) = the gradient of sum(d_glogp * logp + d_gentropy * H) with respect
+ * to the logits,  g_k = g_logp ([k = a] - p_k) - g_H p_k (logp_k + H)  for allowed entries (p_k = w_k / T; the operation
+ * order is in csrc/aie_layout.h) and exactly 0 for the others; every entry of the buffers is written.  M, T and S are
+ * recomputed (nothing is kept from the forward).  A slot where nothing is allowed has a zero gradient row; the g_logp of
+ * a stored action its mask does not allow contributes nothing.  d_glogp_* / d_gentropy_* may be NULL (= zeros), either
+ * actor class may be NULL.  One launch, asynchronous on `stream`. */
+int aie_policy_evaluate_backward(aie_env* env, int64_t B, const float* d_logits_a, const float* d_logits_p,
+                                 const float* d_masks_a, const float* d_masks_p, const int32_t* d_actions_a,
+                                 const int32_t* d_actions_p, const float* d_glogp_a, const float* d_glogp_p,
+                                 const float* d_gentropy_a, const float* d_gentropy_p, float* d_grad_logits_a,
+                                 float* d_grad_logits_p, void* stream);
+
 /* Same counter RNG, but each sub-action is drawn uniformly among the entries that the
  * CURRENT action masks allow (obs_a_action_mask / obs_p_action_mask; NO-OP is always
  * allowed).  This is the random policy a trainer starts from when it applies the
