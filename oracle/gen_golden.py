@@ -71,8 +71,31 @@ def sample_actions(env, rng, t_steps, p_move=0.45, p_build=0.12, p_trade=0.33):
     return acts, acts_p, A
 
 
+def scripted_policy(kind, seed):
+    """A closed-loop `policy=` callback for run_case: tests/rich_states.policy_actions (builder / market / mix) on the
+    masks of the reference's own observations."""
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+    sys.path.insert(0, os.path.dirname(HERE))
+    import rich_states
+    from helpers import make_env
+
+    info = {}
+
+    def policy(cfg, env, obs, t):
+        if "info" not in info:
+            info["info"] = rich_states.Info(make_env(cfg))
+        ob = extract_obs(env, obs)
+        a, p = rich_states.policy_actions(kind, None, ob["obs_a_action_mask"][None], ob["obs_p_action_mask"][None], seed, t,
+                                          info["info"])
+        return a[0, :, 0], p[0]
+
+    return policy
+
+
 def run_case(name, cfg, seed, t_steps, obs_steps, action_seed=123, action_kw=None,
-             n_episodes=1):
+             n_episodes=1, policy=None):
+    """policy: None (actions pre-sampled by sample_actions) or a closed-loop callback
+    policy(cfg, env, obs, t) -> (agent actions int [n], planner actions int [NB]), t = the step within the episode."""
     foundation = load_reference_foundation()
     kwargs = dict(cfg)
     scenario = kwargs.pop("scenario_name")
@@ -92,7 +115,7 @@ def run_case(name, cfg, seed, t_steps, obs_steps, action_seed=123, action_kw=Non
         out["s0_" + k] = v
     rng = np.random.RandomState(action_seed)
     acts, acts_p, A = sample_actions(env, rng, t_steps, **(action_kw or {}))
-    out["actions_a"] = acts
+    out["actions_a"] = acts  # (a closed-loop policy overwrites the rows in place, step by step)
     out["actions_p"] = acts_p
     states = []
     rews = []
@@ -109,6 +132,8 @@ def run_case(name, cfg, seed, t_steps, obs_steps, action_seed=123, action_kw=Non
         keep(0, obs)
     reset_states = []
     for t in range(t_steps):
+        if policy is not None:
+            acts[t], acts_p[t] = policy(cfg, env, obs, int(env.world.timestep))
         ad = {str(i): int(acts[t, i]) for i in range(env.n_agents)}
         if acts_p.shape[1]:
             ad["p"] = [int(x) for x in acts_p[t]]
@@ -307,9 +332,26 @@ CASES = {
 }
 
 
+def _rich_cases():
+    """Closed-loop scripted policies (tests/rich_states.py) on C2 / C3 with a scaled Build payment and scaled bracket
+    cutoffs: incomes in every bracket, ten and more houses, full books that expire whole, n trades in a step, ties."""
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+    sys.path.insert(0, os.path.dirname(HERE))
+    from rich_states import scaled_cfg
+
+    return {
+        "rich_builder_scaled_4ag": dict(cfg=scaled_cfg(4, episode_length=150), seed=61, t_steps=156,
+                                        obs_steps=[0, 1, 50, 51, 150, 151, 156], policy=scripted_policy("builder", 3)),
+        "rich_market_scaled_4ag": dict(cfg=scaled_cfg(4, episode_length=100), seed=67, t_steps=106,
+                                       obs_steps=[0, 1, 6, 50, 51, 56, 100, 101, 106], policy=scripted_policy("market", 5)),
+        "rich_mix_scaled_10ag": dict(cfg=scaled_cfg(10, episode_length=100), seed=71, t_steps=104,
+                                     obs_steps=[0, 1, 50, 51, 100, 101, 104], policy=scripted_policy("mix", 7)),
+    }
+
+
 def main():
     only = sys.argv[1:]
-    for name, kw in CASES.items():
+    for name, kw in list(CASES.items()) + list(_rich_cases().items()):
         if only and name not in only:
             continue
         run_case(name, **kw)
