@@ -166,6 +166,13 @@ class AieTensorDesc(C.Structure):
     ]
 
 
+class AieTrajSegment(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_stride", C.c_int64), ("bytes", C.c_int32), ("rows", C.c_int32)]
+
+
+TRAJ_MAX_SEGMENTS = 16  # AIE_TRAJ_MAX_SEGMENTS
+
+
 def bind(lib):
     """Declares the prototypes of every symbol include/aie.h exports."""
     vp = C.c_void_p
@@ -211,6 +218,10 @@ def bind(lib):
     lib.aie_policy_evaluate.argtypes = [vp, C.c_int64] + [vp] * 11
     lib.aie_policy_evaluate_backward.restype = C.c_int
     lib.aie_policy_evaluate_backward.argtypes = [vp, C.c_int64] + [vp] * 13
+    lib.aie_gae.restype = C.c_int
+    lib.aie_gae.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp]
+    lib.aie_trajectory_store.restype = C.c_int
+    lib.aie_trajectory_store.argtypes = [vp, C.POINTER(AieTrajSegment), C.c_int32, C.c_int32, vp, vp]
     lib.aie_sample_random_actions.restype = C.c_int
     lib.aie_sample_random_actions.argtypes = [vp, C.c_uint64, C.c_int64, vp, vp, vp]
     lib.aie_set_reward_log.restype = C.c_int
@@ -247,6 +258,7 @@ EXPORTED_SYMBOLS = [
     "aie_sample_masked_actions", "aie_sample_policy_actions", "aie_step_sample_next", "aie_step_sample_next_masked", "aie_set_reward_log", "aie_set_auto_reset",
     "aie_set_dense_log_active", "aie_step_kernel_instance", "aie_select_step_kernel", "aie_specialize", "aie_set_global_saez_buffer", "aie_sizeof_config",
     "aie_arena_info", "aie_step_range", "aie_sample_policy_actions_logp", "aie_policy_evaluate", "aie_policy_evaluate_backward",
+    "aie_gae", "aie_trajectory_store",
 ]
 STEP_HEAD, STEP_TAIL, STEP_OBSERVE, STEP_REBASE, STEP_RETAX = 1, 2, 4, 8, 16  # AIE_STEP_*
 STEP_REGEN, STEP_EMIT, STEP_CLOSE = 64, 128, 256  # the end of a step in three parts (scenario hooks run between them)

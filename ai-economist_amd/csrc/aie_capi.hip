@@ -1025,6 +1025,87 @@ int aie_policy_evaluate_backward(aie_env* env, int64_t B, const float* d_logits_
   return AIE_OK;
 }
 
+int aie_gae(aie_env* env, int32_t T, const float* d_log, int32_t n_slots, int32_t first_slot, const float* d_values_a,
+            const float* d_values_p, float gamma, float lambda, float* d_adv_a, float* d_adv_p, float* d_ret_a, float* d_ret_p,
+            void* stream) {
+  if (!env) return AIE_E_INVALID;
+  if (T < 1 || T > n_slots || first_slot < 0 || first_slot >= n_slots || !d_log) {
+    snprintf(env->err, sizeof(env->err), "aie_gae: T = %d steps from slot %d of a log of %d slots at %p (needs a log, 1 <= T <= "
+             "n_slots, 0 <= first_slot < n_slots)", T, first_slot, n_slots, (const void*)d_log);
+    return AIE_E_INVALID;
+  }
+  if (((d_adv_a || d_ret_a) && !d_values_a) || ((d_adv_p || d_ret_p) && !d_values_p)) {
+    snprintf(env->err, sizeof(env->err), "aie_gae: an output without its values");
+    return AIE_E_INVALID;
+  }
+  const int64_t row = (int64_t)env->P.E * (env->P.n + 2);
+  if (row > 0x7fffff00ll) {
+    snprintf(env->err, sizeof(env->err), "aie_gae: %lld floats per log row are more than one launch takes", (long long)row);
+    return AIE_E_INVALID;
+  }
+  aie_gae_args A;
+  memset(&A, 0, sizeof(A));
+  A.log = d_log;
+  // (an actor class none of whose outputs is asked for is left out of the launch)
+  A.va = (d_adv_a || d_ret_a) ? d_values_a : nullptr;
+  A.vp = (d_adv_p || d_ret_p) ? d_values_p : nullptr;
+  if (!A.va && !A.vp) return AIE_OK;
+  A.adv_a = d_adv_a;
+  A.adv_p = d_adv_p;
+  A.ret_a = d_ret_a;
+  A.ret_p = d_ret_p;
+  A.T = T;
+  A.slots = n_slots;
+  A.first = first_slot;
+  A.E = env->P.E;
+  A.n = env->P.n;
+  A.gamma = gamma;
+  A.gl = aie_gae_gl(gamma, lambda);
+  AIE_HIP_CHECK(env, hipSetDevice(env->device));
+  hipLaunchKernelGGL(aie_gae_kernel, dim3((unsigned)((row + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream), A);
+  AIE_HIP_CHECK(env, hipGetLastError());
+  return AIE_OK;
+}
+
+int aie_trajectory_store(aie_env* env, const aie_traj_segment* segs, int32_t n_segs, int32_t n_slots, int32_t* d_slot, void* stream) {
+  if (!env) return AIE_E_INVALID;
+  static_assert(AIE_TRAJ_SEGMENTS == AIE_TRAJ_MAX_SEGMENTS, "aie_layout.h and aie.h disagree on the segment count");
+  if (!segs || n_segs < 1 || n_segs > AIE_TRAJ_MAX_SEGMENTS || n_slots < 1 || !d_slot) {
+    snprintf(env->err, sizeof(env->err), "aie_trajectory_store: %d segments (1 .. %d), %d slots (>= 1), segments and slot counters "
+             "not NULL", n_segs, AIE_TRAJ_MAX_SEGMENTS, n_slots);
+    return AIE_E_INVALID;
+  }
+  aie_traj_args A;
+  memset(&A, 0, sizeof(A));
+  for (int g = 0; g < n_segs; ++g) {
+    const aie_traj_segment& s = segs[g];
+    const uintptr_t sp = reinterpret_cast<uintptr_t>(s.src), dp = reinterpret_cast<uintptr_t>(s.dst);
+    const int64_t count = s.bytes / 4;
+    if (!s.src || !s.dst || s.bytes < 4 || (s.bytes & 3) || (s.src_stride & 3) || (sp & 3) || (dp & 3) || s.rows < 0 ||
+        s.rows > 32767 || (s.rows > 1 && count % s.rows)) {
+      snprintf(env->err, sizeof(env->err), "aie_trajectory_store: segment %d (%d bytes per replica, source stride %lld, rows %d): "
+               "pointers not NULL and 4-byte aligned, sizes and strides multiples of 4, rows dividing the element count", g,
+               s.bytes, (long long)s.src_stride, s.rows);
+      return AIE_E_INVALID;
+    }
+    aie_traj_seg_k& k = A.seg[g];
+    k.src = static_cast<const uint8_t*>(s.src);
+    k.dst = static_cast<uint8_t*>(s.dst);
+    k.src_stride = s.src_stride;
+    k.bytes = s.bytes;
+    k.rows = (int16_t)s.rows;
+    k.wide = (int16_t)(s.rows <= 1 && !((sp | dp | (uintptr_t)s.src_stride | (uintptr_t)s.bytes) & 15));
+  }
+  A.slot = d_slot;
+  A.n_segs = n_segs;
+  A.n_slots = n_slots;
+  A.E = env->P.E;
+  AIE_HIP_CHECK(env, hipSetDevice(env->device));
+  hipLaunchKernelGGL(aie_trajectory_store_kernel, dim3((unsigned)env->P.E), dim3(256), 0, static_cast<hipStream_t>(stream), A);
+  AIE_HIP_CHECK(env, hipGetLastError());
+  return AIE_OK;
+}
+
 // Which step kernel runs this environment: >= 0 = compile-time instance (index into aie_spec_generated.h), -1 = generic.
 int aie_step_kernel_instance(aie_env* env) { return env ? env->spec : -2; }
 

@@ -4710,6 +4710,134 @@ __device__ __forceinline__ void policy_eval_body(const aie_policy_eval_args& A) 
 }
 extern "C" __global__ void __launch_bounds__(256) aie_policy_eval_kernel(const aie_policy_eval_args A) { policy_eval_body<false>(A); }
 extern "C" __global__ void __launch_bounds__(256) aie_policy_eval_bwd_kernel(const aie_policy_eval_args A) { policy_eval_body<true>(A); }
+
+// ---- generalised advantage estimation from the reward log (include/aie.h: aie_gae) ---------------------------------------
+// The recurrence (aie_layout.h: aie_gae_step) is serial in t down a column (replica, actor) and is NOT re-associated across
+// time: these are the bits of the plain float32 loop.  What is parallel is the loads.  A lane per float of a log row
+// (lane c = e (n + 2) + j), so a wave's reward loads are 256 contiguous bytes of the row whatever n is; the done flag is a
+// second load of the same lines (the lane's replica's last column); the values come from one load per step through a
+// per-lane pointer (agents' and planner's tensors), consecutive lanes on consecutive floats within a class.  The lanes on
+// the done column (one in n + 2) and those of a class the caller left out retire at once.  Time runs backwards in chunks of
+// AIE_GAE_U steps, two register buffers: the 3 x AIE_GAE_U loads of the NEXT chunk are issued before the two dependent
+// operations per step of the current one, so with one or two waves per CU (C2: 4096 x 6 lanes = 384 waves) there are
+// ~6 KB per wave in flight -- memory-level parallelism from loads, not from waves.  Workgroups of one wave spread the few
+// waves over every CU.
+#define AIE_GAE_U 8
+struct GaeLane {
+  const float *r, *d, *v;  // the lane's reward / done column in slot 0 of the log; its value in row 0
+  float *adv, *ret;
+  uint32_t row, vstride;   // floats per log row; per value row
+};
+__device__ __forceinline__ void gae_load(const GaeLane& L, int t0, int slot0, int slots, float (&r)[AIE_GAE_U], float (&d)[AIE_GAE_U],
+                                         float (&v)[AIE_GAE_U]) {
+#pragma unroll
+  for (int k = 0; k < AIE_GAE_U; ++k) {
+    const int t = t0 - k;
+    r[k] = d[k] = v[k] = 0.0f;
+    if (t >= 0) {  // (wave-uniform; k <= t < slots: one wrap)
+      const int s = slot0 - k < 0 ? slot0 - k + slots : slot0 - k;
+      r[k] = L.r[(size_t)s * L.row];
+      d[k] = L.d[(size_t)s * L.row];
+      v[k] = L.v[(size_t)t * L.vstride];
+    }
+  }
+}
+__device__ __forceinline__ void gae_chunk(const GaeLane& L, int t0, const float (&r)[AIE_GAE_U], const float (&d)[AIE_GAE_U],
+                                          const float (&v)[AIE_GAE_U], float gamma, float gl, float& v_next, float& a_next) {
+#pragma unroll
+  for (int k = 0; k < AIE_GAE_U; ++k) {
+    const int t = t0 - k;
+    if (t >= 0) {
+      const float a = aie_gae_step(r[k], v[k], v_next, a_next, d[k] > 0.5f, gamma, gl);
+      if (L.adv) L.adv[(size_t)t * L.vstride] = a;
+      if (L.ret) L.ret[(size_t)t * L.vstride] = aie_gae_return(a, v[k]);
+      a_next = a;
+      v_next = v[k];
+    }
+  }
+}
+extern "C" __global__ void __launch_bounds__(64) aie_gae_kernel(const aie_gae_args A) {
+  asm volatile("" ::"s"(A.log), "s"(A.va), "s"(A.vp), "s"(A.adv_a), "s"(A.adv_p), "s"(A.ret_a), "s"(A.ret_p), "s"(A.T), "s"(A.slots),
+               "s"(A.first), "s"(A.E), "s"(A.n), "s"(A.gamma), "s"(A.gl));
+  const uint32_t W = (uint32_t)A.n + 2u, row = (uint32_t)A.E * W;
+  const uint32_t c = blockIdx.x * 64u + threadIdx.x;
+  if (c >= row) return;
+  const uint32_t e = c / W, j = c - e * W;
+  const bool agent = j < (uint32_t)A.n;
+  const float* vals = agent ? A.va : A.vp;
+  if (j > (uint32_t)A.n || !vals) return;  // the done column; a class that is left out (no barrier below)
+  GaeLane L;
+  L.row = row;
+  L.vstride = agent ? (uint32_t)A.E * (uint32_t)A.n : (uint32_t)A.E;
+  const uint32_t vo = agent ? e * (uint32_t)A.n + j : e;
+  L.r = A.log + c;
+  L.d = A.log + (e * W + (uint32_t)A.n + 1u);
+  L.v = vals + vo;
+  L.adv = agent ? A.adv_a : A.adv_p;
+  L.ret = agent ? A.ret_a : A.ret_p;
+  if (L.adv) L.adv += vo;
+  if (L.ret) L.ret += vo;
+  const int T = A.T, slots = A.slots;
+  float v_next = L.v[(size_t)T * L.vstride], a_next = 0.0f;  // row T: the bootstrap value; A_T = 0
+  int t0 = T - 1;
+  int slot0 = (int)((uint32_t)A.first + (uint32_t)t0);  // first, t0 < slots: one wrap
+  if (slot0 < 0 || slot0 >= slots) slot0 = (int)((uint32_t)slot0 - (uint32_t)slots);
+  float r0[AIE_GAE_U], d0[AIE_GAE_U], v0[AIE_GAE_U], r1[AIE_GAE_U], d1[AIE_GAE_U], v1[AIE_GAE_U];
+  gae_load(L, t0, slot0, slots, r0, d0, v0);
+  while (t0 >= 0) {
+    int sn = slot0 - AIE_GAE_U;
+    if (sn < 0) sn += slots;  // (used only while t0 - U >= 0, i.e. U < slots: one wrap)
+    gae_load(L, t0 - AIE_GAE_U, sn, slots, r1, d1, v1);
+    gae_chunk(L, t0, r0, d0, v0, A.gamma, A.gl, v_next, a_next);
+    t0 -= AIE_GAE_U;
+    slot0 = sn - AIE_GAE_U;
+    if (slot0 < 0) slot0 += slots;
+    if (t0 < 0) break;
+    gae_load(L, t0 - AIE_GAE_U, slot0, slots, r0, d0, v0);
+    gae_chunk(L, t0, r1, d1, v1, A.gamma, A.gl, v_next, a_next);
+    t0 -= AIE_GAE_U;
+  }
+}
+
+// ---- trajectory store: this step's blocks into the replica's ring slot (include/aie.h: aie_trajectory_store) -------------
+// A workgroup per replica.  Every thread reads the replica's slot counter, the barrier, then thread 0 -- the only writer of
+// that counter in the launch -- advances it: nothing that changes from step to step is a kernel argument, so a captured launch
+// walks the ring on replay (the reward log's slot and the sampler's draw index work the same way).  A counter outside the
+// ring counts as 0 (nothing is written out of bounds whatever the caller left there).  The segments are dealt to the
+// workgroup's four waves, which copy side by side: 16 bytes per lane where the host found source, destination, stride and
+// size aligned for every replica and slot (a wave-uniform flag per segment), else 4 bytes per lane; a segment with rows > 1
+// is a [rows][cols] block stored as [cols][rows] (4-byte elements; stores coalesced, the strided loads come out of a block of
+// a few hundred bytes).
+extern "C" __global__ void __launch_bounds__(256) aie_trajectory_store_kernel(const aie_traj_args A) {
+  const uint32_t e = blockIdx.x;
+  int32_t s = A.slot[e];
+  __syncthreads();
+  if (threadIdx.x == 0) A.slot[e] = (uint32_t)s + 1u < (uint32_t)A.n_slots ? s + 1 : 0;
+  if ((uint32_t)s >= (uint32_t)A.n_slots) s = 0;
+  const int lane = (int)threadIdx.x & 63;
+  for (int g = aie::uni((int)(threadIdx.x >> 6)); g < A.n_segs; g += 4) {
+    const uint8_t* src = A.seg[g].src + (int64_t)e * A.seg[g].src_stride;
+    const int32_t bytes = A.seg[g].bytes, rows = A.seg[g].rows;
+    uint8_t* dst = A.seg[g].dst + ((int64_t)s * A.E + e) * bytes;
+    if (rows > 1) {
+      const uint32_t* s32 = reinterpret_cast<const uint32_t*>(src);
+      uint32_t* d32 = reinterpret_cast<uint32_t*>(dst);
+      const uint32_t count = (uint32_t)bytes >> 2, cols = count / (uint32_t)rows;
+      for (uint32_t i = (uint32_t)lane; i < count; i += 64u) {
+        const uint32_t cc = i / (uint32_t)rows, rr = i - cc * (uint32_t)rows;
+        d32[i] = s32[rr * cols + cc];
+      }
+    } else if (A.seg[g].wide) {
+      const uint4* s128 = reinterpret_cast<const uint4*>(src);
+      uint4* d128 = reinterpret_cast<uint4*>(dst);
+      for (uint32_t i = (uint32_t)lane; i < ((uint32_t)bytes >> 4); i += 64u) d128[i] = s128[i];
+    } else {
+      const uint32_t* s32 = reinterpret_cast<const uint32_t*>(src);
+      uint32_t* d32 = reinterpret_cast<uint32_t*>(dst);
+      for (uint32_t i = (uint32_t)lane; i < ((uint32_t)bytes >> 2); i += 64u) d32[i] = s32[i];
+    }
+  }
+}
 #endif  // !AIE_JIT
 
 #if defined(AIE_JIT) && !defined(AIE_JIT_OSE)

@@ -1663,6 +1663,51 @@ AIE_HD static inline void aie_policy_row_backward(const aie_policy_row* R, const
     }
   }
 }
+/* Generalised advantage estimation (include/aie.h: aie_gae), one step of the reverse recurrence down one column (replica,
+ * actor): the plain serial float32 loop of every trainer, stated once -- the kernel calls it, tests/test_trajectory_cpu.py
+ * compiles it.  gl = gamma * lambda as ONE rounded float32 product (aie_gae_gl), formed once per call;
+ *   delta_t = done_t ? r_t - V_t : (r_t + gamma V_{t+1}) - V_t       A_t = done_t ? delta_t : delta_t + gl A_{t+1}
+ * with every product and sum rounded on its own.  A done step SELECTS: V_{t+1} and A_{t+1} behind an episode end are the
+ * restarted episode's (auto-reset) and take no part -- a NaN or an infinity there does not reach A_t (0 x NaN would).
+ * The return is aie_gae_return(A_t, V_t) = A_t + V_t. */
+AIE_HD static inline float aie_gae_gl(float gamma, float lambda) {
+  AIE_NOCONTRACT
+  return gamma * lambda;
+}
+AIE_HD static inline float aie_gae_step(float r, float v, float v_next, float a_next, int done, float gamma, float gl) {
+  AIE_NOCONTRACT
+  const float gv = gamma * v_next;
+  const float rv = r + gv;
+  const float delta = (done ? r : rv) - v;
+  const float ga = gl * a_next;
+  const float run = delta + ga;
+  return done ? delta : run;
+}
+AIE_HD static inline float aie_gae_return(float a, float v) { return a + v; }
+/* The kernel's argument (aie_gae fills it): 88 bytes.  A lane per float of a log row, lane c = e (n + 2) + j: j < n agent j,
+ * j == n the planner, j == n + 1 (the done flag itself) idle.  Time t is ring slot (first + t) % slots. */
+typedef struct aie_gae_args {
+  const float *log, *va, *vp; /* the log; values [T + 1][E][n] / [T + 1][E] (NULL: the class is left out) */
+  float *adv_a, *adv_p, *ret_a, *ret_p;
+  int32_t T, slots, first, E, n;
+  float gamma, gl;
+} aie_gae_args;
+/* aie_trajectory_store's kernel argument: the caller's segments (include/aie.h: aie_traj_segment, 32 bytes each) with the
+ * copy width decided on the host: wide != 0 = 16-byte lane accesses (source, destination, stride and size allow it for
+ * every replica and slot), else 4-byte ones. */
+#define AIE_TRAJ_SEGMENTS 16
+typedef struct aie_traj_seg_k {
+  const uint8_t* src;
+  uint8_t* dst;
+  int64_t src_stride;
+  int32_t bytes;
+  int16_t rows, wide;
+} aie_traj_seg_k;
+typedef struct aie_traj_args {
+  aie_traj_seg_k seg[AIE_TRAJ_SEGMENTS];
+  int32_t* slot;
+  int32_t n_segs, n_slots, E, pad_;
+} aie_traj_args;
 /* What the sampler kernel needs of the parameter block, as its kernel argument (aie_sampler_args_of fills it).  A group
  * is a replica's agent rows or its planner rows: row r's entry k has its logit at logits[e lg_estride + r lrs + k] and its
  * mask at the arena's float mk_off / 4 + e mk_estride + r mrs + k mks (COVID's collated agent masks: mrs 1, mks n). */

@@ -428,6 +428,67 @@ class DeviceBackend:
             ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gs[3]), ptr(grad_a), ptr(grad_p), self._stream()))
         return grad_a, grad_p
 
+    def trajectory_segment(self, src, dst, transpose_rows=0):
+        """One aie_traj_segment: `src`, a device tensor whose dimension 0 is the replica ([E, ...], each replica's block
+        contiguous; the replica stride may be anything -- an arena tensor's, a record field's), stored into `dst`
+        ([n_slots, E, ...] contiguous, same dtype, same bytes per replica).  transpose_rows > 1: the replica's block is
+        [transpose_rows][cols] 4-byte elements and is stored as [cols][transpose_rows]."""
+        if src.shape[0] != self.E or dst.dim() < 2 or dst.shape[1] != self.E or src.dtype != dst.dtype:
+            raise ValueError("trajectory segment: src [E, ...] and dst [n_slots, E, ...] of one dtype")
+        if not dst.is_contiguous() or not src[0].is_contiguous():
+            raise ValueError("trajectory segment: dst and each replica's block of src must be contiguous")
+        nbytes = src[0].numel() * src.element_size()
+        if nbytes != dst[0, 0].numel() * dst.element_size():
+            raise ValueError("trajectory segment: %d bytes per replica in src, %d in dst"
+                             % (nbytes, dst[0, 0].numel() * dst.element_size()))
+        stride = (src.stride(0) if self.E > 1 else src[0].numel()) * src.element_size()
+        return _cabi.AieTrajSegment(src.data_ptr(), dst.data_ptr(), stride, nbytes, int(transpose_rows)), (src, dst)
+
+    def trajectory_store(self, segments, n_slots, slot_counters):
+        """aie_trajectory_store: every segment's block of replica e goes to ring slot slot_counters[e] of its destination,
+        then the counter advances modulo n_slots -- one launch on the current stream, capturable (the slot index lives on
+        the device).  segments: what trajectory_segment returns (or bare _cabi.AieTrajSegment), at most
+        _cabi.TRAJ_MAX_SEGMENTS; slot_counters: int32 [E] device tensor, zeroed by the caller."""
+        torch = _torch()
+        segs = [s[0] if isinstance(s, tuple) else s for s in segments]
+        if (slot_counters.dtype != torch.int32 or slot_counters.numel() != self.E or not slot_counters.is_contiguous()
+                or slot_counters.device != self.device):
+            raise ValueError("slot_counters: a contiguous int32 device tensor of %d elements" % self.E)
+        arr = (_cabi.AieTrajSegment * max(1, len(segs)))(*segs)
+        self._check(self.lib.aie_trajectory_store(self.handle, arr, len(segs), int(n_slots),
+                                                  C.c_void_p(slot_counters.data_ptr()), self._stream()))
+
+    def gae(self, T, log, values_a, values_p, gamma, lam, first_slot=0, advantages=True, returns=True, out=None):
+        """aie_gae: (adv_a, adv_p, ret_a, ret_p) of T steps from a reward log (float32 [n_slots, E, n + 2], time t in slot
+        (first_slot + t) % n_slots) and the values (float32 [T + 1, E, n] / [T + 1, E], row T the bootstrap; either may be
+        None).  One launch on the current stream.  out=(adv_a, adv_p, ret_a, ret_p) to fill the caller's own."""
+        torch = _torch()
+        T = int(T)
+        f = dict(dtype=torch.float32, device=self.device)
+        if log.dtype != torch.float32 or not log.is_contiguous() or log.device != self.device or log.dim() != 3 \
+                or tuple(log.shape[1:]) != (self.E, self.n + 2):
+            raise ValueError("gae: the log is a contiguous float32 device tensor [n_slots, %d, %d]" % (self.E, self.n + 2))
+        for v, per, what in ((values_a, self.E * self.n, "values_a"), (values_p, self.E, "values_p")):
+            if v is not None and (v.dtype != torch.float32 or not v.is_contiguous() or v.device != self.device
+                                  or v.numel() != (T + 1) * per):
+                raise ValueError("gae: %s is a contiguous float32 device tensor of (T + 1) x %d elements" % (what, per))
+        if out is None:
+            sa, sp = (T, self.E, self.n), (T, self.E)
+            out = [torch.empty(sa, **f) if values_a is not None and advantages else None,
+                   torch.empty(sp, **f) if values_p is not None and advantages else None,
+                   torch.empty(sa, **f) if values_a is not None and returns else None,
+                   torch.empty(sp, **f) if values_p is not None and returns else None]
+        else:
+            for o, per, what in zip(out, (self.E * self.n, self.E) * 2, ("adv_a", "adv_p", "ret_a", "ret_p")):
+                if o is not None and (o.dtype != torch.float32 or not o.is_contiguous() or o.device != self.device
+                                      or o.numel() != T * per):
+                    raise ValueError("gae: %s is a contiguous float32 device tensor of T x %d elements" % (what, per))
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        self._check(self.lib.aie_gae(self.handle, T, ptr(log), int(log.shape[0]), int(first_slot), ptr(values_a), ptr(values_p),
+                                     C.c_float(gamma), C.c_float(lam), ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]),
+                                     self._stream()))
+        return tuple(out)
+
     def _action_buffers(self, slot):
         torch = _torch()
         if self._rand_a is None:

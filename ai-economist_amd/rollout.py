@@ -17,20 +17,34 @@ torch is plumbing here (streams, graph capture, the policy network); the environ
 
 
 class GraphedStep:
-    def __init__(self, env, policy, auto_reset=True, unroll=1, warmup=3):
+    def __init__(self, env, policy, auto_reset=True, unroll=1, warmup=3, trajectory=None):
         """env: a batched environment (foundation.make_env_instance(..., n_envs=E)), already reset.
         policy(tensors, actions_a, actions_p): reads observation tensors (env.backend.tensors: "obs_a_flat",
         "obs_a_action_mask", "obs_p_flat", ... zero-copy views of the arena) and writes int32 actions IN PLACE into
         actions_a [E, n, width] / actions_p [E, width_p].  It is captured: no host synchronisation, no data-dependent
         Python control flow, fixed shapes.
         auto_reset: replicas restart right behind the step that ends their episode (aie_set_auto_reset).
-        unroll: environment steps per replay."""
+        unroll: environment steps per replay.
+        trajectory: a `Trajectory` of this environment, or None.  With one, an iteration is policy -> trajectory.store(...)
+        -> step: the observations and masks the policy saw, its actions and -- where the trajectory keeps them -- the
+        policy's `logp_a` / `logp_p` and `value_a` / `value_p` tensors go into the trajectory's next slot, one more launch
+        per step, inside the graph.  The warm-up iterations are real steps and real stores: call trajectory.rewind() (and
+        reset the environment, if a clean start is wanted) after construction, before the first fragment."""
         import torch
 
         if env.backend.host_components:  # (its captured aie_step and auto-reset would skip their hooks)
             raise NotImplementedError("GraphedStep: the environment has host components (%s), which run between launches "
                                       "issued from Python: step it with env.step / env.reset"
                                       % ", ".join(env.backend.host_components))
+        self.trajectory = trajectory
+        if trajectory is not None:  # (checked before anything about the environment changes)
+            if trajectory.be is not env.backend:
+                raise ValueError("GraphedStep: the trajectory belongs to another environment")
+            for flag, names in ((trajectory.has_logp, ("logp_a", "logp_p")), (trajectory.has_values, ("value_a", "value_p"))):
+                for name in names:
+                    if flag and getattr(policy, name, None) is None:
+                        raise ValueError("GraphedStep: the trajectory stores %s but the policy has no tensor attribute of that "
+                                         "name (MaskedMLPPolicy: record_logp=True / value_head=True)" % name)
         self.torch = torch
         self.env, self.be = env, env.backend
         self.policy = policy
@@ -48,6 +62,12 @@ class GraphedStep:
 
     def _iteration(self):
         self.policy(self.be.tensors, self.actions_a, self.actions_p)
+        traj = self.trajectory
+        if traj is not None:
+            pol = self.policy
+            traj.store(self.actions_a, self.actions_p,
+                       pol.logp_a if traj.has_logp else None, pol.logp_p if traj.has_logp else None,
+                       pol.value_a if traj.has_values else None, pol.value_p if traj.has_values else None)
         self.be.step(self.actions_a, self.actions_p)
 
     def eager(self, iterations=1):
@@ -77,6 +97,123 @@ class GraphedStep:
         """n replays = n * unroll environment steps; asynchronous like every other call."""
         for _ in range(n):
             self.graph.replay()
+
+
+class Trajectory:
+    """A rollout fragment of T steps in device memory, filled from INSIDE a captured iteration: one aie_trajectory_store
+    launch per step copies what the policy saw and did into the next slot of ring buffers whose slot index is a
+    per-replica counter on the device (a captured `buf[t].copy_(x)` would freeze t), and the step kernel writes (rewards,
+    planner reward, done) of the same step into the same slot of a reward log of exactly T slots, so both rings wrap
+    together.  aie_gae then turns the log and the stored values into advantages and returns in one launch.
+
+        obs[name]   [T, E, ...]     any arena tensor (`observations`), the tensor's dtype, as the policy saw it at step t
+        masks_a     [T, E, n, MA]   masks_p [T, E, MP]   the action masks in the LOGITS' layout (== Backend.action_masks();
+                                    COVID's collated rows are transposed on the way)
+        actions_a / actions_p       int32, the action buffers' shapes behind [T]
+        logp_a / logp_p             float32, the same shapes (logp=True)
+        values_a    [T + 1, E, n]   values_p [T + 1, E]  (values=True); row T is the bootstrap value: finish()
+        slots       int32 [E]       the counters
+
+    THE INVARIANT: exactly one store() per environment step, between the policy and Backend.step -- the store's ring and
+    the reward log's ring advance one slot each per step and stay aligned only then.  After T steps (or any multiple)
+    slot t holds time t.  `done` at step t means the episode ended there; under auto-reset slot t + 1 holds the restarted
+    episode's first observation, and aie_gae does not carry value or advantage across that boundary."""
+
+    def __init__(self, env, T, observations=("obs_a_flat", "obs_p_flat"), logp=True, values=True):
+        import torch
+
+        be = env.backend
+        if be.host_components:
+            raise NotImplementedError("Trajectory: the environment has host components (%s); their hooks run between launches "
+                                      "issued from Python, not inside a captured iteration" % ", ".join(be.host_components))
+        if getattr(be, "reward_log", None) is not None:
+            raise RuntimeError("Trajectory: the backend already has a reward log (sharding.RewardLogGather owns it); a "
+                               "trajectory installs its own of exactly T slots")
+        self.env, self.be, self.T = env, be, int(T)
+        if self.T < 1:
+            raise ValueError("Trajectory: T >= 1")
+        T, E, n, dev = self.T, be.E, be.n, be.device
+        t = be.tensors
+        self.has_logp, self.has_values = bool(logp), bool(values)
+        self.obs = {name: torch.zeros((T,) + tuple(t[name].shape), dtype=t[name].dtype, device=dev) for name in observations}
+        ma, mp = t["obs_a_action_mask"], t["obs_p_action_mask"]
+        if ma.dtype != torch.float32 or mp.dtype != torch.float32:
+            raise NotImplementedError("Trajectory: float32 action masks")
+        from . import _cabi
+
+        self._mask_rows = 0
+        if int(be.cfg.scenario) == _cabi.SCN_COVID:  # the arena's collated [E, 1 + levels, n] -> [E, n, 1 + levels]
+            self._mask_rows = int(ma.shape[1])
+            self.masks_a = torch.zeros((T, E, ma.shape[2], ma.shape[1]), dtype=torch.float32, device=dev)
+        else:
+            self.masks_a = torch.zeros((T,) + tuple(ma.shape), dtype=torch.float32, device=dev)
+        self.masks_p = torch.zeros((T,) + tuple(mp.shape), dtype=torch.float32, device=dev)
+        aa, ap = be._action_buffers(0)
+        self.actions_a = torch.zeros((T,) + tuple(aa.shape), dtype=torch.int32, device=dev)
+        self.actions_p = torch.zeros((T,) + tuple(ap.shape), dtype=torch.int32, device=dev)
+        self.logp_a = self.logp_p = self.values_a = self.values_p = None
+        if self.has_logp:
+            self.logp_a = torch.zeros((T,) + tuple(aa.shape), dtype=torch.float32, device=dev)
+            self.logp_p = torch.zeros((T,) + tuple(ap.shape), dtype=torch.float32, device=dev)
+        if self.has_values:
+            self.values_a = torch.zeros((T + 1, E, n), dtype=torch.float32, device=dev)
+            self.values_p = torch.zeros((T + 1, E), dtype=torch.float32, device=dev)
+        self.slots = torch.zeros(E, dtype=torch.int32, device=dev)
+        self.log = be.set_reward_log(T)
+        seg = be.trajectory_segment
+        self._fixed = [seg(t[name], self.obs[name]) for name in observations]
+        self._fixed.append(seg(ma, self.masks_a, transpose_rows=self._mask_rows))
+        self._fixed.append(seg(mp, self.masks_p))
+        if len(self._fixed) + 2 + 2 * self.has_logp + 2 * self.has_values > _cabi.TRAJ_MAX_SEGMENTS:
+            raise ValueError("Trajectory: more tensors than one store launch takes (%d segments)" % _cabi.TRAJ_MAX_SEGMENTS)
+
+    def store(self, actions_a, actions_p, logp_a=None, logp_p=None, values_a=None, values_p=None):
+        """ONE aie_trajectory_store launch on the current stream: the observations and masks as they stand, the given
+        actions and -- where the trajectory keeps them -- logp and values go to the replicas' next slot, and the counters
+        advance.  Call it between the policy and Backend.step, exactly once per environment step (see the class)."""
+        be, E = self.be, self.be.E
+        segs = list(self._fixed)
+        segs.append(be.trajectory_segment(actions_a.view(self.actions_a.shape[1:]), self.actions_a))
+        segs.append(be.trajectory_segment(actions_p.view(self.actions_p.shape[1:]), self.actions_p))
+        for have, pairs, what in ((self.has_logp, ((logp_a, self.logp_a), (logp_p, self.logp_p)), "logp"),
+                                  (self.has_values, ((values_a, self.values_a), (values_p, self.values_p)), "values")):
+            if have:
+                for src, dst in pairs:
+                    if src is None:
+                        raise ValueError("Trajectory.store: this trajectory keeps %s: pass both tensors" % what)
+                    segs.append(be.trajectory_segment(src.view((E,) + tuple(dst.shape[2:])), dst[: self.T]))
+        be.trajectory_store(segs, self.T, self.slots)
+
+    def rewind(self):
+        """The next store -- and the next step's rewards -- go to slot 0 again.  Outside capture (it zeroes the counters and
+        restarts the reward log, which waits for the device)."""
+        self.slots.zero_()
+        self.be.rewind_reward_log()
+
+    def finish(self, values_a, values_p):
+        """Row T of the values: the bootstrap value of the observation behind the fragment's last step."""
+        if not self.has_values:
+            raise ValueError("Trajectory.finish: this trajectory keeps no values")
+        self.values_a[self.T].copy_(values_a.view(self.values_a.shape[1:]))
+        self.values_p[self.T].copy_(values_p.view(self.values_p.shape[1:]))
+
+    def advantages(self, gamma=0.998, lam=0.98):
+        """(adv_a [T, E, n], adv_p [T, E], ret_a, ret_p): aie_gae on the reward log and the stored values, one launch.
+        Call it after T (or a multiple of T) steps since rewind(), and after finish()."""
+        if not self.has_values:
+            raise ValueError("Trajectory.advantages: this trajectory keeps no values")
+        return self.be.gae(self.T, self.log, self.values_a, self.values_p, gamma, lam)
+
+    def flat(self):
+        """Everything as [T * E, ...] views (values: rows 0 .. T - 1), ready for rollout.masked_logp_entropy with B = T * E."""
+        out = {"obs": {k: v.flatten(0, 1) for k, v in self.obs.items()}}
+        for k in ("masks_a", "masks_p", "actions_a", "actions_p", "logp_a", "logp_p"):
+            v = getattr(self, k)
+            out[k] = None if v is None else v.flatten(0, 1)
+        out["values_a"] = None if self.values_a is None else self.values_a[: self.T].flatten(0, 1)
+        out["values_p"] = None if self.values_p is None else self.values_p[: self.T].flatten(0, 1)
+        out["done"] = self.log[..., -1].flatten(0, 1)
+        return out
 
 
 def _masked_categorical():
@@ -147,9 +284,13 @@ class MaskedMLPPolicy:
     buffers' shapes) with log pi(a|s) of every pick, in place -- a trainer copies them into its trajectory with the
     actions and Backend.action_masks().
     `sampler="torch"` keeps the round-4 formulation (Gumbel noise, masked_fill and argmax as ~15 elementwise launches per
-    actor class) for comparison."""
+    actor class) for comparison.
+    value_head=True: one more output column per actor class (the critic), written in place on every call into the fixed
+    float32 tensors `value_a` [E, n] and `value_p` [E] -- what rollout.Trajectory stores beside the actions.  Its weights
+    are drawn behind the six layers', so the policy's own weights do not depend on it."""
 
-    def __init__(self, be, hidden=128, seed=0, dtype=None, sampler="library", sample_seed=1234, record_logp=False):
+    def __init__(self, be, hidden=128, seed=0, dtype=None, sampler="library", sample_seed=1234, record_logp=False,
+                 value_head=False):
         import torch
 
         self.torch = torch
@@ -174,6 +315,13 @@ class MaskedMLPPolicy:
         self.wp2, self.bp2 = lin(hidden, hidden)
         self.wp3, self.bp3 = lin(hidden, MP)
         self.MA, self.MP = MA, MP
+        self.value_head = bool(value_head)
+        self.value_a = self.value_p = None
+        if self.value_head:
+            self.wav, self.bav = lin(hidden, 1)
+            self.wpv, self.bpv = lin(hidden, 1)
+            self.value_a = torch.zeros((be.E, be.n), dtype=torch.float32, device=dev)
+            self.value_p = torch.zeros((be.E,), dtype=torch.float32, device=dev)
         cfg = be.cfg
         self.multi_a = bool(cfg.multi_action_mode_agents)
         self.multi_p = bool(cfg.multi_action_mode_planner)
@@ -227,10 +375,14 @@ class MaskedMLPPolicy:
         h = self._layer(self.ba1, xa, self.wa1)
         h = self._layer(self.ba2, h, self.wa2)
         la = torch.addmm(self.ba3, h, self.wa3).float()
+        if self.value_head:
+            self.value_a.view(-1, 1).copy_(torch.addmm(self.bav, h, self.wav))
         xp = tensors["obs_p_flat"].to(self.dtype)
         h = self._layer(self.bp1, xp, self.wp1)
         h = self._layer(self.bp2, h, self.wp2)
         lp = torch.addmm(self.bp3, h, self.wp3).float()
+        if self.value_head:
+            self.value_p.view(-1, 1).copy_(torch.addmm(self.bpv, h, self.wpv))
         return la, lp
 
     def __call__(self, tensors, actions_a, actions_p):

@@ -634,6 +634,52 @@ int aie_policy_evaluate_backward(aie_env* env, int64_t B, const float* d_logits_
                                  const float* d_gentropy_a, const float* d_gentropy_p, float* d_grad_logits_a,
                                  float* d_grad_logits_p, void* stream);
 
+/* Generalised advantage estimation straight from a reward log: advantages and returns of T steps for every (replica, actor)
+ * column, one launch -- what PPO with use_gae does between a rollout and its update (the reference's training configurations:
+ * gamma 0.998, lambda 0.98, fragments of 200 steps), where torch takes ~6 elementwise launches per step of the fragment.
+ *   d_log      float32 [n_slots][E][n + 2] in aie_set_reward_log's layout (agents' rewards, the planner's reward, done as
+ *              0/1); it need not be the log currently installed.  Time t (0 <= t < T <= n_slots) lives in ring slot
+ *              (first_slot + t) % n_slots;
+ *   d_values_a float32 [T + 1][E][n], d_values_p float32 [T + 1][E]: row T is the bootstrap value of the observation behind
+ *              the last step;
+ *   d_adv_* / d_ret_*: the values' shapes with T rows.
+ * float32, every product and sum rounded on its own (no fma), a fixed order (csrc/aie_layout.h states it once; the CPU test
+ * compiles the same helper): with gl = gamma * lambda rounded once and done_t = log[t][e][n + 1] > 0.5,
+ *   delta_t = done_t ? r_t - V_t : (r_t + gamma V_{t+1}) - V_t,   A_t = done_t ? delta_t : delta_t + gl A_{t+1}  (A_T = 0),
+ *   ret_t = A_t + V_t
+ * -- the bits of the plain serial float32 loop; the recurrence is not re-associated across time.  A done step SELECTS (it
+ * does not multiply by zero): under auto-reset V_{t+1} and A_{t+1} behind an episode's end belong to the restarted episode
+ * and do not enter the arithmetic, so a NaN or an infinity there does not leak.
+ * Either actor class may be NULL (values and outputs), either d_ret_* may be NULL, and d_adv_* may be NULL when its d_ret_*
+ * is not; a class with no output is left out.  All scenarios (E and n are the environment's).  One launch, asynchronous on
+ * `stream`, no synchronisation, capturable.  AIE_E_INVALID for T < 1, T > n_slots, first_slot outside the ring, a NULL log
+ * or an output without its values. */
+int aie_gae(aie_env* env, int32_t T, const float* d_log, int32_t n_slots, int32_t first_slot, const float* d_values_a,
+            const float* d_values_p, float gamma, float lambda, float* d_adv_a, float* d_adv_p, float* d_ret_a, float* d_ret_p,
+            void* stream);
+
+/* Trajectory storage with the slot index on the device: one launch per step copies up to AIE_TRAJ_MAX_SEGMENTS per-replica
+ * blocks (observations, masks, actions, log-probabilities, values -- any device memory, arena tensors included) into
+ * replica e's slot d_slot[e] of the caller's ring buffers, then d_slot[e] becomes (d_slot[e] + 1) % n_slots.
+ *   d_slot  caller-owned int32 [n_envs] in device memory, zeroed by the caller (a value outside the ring counts as 0).
+ * Nothing that changes from step to step travels by value: a launch captured in a hipGraph walks the ring on replay, like
+ * the reward log's slot and the samplers' draw index.  Exactly one workgroup reads and advances replica e's counter, after
+ * all of its threads have read it.  Copies use 16-byte lane accesses where a segment's source, destination, stride and size
+ * allow it for every replica and slot, else 4-byte ones; plain vector loads and stores.  One launch, asynchronous on
+ * `stream`, no synchronisation.  AIE_E_INVALID for n_segs outside 1 .. AIE_TRAJ_MAX_SEGMENTS, sizes or strides that are not
+ * multiples of 4, rows that do not divide the element count, n_slots < 1, NULL or misaligned pointers. */
+#define AIE_TRAJ_MAX_SEGMENTS 16
+typedef struct aie_traj_segment {
+  const void* src;     /* replica e's block starts at src + e * src_stride                                  */
+  void* dst;           /* slot s, replica e: dst + ((int64_t)s * n_envs + e) * bytes                          */
+  int64_t src_stride;  /* bytes, a multiple of 4 (an arena tensor's replica stride, or the record stride)     */
+  int32_t bytes;       /* per replica, a multiple of 4                                                        */
+  int32_t rows;        /* 0 or 1: plain copy.  > 1: the block is [rows][bytes / 4 / rows] 4-byte elements and  */
+                       /* is stored transposed (COVID's collated agent masks -> the logits' layout)           */
+} aie_traj_segment;
+int aie_trajectory_store(aie_env* env, const aie_traj_segment* segs, int32_t n_segs, int32_t n_slots, int32_t* d_slot,
+                         void* stream);
+
 /* Same counter RNG, but each sub-action is drawn uniformly among the entries that the
  * CURRENT action masks allow (obs_a_action_mask / obs_p_action_mask; NO-OP is always
  * allowed).  This is the random policy a trainer starts from when it applies the
