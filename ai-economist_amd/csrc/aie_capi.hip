@@ -43,6 +43,9 @@ static bool aie_jit_eligible(const aie_env* env);
 static int aie_jit_request(aie_env* env);
 
 #define AIE_DEV_API __attribute__((visibility("default")))
+// dev_skip_mask bit that is no phase of the kernel: "run the full-featured kernel, not the traced instance" (set by
+// aie_dev_set_draw_window).  It had been 1 << 20, which now switches the in-place flat vectors off.
+#define AIE_DEV_GENERIC_KERNEL (1 << 30)
 
 #define AIE_HIP_CHECK(env, expr)                                                          \
   do {                                                                                    \
@@ -369,6 +372,16 @@ static int copy_tensor(aie_env* env, const char* name, void* host, int64_t bytes
 
 int aie_upload(aie_env* env, const char* name, const void* host, int64_t bytes) {
   const int rc = copy_tensor(env, name, const_cast<void*>(host), bytes, true);
+  if (rc == AIE_OK && env->P.o_obs_valid && strcmp(name, "obs_valid") != 0) {
+    // A record field written from outside the kernels: the observation tensors no longer show every replica's state, and
+    // the next step rewrites maps, masks and flat vectors in full (obs_valid, aie_layout.h) -- one strided fill over
+    // the records, on the stream of the copy above.
+    const aie_tensor_desc* d = find_tensor(env, name);
+    const int64_t r0 = env->P.a_records, r1 = r0 + (int64_t)env->P.E * env->P.rec_bytes;
+    if (d->arena_offset >= r0 && d->arena_offset < r1)
+      AIE_HIP_CHECK(env, hipMemset2DAsync(env->arena + r0 + env->P.o_obs_valid, (size_t)env->P.rec_bytes, 0, 4,
+                                          (size_t)env->P.E, nullptr));
+  }
   if (rc == AIE_OK && (strcmp(name, "cells") == 0 || strcmp(name, "cell_flags") == 0))
     return aie_rebuild_src_lists(env);  // the regeneration's source doubles follow the flags (o_src_list)
   if (rc == AIE_OK && env->P.c.scenario == AIE_SCN_COVID && strcmp(name, "model_unemp_conv_filters") == 0) {
@@ -710,7 +723,7 @@ static int aie_step_impl(aie_env* env, const int32_t* d_actions_a, const int32_t
     hipLaunchKernelGGL(aie_ose_step_kernel, dim3((unsigned)env->P.E), dim3(OSE_NT), env->lds,
                        static_cast<hipStream_t>(stream), env->d_params, env->arena, d_actions_a, d_actions_p, next);
 #ifdef AIE_DEV
-  else if (env->spec >= 0 && !(env->P.dev_skip_mask & (1 << 20)) && (env->P.dev_trace != nullptr || env->P.dev_skip_mask != 0)) {
+  else if (env->spec >= 0 && !(env->P.dev_skip_mask & AIE_DEV_GENERIC_KERNEL) && (env->P.dev_trace != nullptr || env->P.dev_skip_mask != 0)) {
     const dim3 g((unsigned)env->P.E), b(2 * AIE_NT);
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define AIE_SPEC_LAUNCH_TR(K) \
@@ -1288,7 +1301,7 @@ AIE_DEV_API int aie_dev_set_lds_pad(aie_env* env, int bytes) {
 AIE_DEV_API int aie_dev_set_draw_window(aie_env* env, int words) {
   if (!env || words < 0) return AIE_E_INVALID;
   env->P.dev_draw_window = words;
-  env->P.dev_skip_mask = words ? (env->P.dev_skip_mask | (1 << 20)) : (env->P.dev_skip_mask & ~(1 << 20));
+  env->P.dev_skip_mask = words ? (env->P.dev_skip_mask | AIE_DEV_GENERIC_KERNEL) : (env->P.dev_skip_mask & ~AIE_DEV_GENERIC_KERNEL);
   return aie_dev_push_params(env);
 }
 

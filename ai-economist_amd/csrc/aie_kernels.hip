@@ -926,7 +926,20 @@ struct Agents {
   int no0, no1;          // open orders per commodity (CDA n_orders)
   uint32_t act;          // bit 0 build | gather << 1 (3 bits) | buy0 << 4 | sell0 << 11 | buy1 << 18 | sell1 << 25
   double coin, esc_coin, labor;
+  // What the step's components did to the slow-moving entries of the flat observation vectors (wave-uniform; zeroed by
+  // step_body, read by update_flat_observations -- the record has no such field):
+  uint64_t hist_dirty;   // order-count histogram columns that changed (hist_bit)
+  bool tax_dirty;        // PeriodicBracketTax latched new rates or enacted taxes in this step
 };
+// Bit of Agents::hist_dirty for a change of cda_ask_hist (side 0) / cda_bid_hist (side 1) of commodity r at `price`: one
+// bit per (commodity, side, price) while those fit one 64-bit word (P <= 16; 44 bits with the default 11 price levels),
+// one per (commodity, side) beyond.  hist_col_dirty: the test for one column.
+__device__ __forceinline__ uint64_t hist_bit(const aie_params& P, int r, int side, int price) {
+  return 4 * P.P <= 64 ? 1ull << ((2 * r + side) * P.P + price) : 1ull << (2 * r + side);
+}
+__device__ __forceinline__ bool hist_col_dirty(const aie_params& P, uint64_t dirty, int r, int side, int price) {
+  return ((dirty >> (4 * P.P <= 64 ? (2 * r + side) * P.P + price : 2 * r + side)) & 1ull) != 0;
+}
 #define AIE_ACT_BUILD(a) ((a) & 1u)
 #define AIE_ACT_GATHER(a) (((a) >> 1) & 7u)
 #define AIE_ACT_BUY(a, r) (((a) >> (4 + 14 * (r))) & 0x7fu)
@@ -1383,6 +1396,7 @@ __device__ __forceinline__ void cda_component_step(const Ctx& c, Agents& A) {
           bids[nb[r]] = AIE_ORD_PACK(i, price, 0);
           nb[r] += 1;
           hist_add(bid_hist, (r * n + i) * P + price, lane);
+          A.hist_dirty |= hist_bit(c.P, r, 1, price);
           if (lane == i) {
             if (r) A.no1 += 1; else A.no0 += 1;
             const double tr = A.coin < (double)price ? A.coin : (double)price;  // base_agent.py:279-299
@@ -1399,6 +1413,7 @@ __device__ __forceinline__ void cda_component_step(const Ctx& c, Agents& A) {
           asks[na[r]] = AIE_ORD_PACK(i, price, 0);
           na[r] += 1;
           hist_add(ask_hist, (r * n + i) * P + price, lane);
+          A.hist_dirty |= hist_bit(c.P, r, 0, price);
           if (lane == i) {
             if (r) { A.no1 += 1; A.inv1 -= 1; A.esc1 += 1; }
             else { A.no0 += 1; A.inv0 -= 1; A.esc0 += 1; }
@@ -1469,6 +1484,7 @@ __device__ __forceinline__ void cda_component_step(const Ctx& c, Agents& A) {
         const bool at_ask = AIE_ORD_LIFE(bid) <= AIE_ORD_LIFE(ask);  // :297-304
         const int price = at_ask ? aprice : bprice;
         if (lane == ntrades) trade = buyer | (seller << 6) | (bprice << 12) | (aprice << 20) | ((int)at_ask << 28);
+        A.hist_dirty |= hist_bit(c.P, r, 1, bprice) | hist_bit(c.P, r, 0, aprice);  // (the decrements behind the loop)
         ntrades += 1;
         if (c.ev) log_event(c, AIE_EV_TRADE, r, seller, buyer, aprice, bprice, price, AIE_ORD_LIFE(ask), AIE_ORD_LIFE(bid), 0.0);
         if (lane == seller) {
@@ -1530,6 +1546,7 @@ __device__ __forceinline__ void cda_component_step(const Ctx& c, Agents& A) {
       const int price = (AIE_ORD_LIFE(bid) <= AIE_ORD_LIFE(ask)) ? aprice : bprice;  // :297-304
       bid_hist[(r * n + buyer) * P + bprice] -= 1;
       ask_hist[(r * n + seller) * P + aprice] -= 1;
+      A.hist_dirty |= hist_bit(c.P, r, 1, bprice) | hist_bit(c.P, r, 0, aprice);
       R_F64(c, o_cda_price_history)[(r * n + seller) * P + price] += 1.0;
       if (lane == 0 && C_MET(c)) {  // get_metrics :585-641: fire-and-forget integer atomics
         int32_t* tm = reinterpret_cast<int32_t*>(C_MET(c) + c.P.mo_cda);
@@ -1582,6 +1599,7 @@ __device__ __forceinline__ void cda_component_step(const Ctx& c, Agents& A) {
           em &= em - 1;
           const int32_t eo = bcast(o, q);
           const int ag = AIE_ORD_AGENT(eo), pr = AIE_ORD_PRICE(eo);
+          A.hist_dirty |= hist_bit(c.P, r, side == 0 ? 1 : 0, pr);  // (hist_sub_lane above)
           if (lane == ag) {
             if (side == 0) {
               const double tr = A.esc_coin < (double)pr ? A.esc_coin : (double)pr;  // escrow_to_inventory
@@ -1620,6 +1638,7 @@ __device__ __forceinline__ void cda_component_step(const Ctx& c, Agents& A) {
           em &= em - 1;
           const int32_t eo = bcast(o, q);
           const int ag = AIE_ORD_AGENT(eo), pr = AIE_ORD_PRICE(eo);
+          A.hist_dirty |= hist_bit(c.P, r, side == 0 ? 1 : 0, pr);
           if (side == 0) {
             bid_hist[(r * n + ag) * P + pr] -= 1;
             if (lane == ag) {
@@ -1808,6 +1827,9 @@ __device__ __forceinline__ void tax_enact(const Ctx& c, Agents& A) {
 // component_step :945-972 + set_new_period_rates_model :419-434
 __device__ __forceinline__ void tax_component_step(const Ctx& c, MTL& ml, Agents& A) {
   int pos = uni(*R_I32(c, o_tax_cycle_pos));
+  // the flat vectors' tax block follows the latched rates (Saez, the model wrapper: pos == 1) and what tax_enact leaves
+  A.tax_dirty |= (pos == 1 && (c.saez || (c.P.c.tax_model == AIE_TAX_MODEL_WRAPPER && !c.P.c.tax_disable))) ||
+                 pos >= c.R.c.tax_period;
   if (pos == 1 && c.saez) {  // compute_and_set_new_period_rates_from_saez_formula
     uint8_t* blk = saez_block(c);
     if (uni(reinterpret_cast<const int32_t*>(blk)[1])) {  // the formula ran in aie_saez_kernel just before this launch
@@ -2584,6 +2606,125 @@ __device__ __forceinline__ void write_flat_observations(const Ctx& c, uint8_t* _
   }
 }
 
+// Incremental form of write_flat_observations (what update_spatial_observations is to the maps): the tensors still hold
+// the previous step's vectors, and a whole step changes few of their entries -- on BASELINE configs[1] about 10 of an
+// agent's 136 floats.  Written on every step, untracked: time, the world scalars, the current marginal rate, the tax
+// calendar (first day, tax day, phase), and a price-history column / a market rate whose sum is nonzero (a zero sum
+// means no trade since the reset, whose full rewrite stored the zeros; 0.995^t never reaches zero from above before
+// its float32 image has).  Written when the CDA component touched them (Agents::hist_dirty): the order-count columns
+// -- one lane per (commodity, price) rewrites the 2n + 1 entries per side that show its column.  Never: build payment,
+// skill, gather bonus, the planner's inventory (resets only).  The tax block's slow entries (rates, sorted incomes, the
+// planner's per-agent last income / last marginal rate) change on two steps of a tax period: step_body sends those
+// steps down the full path instead (Agents::tax_dirty), as it does with everything that obs_valid == 0 stands for.
+// No LDS staging: every entry goes straight to the tensors.
+__device__ __forceinline__ void update_flat_observations(const Ctx& c, uint8_t* __restrict__ arena, uint64_t hist_dirty) {
+  const aie_params& P = c.P;
+  const int n = P.n, tid = c.tid, Pp = P.P, NB = P.NB;
+  const double isc = P.c.allow_observation_scaling ? 0.01 : 1.0;
+  const BufRsrc aflat = make_rsrc(arena + c.R.a_obs_a_flat + (int64_t)c.e * n * P.FA * 4, (uint32_t)(n * P.FA * 4));
+  auto AF = [&](int idx, float v) { buf_store_f32(aflat, v, 4 * idx, 0); };
+  float* const pflat = reinterpret_cast<float*>(arena + c.R.a_obs_p_flat) + (int64_t)c.e * P.FP;
+  float* const pag = reinterpret_cast<float*>(arena + c.R.a_obs_p_agents) + (int64_t)c.e * n * P.FPA;
+  const int t = *R_I32(c, o_timestep);
+  const float tval = (float)((double)t / (P.c.allow_observation_scaling ? (double)c.R.c.episode_length : 1.0));
+  const int skip = c.skipm;
+  if (P.has_cda && !(skip & 64)) {
+    // lanes over (commodity r, price k): the column's net price history; its order counts where they changed
+    double* net_ph = scr_net_ph(c);
+    for (int q = tid; q < 2 * Pp; q += AIE_NT) {
+      const int r = q >= Pp ? 1 : 0, k = q - r * Pp;
+      double s = 0;
+      for (int i = 0; i < n; ++i) {
+        const double v = R_F64(c, o_cda_price_history)[(r * n + i) * Pp + k];
+        s = (i == 0) ? v : s + v;  // (write_flat_observations' order)
+      }
+      net_ph[q] = s;
+      if (s != 0 && !(skip & 128)) {
+        const float v = (float)(s * isc);
+        pflat[P.fp_cda + 4 * Pp + 2 + q] = v;
+        for (int i = 0; i < n; ++i) AF(i * P.FA + P.fa_cda + 8 * Pp + 2 + q, v);
+      }
+#pragma unroll
+      for (int side = 0; side < 2; ++side) {  // 0: asks, 1: bids
+        if (!hist_col_dirty(P, hist_dirty, r, side, k) || (skip & 128)) continue;
+        const uint8_t* h = side ? R_U8(c, o_cda_bid_hist) : R_U8(c, o_cda_ask_hist);
+        int f = 0;
+        for (int i = 0; i < n; ++i) f += h[(r * n + i) * Pp + k];
+        const float full = (float)f;
+        pflat[P.fp_cda + 2 * side * Pp + q] = full;  // full_asks / full_bids
+        for (int i = 0; i < n; ++i) {
+          const float my = (float)h[(r * n + i) * Pp + k];
+          const int fc = i * P.FA + P.fa_cda;
+          AF(fc + 2 * side * Pp + q, full - my);          // available_asks / available_bids
+          AF(fc + (4 + 2 * side) * Pp + 2 + q, my);       // my_asks / my_bids
+        }
+      }
+    }
+  }
+  if (tid < n && !(skip & 64)) {
+    const int i = tid;
+    const int f0 = i * P.FA;
+    const double coin = R_F64(c, o_inv_coin)[i];
+    const int inv0 = R_I32(c, o_inv_res)[i], inv1 = R_I32(c, o_inv_res)[n + i];
+    const int lr = R_I32(c, o_loc_r)[i], lc = R_I32(c, o_loc_c)[i];
+    AF(f0 + P.fa_time, tval);
+    const float w0 = (float)(coin * isc);
+    const float w1 = (float)((double)inv0 * isc);
+    const float w2 = (float)((double)inv1 * isc);
+    const float w3 = (float)((double)lc / (double)P.W);
+    const float w4 = (float)((double)lr / (double)P.H);
+    AF(f0 + P.fa_world + 0, w0); AF(f0 + P.fa_world + 1, w1); AF(f0 + P.fa_world + 2, w2);
+    float* q = pag + i * P.FPA;
+    if (!P.c.full_observability) {
+      AF(f0 + P.fa_world + 3, w3); AF(f0 + P.fa_world + 4, w4);
+      q[P.fpa_world + 0] = w0; q[P.fpa_world + 1] = w1; q[P.fpa_world + 2] = w2;
+      if (P.c.planner_gets_spatial_info) { q[P.fpa_world + 3] = w3; q[P.fpa_world + 4] = w4; }
+    }
+    reinterpret_cast<float*>(arena + c.R.a_obs_a_time)[(int64_t)c.e * n + i] = tval;
+    if (P.has_tax) {
+      const double cmr = tax_marginal_rate(c, (coin + R_F64(c, o_esc_coin)[i]) - R_F64(c, o_tax_last_coin)[i]);
+      AF(f0 + P.fa_tax + NB + 2 + n, (float)cmr);
+      q[P.fpa_tax + 0] = (float)cmr;
+    }
+  }
+  if (tid == 0) {
+    pflat[P.fp_time] = tval;
+    reinterpret_cast<float*>(arena + c.R.a_obs_p_time)[c.e] = tval;
+  }
+  if (P.has_tax && !(skip & 256)) {  // the calendar entries of the n agents' and the planner's tax block
+    const int pos = *R_I32(c, o_tax_cycle_pos);
+    const float is_tax_day = pos >= c.R.c.tax_period ? 1.0f : 0.0f;
+    const float is_first_day = pos == 1 ? 1.0f : 0.0f;
+    const float tax_phase = (float)((double)pos / (double)c.R.c.tax_period);
+    for (int i = tid; i <= n; i += AIE_NT) {
+      if (i == n) {
+        pflat[P.fp_tax + NB] = is_first_day;
+        pflat[P.fp_tax + NB + 1] = is_tax_day;
+        pflat[P.fp_tax + NB + 2 + n] = tax_phase;
+      } else {
+        AF(i * P.FA + P.fa_tax + NB, is_first_day);
+        AF(i * P.FA + P.fa_tax + NB + 1, is_tax_day);
+        AF(i * P.FA + P.fa_tax + NB + 3 + n, tax_phase);
+      }
+    }
+  }
+  if (P.has_cda && !(skip & 128)) {
+    AIE_WSYNC();  // (net_ph)
+    if (tid < 2) {  // the market rates, continuous_double_auction.py:491-542
+      const int r = tid;
+      const double* a = scr_net_ph(c) + r * Pp;
+      double dot = 0;
+      for (int k = 0; k < Pp; ++k) dot += (double)k * a[k];
+      const double tot = np_sum_small(a, Pp);
+      if (tot != 0) {
+        const float mr = (float)(dot / (tot > 0.001 ? tot : 0.001));
+        pflat[P.fp_cda + 4 * Pp + r] = mr;
+        for (int i = 0; i < n; ++i) AF(i * P.FA + P.fa_cda + 4 * Pp + r, mr);
+      }
+    }
+  }
+}
+
 
 // Action masks (own staging slots, own per-agent mask bits): independent of the flat vectors
 // above, so the second wave of a replica builds them while the first one does those.
@@ -2888,6 +3029,8 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
   if (wid == 0) {
     // ---------------- first wave: actions, components, flat vectors, rewards ----------------
     Agents A;
+    A.hist_dirty = 0;
+    A.tax_dirty = false;
     int act_err = 0;
     if (!(skip & (1 << 18))) act_err = decode_actions(c, A, act_a, act_p, arena);  // (c.act_p is LDS scratch)
     else A.act = 0;
@@ -2910,6 +3053,14 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
       if (ml.avail > covered) ml.avail = covered;
     }
     agents_load(c, A);
+    // The flat vectors are updated in place (update_flat_observations) on a whole step whose tensors still show the
+    // previous step -- the rule of the map observations and the masks.  obs_valid is read HERE, while the image is
+    // fresh: the second wave rewrites the field in its tail, which runs beside this wave's.
+#ifdef AIE_FLAT_FULL  // (A/B builds: every step rewrites the vectors in full, as before round 7)
+    const bool flat_in_place = false;
+#else
+    const bool flat_in_place = ph == 0 && uni(*R_I32(c, o_obs_valid)) != 0 && !(skip & (1 << 20));
+#endif
     if (act_err && c.tid == 0) *R_I32(c, o_error_flags) |= act_err;
     bool cda_in_range = ph == 0;  // (the decay opens ContinuousDoubleAuction.component_step: with the component)
     if (ph != 0)
@@ -2951,7 +3102,14 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
       if (c.tid < P.n) R_F64(c, o_tax_last_coin)[c.tid] = R_F64(c, o_inv_coin)[c.tid] + R_F64(c, o_esc_coin)[c.tid];
       AIE_WSYNC();
     }
-    if (!(skip & 8) && (EMIT || OBSERVE)) write_flat_observations(c, arena);
+    if (!(skip & 8) && (EMIT || OBSERVE)) {
+      // An annealed tax schedule caps the rates by the completions count the reset latches BEHIND its own observations
+      // (reset_body: o_tax_last_completions, generate_masks' order): the episode's first step shows new curr_rates
+      // although no tax day has passed.
+      const bool annealed_first = P.has_tax && P.c.tax_annealing && uni(*R_I32(c, o_timestep)) == 1;
+      if (flat_in_place && !A.tax_dirty && !annealed_first) update_flat_observations(c, arena, A.hist_dirty);
+      else write_flat_observations(c, arena);
+    }
     if (TRACE && R.dev_trace && c.tid == 0) R.dev_trace[12 * blockIdx.x + 10] = wall_clock64();
     if (!REW_ON_W1 && (EMIT || CLOSE)) step_rewards_and_done(c, arena, next, skip, EMIT, CLOSE);
     if (REBASE) {  // (reset_body's last lines: the metrics of the state as the host's reset hooks left it)

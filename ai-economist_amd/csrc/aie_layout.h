@@ -116,9 +116,10 @@ typedef struct aie_params {
                           * step -- straight into the registers of the wave that regenerates, while the components run -- instead
                           * of a scan of the flags.  Behind the generator's state, i.e. outside the record's LDS image.  Absent
                           * (0) where the batch shares one list (a_src_list). */
-  int32_t o_obs_valid;   /* 1: the map observation tensors hold this replica's current state (the step
-                          * kernel then only rewrites what a step changes); cleared by anything that
-                          * edits state from outside the kernels                                     */
+  int32_t o_obs_valid;   /* 1: the observation tensors -- maps, action masks and (round 7) the flat vectors --
+                          * hold this replica's current state (a whole step then only rewrites what it
+                          * changes); cleared by anything that edits state from outside the kernels:
+                          * aie_upload of a record field, Backend.invalidate_observations             */
 
   /* arena: byte offsets of the dense regions */
   int64_t a_records;

@@ -537,8 +537,9 @@ class DeviceBackend:
         return arr
 
     def invalidate_observations(self, e=None):
-        """Call after editing state tensors from outside the kernels: the next step rewrites the
-        map observations in full instead of updating them in place (`obs_valid`)."""
+        """Call after editing state tensors (or overwriting observation tensors) from outside the kernels: the next
+        step rewrites the map observations, the action masks and the flat vectors of replica(s) `e` in full instead of
+        updating them in place (`obs_valid`).  `upload` of a record field does it for every replica."""
         if "obs_valid" in self.tensors:
             if e is None:
                 self.tensors["obs_valid"].zero_()

@@ -396,7 +396,12 @@ int aie_get_tensor(const aie_env* env, const char* name, aie_tensor_desc* out);
  * Synchronous; meant for initial state injection and parity dumps.  The COVID tables "model_stringency_level_history_0"
  * and "model_unemp_conv_filters" have to be written through aie_upload (not through a view of the arena): the library
  * derives data from them at that point (the history-format image and the pre-episode change events every reset copies;
- * whether the taps are float32 values, which selects the tap-table format of the window-sum kernel). */
+ * whether the taps are float32 values, which selects the tap-table format of the window-sum kernel).
+ * Between steps the observation tensors belong to the kernels: aie_step updates maps, masks and flat vectors IN PLACE,
+ * writing only what the step changed, while the record field obs_valid is 1.  aie_upload of any record field other
+ * than obs_valid clears obs_valid for every replica (the next step rewrites all observations in full); code that edits
+ * state through a view of the arena clears it itself (per replica), and so does code that overwrote an observation
+ * tensor and wants it back. */
 int aie_upload(aie_env* env, const char* name, const void* host, int64_t bytes);
 int aie_download(aie_env* env, const char* name, void* host, int64_t bytes);
 
@@ -470,7 +475,8 @@ int aie_step_sample_next_masked(aie_env* env, const int32_t* d_actions_a, const 
  * EMIT | CLOSE in one call is TAIL without regeneration.  They exclude TAIL and OBSERVE; CLOSE takes no component range and
  * goes with REGEN or HEAD only when EMIT is set too; EMIT and CLOSE take an empty range unless REGEN rides along.
  * obs_valid: a call that changes state without EMIT clears it (the EMIT that follows rewrites maps and masks in full), EMIT
- * sets it, a CLOSE-only call leaves it alone.
+ * sets it, a CLOSE-only call leaves it alone.  The flat vectors are rewritten in full by EVERY aie_step_range call that
+ * writes them; only a whole aie_step with obs_valid == 1 updates them (and the maps and masks) in place.
  * (phases == 0: components only, a stretch in the middle of a step.)
  * One step = any sequence of calls whose first carries HEAD, whose last carries TAIL (or CLOSE) and whose ranges tile the list;
  * aie_step(a, p) == aie_step_range(a, p, 0, n_components, HEAD | TAIL).  Every call takes the same action buffers.
