@@ -2448,6 +2448,76 @@ __device__ __forceinline__ void update_spatial_observations(const Ctx& c, uint8_
   else update_spatial_observations_t<false>(c, arena);
 }
 
+// ---- the parts of the flat vectors that write_flat_observations and update_flat_observations both write; the planner's
+// vector and its per-agent fragments arrive as pointers (LDS staging in the former, the tensors in the latter) ----
+__device__ __forceinline__ void flat_a(const BufRsrc& aflat, int idx, float v) { buf_store_f32(aflat, v, 4 * idx, 0); }
+
+__device__ __forceinline__ float flat_time_value(const Ctx& c) {
+  const int t = *R_I32(c, o_timestep);
+  return (float)((double)t / (c.P.c.allow_observation_scaling ? (double)c.R.c.episode_length : 1.0));
+}
+
+// Agent i's block: what the record holds behind time / world-* and the marginal rate, loaded ahead of the caller's own
+// stores; q = the planner's p{i}.
+struct AgentScalars {
+  double coin; int inv0, inv1, lr, lc;
+  __device__ __forceinline__ AgentScalars(const Ctx& c, int i)
+      : coin(R_F64(c, o_inv_coin)[i]), inv0(R_I32(c, o_inv_res)[i]), inv1(R_I32(c, o_inv_res)[c.P.n + i]),
+        lr(R_I32(c, o_loc_r)[i]), lc(R_I32(c, o_loc_c)[i]) {}
+  // time and world-* of the agent's vector, their copy in p{i}, obs_a_time
+  __device__ __forceinline__ void write(const Ctx& c, uint8_t* __restrict__ arena, const BufRsrc& aflat, float* q, int i,
+                                        float tval, double isc) const {
+    const aie_params& P = c.P;
+    const int f0 = i * P.FA;
+    flat_a(aflat, f0 + P.fa_time, tval);
+    const float w0 = (float)(coin * isc);
+    const float w1 = (float)((double)inv0 * isc);
+    const float w2 = (float)((double)inv1 * isc);
+    const float w3 = (float)((double)lc / (double)P.W);
+    const float w4 = (float)((double)lr / (double)P.H);
+    flat_a(aflat, f0 + P.fa_world + 0, w0); flat_a(aflat, f0 + P.fa_world + 1, w1); flat_a(aflat, f0 + P.fa_world + 2, w2);
+    if (!P.c.full_observability) {  // locations and the planner's per-agent fragments: egocentric mode only
+      flat_a(aflat, f0 + P.fa_world + 3, w3); flat_a(aflat, f0 + P.fa_world + 4, w4);
+      q[P.fpa_world + 0] = w0; q[P.fpa_world + 1] = w1; q[P.fpa_world + 2] = w2;
+      if (P.c.planner_gets_spatial_info) { q[P.fpa_world + 3] = w3; q[P.fpa_world + 4] = w4; }
+    }
+    reinterpret_cast<float*>(arena + c.R.a_obs_a_time)[(int64_t)c.e * P.n + i] = tval;
+  }
+  // the current marginal rate: the agent's own vector and p{i}
+  __device__ __forceinline__ void write_marginal_rate(const Ctx& c, const BufRsrc& aflat, float* q, int i) const {
+    const double cmr = tax_marginal_rate(c, (coin + R_F64(c, o_esc_coin)[i]) - R_F64(c, o_tax_last_coin)[i]);
+    flat_a(aflat, i * c.P.FA + c.P.fa_tax + AIE_FA_TAX_MARGINAL_RATE(c.P.NB, c.P.n), (float)cmr);
+    q[c.P.fpa_tax + AIE_FPA_TAX_CURR_MARGINAL_RATE] = (float)cmr;
+  }
+};
+// Net price history of column (commodity r, price k): np.sum(np.stack(...), axis=0) adds row by row, from the first
+// row's value and not from 0.  row(at) runs on every agent's entry `at` of the [2][n][P] record tables along the way.
+template <class Row>
+__device__ __forceinline__ double price_history_column(const Ctx& c, int r, int k, Row row) {
+  double s = 0;
+  for (int i = 0; i < c.P.n; ++i) {
+    const int at = (r * c.P.n + i) * c.P.P + k;
+    const double v = R_F64(c, o_cda_price_history)[at];
+    s = (i == 0) ? v : s + v;
+    row(at);
+  }
+  return s;
+}
+// market_rate of commodity r from the column sums in scr_net_ph (continuous_double_auction.py:491-542); tot = their sum
+__device__ __forceinline__ float cda_market_rate(const Ctx& c, int r, double& tot) {
+  const double* a = scr_net_ph(c) + r * c.P.P;
+  double dot = 0;
+  for (int k = 0; k < c.P.P; ++k) dot += (double)k * a[k];
+  tot = np_sum_small(a, c.P.P);
+  return (float)(dot / (tot > 0.001 ? tot : 0.001));
+}
+// the tax calendar (redistribution.py:974-1023)
+struct TaxCalendar { float is_tax_day, is_first_day, tax_phase; };
+__device__ __forceinline__ TaxCalendar tax_calendar(const Ctx& c) {
+  const int pos = *R_I32(c, o_tax_cycle_pos);
+  return {pos >= c.R.c.tax_period ? 1.0f : 0.0f, pos == 1 ? 1.0f : 0.0f, (float)((double)pos / (double)c.R.c.tax_period)};
+}
+
 // Component + scalar observations, packed in SORTED key order (base_env.py:561-612):
 // Build (build.py:163-178), CDA (continuous_double_auction.py:491-542), Gather
 // (move.py:155-165), PeriodicBracketTax (redistribution.py:974-1023), time, world-*.
@@ -2462,9 +2532,8 @@ __device__ __forceinline__ void write_flat_observations(const Ctx& c, uint8_t* _
   float* s_pag = c.stage + stage_window_words(P);
   float* s_pflat = s_pag + pad4(n * P.FPA);
   const BufRsrc aflat = make_rsrc(arena + c.R.a_obs_a_flat + (int64_t)c.e * n * P.FA * 4, (uint32_t)(n * P.FA * 4));
-  auto AF = [&](int idx, float v) { buf_store_f32(aflat, v, 4 * idx, 0); };
-  const int t = *R_I32(c, o_timestep);
-  const float tval = (float)((double)t / (P.c.allow_observation_scaling ? (double)c.R.c.episode_length : 1.0));
+  auto AF = [&](int idx, float v) { flat_a(aflat, idx, v); };
+  const float tval = flat_time_value(c);
 
   const int skip = c.skipm;
   // ================= stage A: per-(commodity, price) sums, per-agent scalars ===========
@@ -2473,46 +2542,27 @@ __device__ __forceinline__ void write_flat_observations(const Ctx& c, uint8_t* _
     double* net_ph = scr_net_ph(c);
     for (int q = tid; q < 2 * Pp; q += AIE_NT) {
       const int r = q >= Pp ? 1 : 0, k = q - r * Pp;
-      double s = 0;
       int fa = 0, fb = 0;
-      for (int i = 0; i < n; ++i) {
-        const double v = R_F64(c, o_cda_price_history)[(r * n + i) * Pp + k];
-        s = (i == 0) ? v : s + v;  // np.sum(np.stack(...), axis=0): row by row
-        fa += R_U8(c, o_cda_ask_hist)[(r * n + i) * Pp + k];
-        fb += R_U8(c, o_cda_bid_hist)[(r * n + i) * Pp + k];
-      }
+      const double s = price_history_column(
+          c, r, k, [&](int at) { fa += R_U8(c, o_cda_ask_hist)[at], fb += R_U8(c, o_cda_bid_hist)[at]; });
       net_ph[q] = s;
-      float* g = s_pflat + P.fp_cda;  // planner: full_asks, full_bids, price_history
-      g[0 * Pp + q] = (float)fa;
-      g[2 * Pp + q] = (float)fb;
-      g[4 * Pp + 2 + q] = (float)(s * isc);
+      float* g = s_pflat + P.fp_cda;
+      g[AIE_FP_CDA_FULL_ASKS(Pp) + q] = (float)fa;
+      g[AIE_FP_CDA_FULL_BIDS(Pp) + q] = (float)fb;
+      g[AIE_FP_CDA_PRICE_HISTORY(Pp) + q] = (float)(s * isc);
     }
   }
   if (tid < n && !(skip & 64)) {
     const int i = tid;
     const int f0 = i * P.FA;
-    const double coin = R_F64(c, o_inv_coin)[i];
-    const int inv0 = R_I32(c, o_inv_res)[i], inv1 = R_I32(c, o_inv_res)[n + i];
-    const int lr = R_I32(c, o_loc_r)[i], lc = R_I32(c, o_loc_c)[i];
+    const AgentScalars a(c, i);
     if (P.has_build) {  // build.py:163-178
       AF(f0 + P.fa_build + 0, (float)(R_F64(c, o_build_payment)[i] / (double)c.R.c.build_payment));
       AF(f0 + P.fa_build + 1, (float)R_F64(c, o_build_skill)[i]);
     }
     if (P.has_gather) AF(f0 + P.fa_gather, (float)R_F64(c, o_bonus_gather_prob)[i]);  // move.py:155-165
-    AF(f0 + P.fa_time, tval);
-    const float w0 = (float)(coin * isc);
-    const float w1 = (float)((double)inv0 * isc);
-    const float w2 = (float)((double)inv1 * isc);
-    const float w3 = (float)((double)lc / (double)P.W);
-    const float w4 = (float)((double)lr / (double)P.H);
-    AF(f0 + P.fa_world + 0, w0); AF(f0 + P.fa_world + 1, w1); AF(f0 + P.fa_world + 2, w2);
     float* q = s_pag + i * P.FPA;
-    if (!P.c.full_observability) {  // locations and the planner's per-agent fragments: egocentric mode only
-      AF(f0 + P.fa_world + 3, w3); AF(f0 + P.fa_world + 4, w4);
-      q[P.fpa_world + 0] = w0; q[P.fpa_world + 1] = w1; q[P.fpa_world + 2] = w2;
-      if (P.c.planner_gets_spatial_info) { q[P.fpa_world + 3] = w3; q[P.fpa_world + 4] = w4; }
-    }
-    reinterpret_cast<float*>(arena + c.R.a_obs_a_time)[(int64_t)c.e * n + i] = tval;
+    a.write(c, arena, aflat, q, i, tval, isc);
     if (P.has_tax) {
       // last_incomes sorted ascending (redistribution.py:908-911): rank by counting
       const double per = (double)c.R.c.tax_period;
@@ -2526,11 +2576,9 @@ __device__ __forceinline__ void write_flat_observations(const Ctx& c, uint8_t* _
         rank += (y < x || (y == x && j < i)) ? 1 : 0;
       }
       scr_sorted_inc(c)[rank] = x;
-      const double cmr = tax_marginal_rate(c, (coin + R_F64(c, o_esc_coin)[i]) - R_F64(c, o_tax_last_coin)[i]);
-      AF(f0 + P.fa_tax + NB + 2 + n, (float)cmr);
-      q[P.fpa_tax + 0] = (float)cmr;
-      q[P.fpa_tax + 1] = (float)x;
-      q[P.fpa_tax + 2] = (float)R_F64(c, o_tax_last_marginal_rate)[i];
+      a.write_marginal_rate(c, aflat, q, i);
+      q[P.fpa_tax + AIE_FPA_TAX_LAST_INCOME] = (float)x;
+      q[P.fpa_tax + AIE_FPA_TAX_LAST_MARGINAL_RATE] = (float)R_F64(c, o_tax_last_marginal_rate)[i];
     }
   }
   if (tid == 0) {
@@ -2547,13 +2595,10 @@ __device__ __forceinline__ void write_flat_observations(const Ctx& c, uint8_t* _
     // continuous_double_auction.py:491-542
     if (tid < 2) {
       const int r = tid;
-      const double* a = scr_net_ph(c) + r * Pp;
-      double dot = 0;
-      for (int k = 0; k < Pp; ++k) dot += (double)k * a[k];
-      const double tot = np_sum_small(a, Pp);
-      const float mr = (float)(dot / (tot > 0.001 ? tot : 0.001));
-      s_pflat[P.fp_cda + 4 * Pp + r] = mr;
-      for (int i = 0; i < n; ++i) AF(i * P.FA + P.fa_cda + 4 * Pp + r, mr);
+      double tot;
+      const float mr = cda_market_rate(c, r, tot);
+      s_pflat[P.fp_cda + AIE_FP_CDA_MARKET_RATE(Pp) + r] = mr;
+      for (int i = 0; i < n; ++i) AF(i * P.FA + P.fa_cda + AIE_FA_CDA_MARKET_RATE(Pp) + r, mr);
     }
     const float* g = s_pflat + P.fp_cda;
     for (int it = tid; it < n * 2 * Pp; it += AIE_NT) {
@@ -2563,36 +2608,33 @@ __device__ __forceinline__ void write_flat_observations(const Ctx& c, uint8_t* _
       const float mya = (float)R_U8(c, o_cda_ask_hist)[(r * n + i) * Pp + k];
       const float myb = (float)R_U8(c, o_cda_bid_hist)[(r * n + i) * Pp + k];
       const int fc = i * P.FA + P.fa_cda;
-      AF(fc + 0 * Pp + q, g[0 * Pp + q] - mya);    // available_asks
-      AF(fc + 2 * Pp + q, g[2 * Pp + q] - myb);    // available_bids
-      AF(fc + 4 * Pp + 2 + q, mya);                // my_asks
-      AF(fc + 6 * Pp + 2 + q, myb);                // my_bids
-      AF(fc + 8 * Pp + 2 + q, g[4 * Pp + 2 + q]);  // price_history
+      AF(fc + AIE_FA_CDA_AVAILABLE_ASKS(Pp) + q, g[AIE_FP_CDA_FULL_ASKS(Pp) + q] - mya);
+      AF(fc + AIE_FA_CDA_AVAILABLE_BIDS(Pp) + q, g[AIE_FP_CDA_FULL_BIDS(Pp) + q] - myb);
+      AF(fc + AIE_FA_CDA_MY_ASKS(Pp) + q, mya);
+      AF(fc + AIE_FA_CDA_MY_BIDS(Pp) + q, myb);
+      AF(fc + AIE_FA_CDA_PRICE_HISTORY(Pp) + q, g[AIE_FP_CDA_PRICE_HISTORY(Pp) + q]);
     }
   }
   if (P.has_tax && !(skip & 256)) {
     // redistribution.py:974-1023; lanes over (agent or planner, element of the fragment)
-    const int pos = *R_I32(c, o_tax_cycle_pos);
-    const float is_tax_day = pos >= c.R.c.tax_period ? 1.0f : 0.0f;
-    const float is_first_day = pos == 1 ? 1.0f : 0.0f;
-    const float tax_phase = (float)((double)pos / (double)c.R.c.tax_period);
-    const int fragA = NB + n + 4;
+    const TaxCalendar cal = tax_calendar(c);
+    const int fragA = AIE_FA_TAX_LEN(NB, n);
     for (int q = tid; q < (n + 1) * fragA; q += AIE_NT) {
       const int i = udiv(q, fragA, P.mg_taxA);
       const int j = q - i * fragA;
       const bool planner = i == n;
-      if (j == NB + 2 + n) {  // marginal_rate: written in stage A (agents), absent for the planner
-        if (planner) s_pflat[P.fp_tax + NB + 2 + n] = tax_phase;
+      if (j == AIE_FA_TAX_MARGINAL_RATE(NB, n)) {  // written in stage A (agents), absent for the planner
+        if (planner) s_pflat[P.fp_tax + AIE_FP_TAX_PHASE(NB, n)] = cal.tax_phase;
         continue;
       }
-      if (planner && j == NB + 3 + n) continue;
+      if (planner && j == AIE_FA_TAX_PHASE(NB, n)) continue;
       float v;
-      if (j < NB) v = (float)tax_rate_obs(c, j);
-      else if (j == NB) v = is_first_day;
-      else if (j == NB + 1) v = is_tax_day;
-      else if (j < NB + 2 + n) v = (float)scr_sorted_inc(c)[j - NB - 2];
-      else v = tax_phase;
-      if (planner) s_pflat[P.fp_tax + j] = v;
+      if (j < AIE_F_TAX_IS_FIRST_DAY(NB)) v = (float)tax_rate_obs(c, j - AIE_F_TAX_CURR_RATES);
+      else if (j == AIE_F_TAX_IS_FIRST_DAY(NB)) v = cal.is_first_day;
+      else if (j == AIE_F_TAX_IS_TAX_DAY(NB)) v = cal.is_tax_day;
+      else if (j < AIE_FA_TAX_MARGINAL_RATE(NB, n)) v = (float)scr_sorted_inc(c)[j - AIE_F_TAX_LAST_INCOMES(NB)];
+      else v = cal.tax_phase;
+      if (planner) s_pflat[P.fp_tax + j] = v;  // (AIE_F_TAX_*: the same place in both blocks)
       else AF(i * P.FA + P.fa_tax + j, v);
     }
   }
@@ -2622,27 +2664,22 @@ __device__ __forceinline__ void update_flat_observations(const Ctx& c, uint8_t* 
   const int n = P.n, tid = c.tid, Pp = P.P, NB = P.NB;
   const double isc = P.c.allow_observation_scaling ? 0.01 : 1.0;
   const BufRsrc aflat = make_rsrc(arena + c.R.a_obs_a_flat + (int64_t)c.e * n * P.FA * 4, (uint32_t)(n * P.FA * 4));
-  auto AF = [&](int idx, float v) { buf_store_f32(aflat, v, 4 * idx, 0); };
+  auto AF = [&](int idx, float v) { flat_a(aflat, idx, v); };
   float* const pflat = reinterpret_cast<float*>(arena + c.R.a_obs_p_flat) + (int64_t)c.e * P.FP;
   float* const pag = reinterpret_cast<float*>(arena + c.R.a_obs_p_agents) + (int64_t)c.e * n * P.FPA;
-  const int t = *R_I32(c, o_timestep);
-  const float tval = (float)((double)t / (P.c.allow_observation_scaling ? (double)c.R.c.episode_length : 1.0));
+  const float tval = flat_time_value(c);
   const int skip = c.skipm;
   if (P.has_cda && !(skip & 64)) {
     // lanes over (commodity r, price k): the column's net price history; its order counts where they changed
     double* net_ph = scr_net_ph(c);
     for (int q = tid; q < 2 * Pp; q += AIE_NT) {
       const int r = q >= Pp ? 1 : 0, k = q - r * Pp;
-      double s = 0;
-      for (int i = 0; i < n; ++i) {
-        const double v = R_F64(c, o_cda_price_history)[(r * n + i) * Pp + k];
-        s = (i == 0) ? v : s + v;  // (write_flat_observations' order)
-      }
+      const double s = price_history_column(c, r, k, [](int) {});
       net_ph[q] = s;
       if (s != 0 && !(skip & 128)) {
         const float v = (float)(s * isc);
-        pflat[P.fp_cda + 4 * Pp + 2 + q] = v;
-        for (int i = 0; i < n; ++i) AF(i * P.FA + P.fa_cda + 8 * Pp + 2 + q, v);
+        pflat[P.fp_cda + AIE_FP_CDA_PRICE_HISTORY(Pp) + q] = v;
+        for (int i = 0; i < n; ++i) AF(i * P.FA + P.fa_cda + AIE_FA_CDA_PRICE_HISTORY(Pp) + q, v);
       }
 #pragma unroll
       for (int side = 0; side < 2; ++side) {  // 0: asks, 1: bids
@@ -2651,75 +2688,50 @@ __device__ __forceinline__ void update_flat_observations(const Ctx& c, uint8_t* 
         int f = 0;
         for (int i = 0; i < n; ++i) f += h[(r * n + i) * Pp + k];
         const float full = (float)f;
-        pflat[P.fp_cda + 2 * side * Pp + q] = full;  // full_asks / full_bids
+        pflat[P.fp_cda + (side ? AIE_FP_CDA_FULL_BIDS(Pp) : AIE_FP_CDA_FULL_ASKS(Pp)) + q] = full;
         for (int i = 0; i < n; ++i) {
           const float my = (float)h[(r * n + i) * Pp + k];
           const int fc = i * P.FA + P.fa_cda;
-          AF(fc + 2 * side * Pp + q, full - my);          // available_asks / available_bids
-          AF(fc + (4 + 2 * side) * Pp + 2 + q, my);       // my_asks / my_bids
+          AF(fc + (side ? AIE_FA_CDA_AVAILABLE_BIDS(Pp) : AIE_FA_CDA_AVAILABLE_ASKS(Pp)) + q, full - my);
+          AF(fc + (side ? AIE_FA_CDA_MY_BIDS(Pp) : AIE_FA_CDA_MY_ASKS(Pp)) + q, my);
         }
       }
     }
   }
   if (tid < n && !(skip & 64)) {
     const int i = tid;
-    const int f0 = i * P.FA;
-    const double coin = R_F64(c, o_inv_coin)[i];
-    const int inv0 = R_I32(c, o_inv_res)[i], inv1 = R_I32(c, o_inv_res)[n + i];
-    const int lr = R_I32(c, o_loc_r)[i], lc = R_I32(c, o_loc_c)[i];
-    AF(f0 + P.fa_time, tval);
-    const float w0 = (float)(coin * isc);
-    const float w1 = (float)((double)inv0 * isc);
-    const float w2 = (float)((double)inv1 * isc);
-    const float w3 = (float)((double)lc / (double)P.W);
-    const float w4 = (float)((double)lr / (double)P.H);
-    AF(f0 + P.fa_world + 0, w0); AF(f0 + P.fa_world + 1, w1); AF(f0 + P.fa_world + 2, w2);
+    const AgentScalars a(c, i);
     float* q = pag + i * P.FPA;
-    if (!P.c.full_observability) {
-      AF(f0 + P.fa_world + 3, w3); AF(f0 + P.fa_world + 4, w4);
-      q[P.fpa_world + 0] = w0; q[P.fpa_world + 1] = w1; q[P.fpa_world + 2] = w2;
-      if (P.c.planner_gets_spatial_info) { q[P.fpa_world + 3] = w3; q[P.fpa_world + 4] = w4; }
-    }
-    reinterpret_cast<float*>(arena + c.R.a_obs_a_time)[(int64_t)c.e * n + i] = tval;
-    if (P.has_tax) {
-      const double cmr = tax_marginal_rate(c, (coin + R_F64(c, o_esc_coin)[i]) - R_F64(c, o_tax_last_coin)[i]);
-      AF(f0 + P.fa_tax + NB + 2 + n, (float)cmr);
-      q[P.fpa_tax + 0] = (float)cmr;
-    }
+    a.write(c, arena, aflat, q, i, tval, isc);
+    if (P.has_tax) a.write_marginal_rate(c, aflat, q, i);
   }
   if (tid == 0) {
     pflat[P.fp_time] = tval;
     reinterpret_cast<float*>(arena + c.R.a_obs_p_time)[c.e] = tval;
   }
   if (P.has_tax && !(skip & 256)) {  // the calendar entries of the n agents' and the planner's tax block
-    const int pos = *R_I32(c, o_tax_cycle_pos);
-    const float is_tax_day = pos >= c.R.c.tax_period ? 1.0f : 0.0f;
-    const float is_first_day = pos == 1 ? 1.0f : 0.0f;
-    const float tax_phase = (float)((double)pos / (double)c.R.c.tax_period);
+    const TaxCalendar cal = tax_calendar(c);
     for (int i = tid; i <= n; i += AIE_NT) {
       if (i == n) {
-        pflat[P.fp_tax + NB] = is_first_day;
-        pflat[P.fp_tax + NB + 1] = is_tax_day;
-        pflat[P.fp_tax + NB + 2 + n] = tax_phase;
+        pflat[P.fp_tax + AIE_F_TAX_IS_FIRST_DAY(NB)] = cal.is_first_day;
+        pflat[P.fp_tax + AIE_F_TAX_IS_TAX_DAY(NB)] = cal.is_tax_day;
+        pflat[P.fp_tax + AIE_FP_TAX_PHASE(NB, n)] = cal.tax_phase;
       } else {
-        AF(i * P.FA + P.fa_tax + NB, is_first_day);
-        AF(i * P.FA + P.fa_tax + NB + 1, is_tax_day);
-        AF(i * P.FA + P.fa_tax + NB + 3 + n, tax_phase);
+        AF(i * P.FA + P.fa_tax + AIE_F_TAX_IS_FIRST_DAY(NB), cal.is_first_day);
+        AF(i * P.FA + P.fa_tax + AIE_F_TAX_IS_TAX_DAY(NB), cal.is_tax_day);
+        AF(i * P.FA + P.fa_tax + AIE_FA_TAX_PHASE(NB, n), cal.tax_phase);
       }
     }
   }
   if (P.has_cda && !(skip & 128)) {
     AIE_WSYNC();  // (net_ph)
-    if (tid < 2) {  // the market rates, continuous_double_auction.py:491-542
+    if (tid < 2) {
       const int r = tid;
-      const double* a = scr_net_ph(c) + r * Pp;
-      double dot = 0;
-      for (int k = 0; k < Pp; ++k) dot += (double)k * a[k];
-      const double tot = np_sum_small(a, Pp);
+      double tot;
+      const float mr = cda_market_rate(c, r, tot);
       if (tot != 0) {
-        const float mr = (float)(dot / (tot > 0.001 ? tot : 0.001));
-        pflat[P.fp_cda + 4 * Pp + r] = mr;
-        for (int i = 0; i < n; ++i) AF(i * P.FA + P.fa_cda + 4 * Pp + r, mr);
+        pflat[P.fp_cda + AIE_FP_CDA_MARKET_RATE(Pp) + r] = mr;
+        for (int i = 0; i < n; ++i) AF(i * P.FA + P.fa_cda + AIE_FA_CDA_MARKET_RATE(Pp) + r, mr);
       }
     }
   }

@@ -579,16 +579,16 @@ __device__ __forceinline__ void ose_write_observations(const Ctx& c, const OseSc
     rank_sort(s.tmp, s.sorted, n, tid);
     __syncthreads();
     const int pos = *R_I32(c, o_tax_cycle_pos);
-    for (int j = tid; j < NB + n + 4; j += OSE_NT) {
+    for (int j = tid; j < AIE_FA_TAX_LEN(NB, n); j += OSE_NT) {  // lanes over the agents' block
       float v;
-      if (j < NB) v = (float)tax_rate_obs(c, j);
-      else if (j == NB) v = pos == 1 ? 1.0f : 0.0f;               // is_first_day
-      else if (j == NB + 1) v = pos >= c.P.c.tax_period ? 1.0f : 0.0f;  // is_tax_day
-      else if (j < NB + 2 + n) v = (float)s.sorted[j - NB - 2];   // last_incomes (sorted)
+      if (j < AIE_F_TAX_IS_FIRST_DAY(NB)) v = (float)tax_rate_obs(c, j - AIE_F_TAX_CURR_RATES);
+      else if (j == AIE_F_TAX_IS_FIRST_DAY(NB)) v = pos == 1 ? 1.0f : 0.0f;
+      else if (j == AIE_F_TAX_IS_TAX_DAY(NB)) v = pos >= c.P.c.tax_period ? 1.0f : 0.0f;
+      else if (j < AIE_FA_TAX_MARGINAL_RATE(NB, n)) v = (float)s.sorted[j - AIE_F_TAX_LAST_INCOMES(NB)];
       else v = (float)((double)pos / per);                        // tax_phase
-      if (j != NB + 2 + n) s.tmpl_a[P.fa_tax + j] = v;            // [NB+2+n] = marginal_rate: per agent
-      if (j < NB + 2 + n) s.tmpl_p[P.fp_tax + j] = v;
-      else if (j == NB + 3 + n) s.tmpl_p[P.fp_tax + NB + 2 + n] = v;
+      if (j != AIE_FA_TAX_MARGINAL_RATE(NB, n)) s.tmpl_a[P.fa_tax + j] = v;  // (marginal_rate: per agent)
+      if (j < AIE_FA_TAX_MARGINAL_RATE(NB, n)) s.tmpl_p[P.fp_tax + j] = v;   // (AIE_F_TAX_*: the same place in both blocks)
+      else if (j == AIE_FA_TAX_PHASE(NB, n)) s.tmpl_p[P.fp_tax + AIE_FP_TAX_PHASE(NB, n)] = v;
     }
   }
   OSE_MY_AGENTS(k, i, n) {
@@ -616,7 +616,7 @@ __device__ __forceinline__ void ose_write_observations(const Ctx& c, const OseSc
   // ---- agent flat vectors: the shared template with two per-agent entries ----
   {
     const BufRsrc g = make_rsrc(arena + c.R.a_obs_a_flat + (int64_t)c.e * n * P.FA * 4, (uint32_t)(n * P.FA * 4));
-    const int i_mr = P.has_tax ? P.fa_tax + NB + 2 + n : -1;
+    const int i_mr = P.has_tax ? P.fa_tax + AIE_FA_TAX_MARGINAL_RATE(NB, n) : -1;
     const int i_sk = P.has_labor ? P.fa_labor : -1;
     if (i_sk >= 0) {  // SimpleLabor-skill = skill / pmsm: n divisions, one lane per agent (s.part is free until the rewards)
       OSE_MY_AGENTS(k, i, n) s.part[i] = (double)L.skobs(k);  // (float)(skill / pmsm), simple_labor.py:128-134
@@ -628,9 +628,10 @@ __device__ __forceinline__ void ose_write_observations(const Ctx& c, const OseSc
     if (P.FPA && !OSE_SKIP(c, 8)) {
       float* gp = reinterpret_cast<float*>(arena + c.R.a_obs_p_agents) + (int64_t)c.e * n * P.FPA;
       for (int i = tid; i < n; i += OSE_NT) {
-        gp[i * 3 + 0] = (float)s.tmp[i];
-        gp[i * 3 + 1] = (float)(R_F64(c, o_tax_last_income)[i] / (double)c.P.c.tax_period);
-        gp[i * 3 + 2] = (float)R_F64(c, o_tax_last_marginal_rate)[i];
+        float* q = gp + i * P.FPA + P.fpa_tax;
+        q[AIE_FPA_TAX_CURR_MARGINAL_RATE] = (float)s.tmp[i];
+        q[AIE_FPA_TAX_LAST_INCOME] = (float)(R_F64(c, o_tax_last_income)[i] / (double)c.P.c.tax_period);
+        q[AIE_FPA_TAX_LAST_MARGINAL_RATE] = (float)R_F64(c, o_tax_last_marginal_rate)[i];
       }
     }
     if (!OSE_SKIP(c, 8)) stream_out(s.tmpl_p, reinterpret_cast<float*>(arena + c.R.a_obs_p_flat) + (int64_t)c.e * P.FP, P.FP, tid);

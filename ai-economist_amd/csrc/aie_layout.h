@@ -344,6 +344,39 @@ static inline void aie_spec_normalize(aie_params* p) {
 #undef AIE__BLANK
 }
 
+/* ---- inside a component's block of the flat observation vectors ----
+ * Where each of the block's sorted keys starts, in f32 elements from the block's own offset (aie_params: fa_cda,
+ * fp_tax, fpa_tax, ...), and how long the block is; P = price levels, NB = tax brackets, n = agents.  The kernels and
+ * the oracle address the entries through these names only (foundation/obs_keys.py derives the same layout from the
+ * reference's keys and is pinned against it).
+ * ContinuousDoubleAuction (continuous_double_auction.py:491-542): a key holds (commodity r, price k) at r * P + k,
+ * market_rate one entry per commodity. */
+#define AIE_FA_CDA_AVAILABLE_ASKS(P) 0
+#define AIE_FA_CDA_AVAILABLE_BIDS(P) (2 * (P))
+#define AIE_FA_CDA_MARKET_RATE(P) (4 * (P))
+#define AIE_FA_CDA_MY_ASKS(P) (4 * (P) + 2)
+#define AIE_FA_CDA_MY_BIDS(P) (6 * (P) + 2)
+#define AIE_FA_CDA_PRICE_HISTORY(P) (8 * (P) + 2)
+#define AIE_FA_CDA_LEN(P) (10 * (P) + 2)
+#define AIE_FP_CDA_FULL_ASKS(P) 0
+#define AIE_FP_CDA_FULL_BIDS(P) (2 * (P))
+#define AIE_FP_CDA_MARKET_RATE(P) (4 * (P))
+#define AIE_FP_CDA_PRICE_HISTORY(P) (4 * (P) + 2)
+#define AIE_FP_CDA_LEN(P) (6 * (P) + 2)
+/* PeriodicBracketTax (redistribution.py:974-1023): the planner's block is the agents' without marginal_rate, so the
+ * keys ahead of it (AIE_F_TAX_*) sit at the same place in both */
+#define AIE_F_TAX_CURR_RATES 0
+#define AIE_F_TAX_IS_FIRST_DAY(NB) (NB)
+#define AIE_F_TAX_IS_TAX_DAY(NB) ((NB) + 1)
+#define AIE_F_TAX_LAST_INCOMES(NB) ((NB) + 2)     /* n entries, ascending */
+#define AIE_FA_TAX_MARGINAL_RATE(NB, n) ((NB) + 2 + (n))
+#define AIE_FA_TAX_PHASE(NB, n) ((NB) + 3 + (n))
+#define AIE_FA_TAX_LEN(NB, n) ((NB) + (n) + 4)
+#define AIE_FP_TAX_PHASE(NB, n) ((NB) + 2 + (n))
+#define AIE_FP_TAX_LEN(NB, n) ((NB) + (n) + 3)
+/* ... and its fragment of the planner's per-agent vector p{i} */
+enum { AIE_FPA_TAX_CURR_MARGINAL_RATE = 0, AIE_FPA_TAX_LAST_INCOME = 1, AIE_FPA_TAX_LAST_MARGINAL_RATE = 2, AIE_FPA_TAX_LEN = 3 };
+
 typedef struct aie_tensor_table {
   int32_t n;
   aie_tensor_desc t[AIE_MAX_TENSORS];
@@ -785,19 +818,19 @@ static inline void aie__add_metrics_tensors(const aie_params* p, aie_tensor_tabl
 static inline int aie__build_one_step_economy(const aie_config* c, aie_params* p, aie_tensor_table* tt) {
   const int n = p->n;
   int f = 0;
-  p->fa_tax = f;   if (p->has_tax) f += p->NB + n + 4;
+  p->fa_tax = f;   if (p->has_tax) f += AIE_FA_TAX_LEN(p->NB, n);
   p->fa_labor = f; if (p->has_labor) f += 1;
   p->fa_time = f;  f += 1;
   p->fa_world = f;
   p->FA = f;
   f = 0;
-  p->fp_tax = f;   if (p->has_tax) f += p->NB + n + 3;
+  p->fp_tax = f;   if (p->has_tax) f += AIE_FP_TAX_LEN(p->NB, n);
   p->fp_time = f;  f += 1;
   p->fp_world = f; f += 2;
   p->FP = f;
   p->fpa_tax = 0;
-  p->fpa_world = p->has_tax ? 3 : 0;
-  p->FPA = p->has_tax ? 3 : 0;
+  p->fpa_world = p->has_tax ? AIE_FPA_TAX_LEN : 0;
+  p->FPA = p->has_tax ? AIE_FPA_TAX_LEN : 0;
   p->mg_FA = aie__magic(p->FA);
   p->mg_MA = aie__magic(p->MA);
 
@@ -1187,22 +1220,22 @@ static inline int aie_build_params(const aie_config* c, aie_params* p, aie_tenso
   {
     int f = 0;
     p->fa_build = f;  if (p->has_build) f += 2;
-    p->fa_cda = f;    if (p->has_cda) f += 10 * p->P + 2;
+    p->fa_cda = f;    if (p->has_cda) f += AIE_FA_CDA_LEN(p->P);
     p->fa_gather = f; if (p->has_gather) f += 1;
-    p->fa_tax = f;    if (p->has_tax) f += p->NB + p->n + 4;
+    p->fa_tax = f;    if (p->has_tax) f += AIE_FA_TAX_LEN(p->NB, p->n);
     p->fa_time = f;   f += 1;
     /* inventory-Coin,-Stone,-Wood, loc-col, loc-row; with full_observability the location is
      * only conveyed through the maps (layout_from_file.py:466-472) */
     p->fa_world = f;  f += c->full_observability ? 3 : 5;
     p->FA = f;
     f = 0;
-    p->fp_cda = f;    if (p->has_cda) f += 6 * p->P + 2;
-    p->fp_tax = f;    if (p->has_tax) f += p->NB + p->n + 3;
+    p->fp_cda = f;    if (p->has_cda) f += AIE_FP_CDA_LEN(p->P);
+    p->fp_tax = f;    if (p->has_tax) f += AIE_FP_TAX_LEN(p->NB, p->n);
     p->fp_time = f;   f += 1;
     p->fp_world = f;  f += 3;
     p->FP = f;
     f = 0;
-    p->fpa_tax = f;   if (p->has_tax) f += 3;
+    p->fpa_tax = f;   if (p->has_tax) f += AIE_FPA_TAX_LEN;
     /* the scenario's per-agent planner fragments only exist with egocentric observations (:508-515) */
     p->fpa_world = f; if (!c->full_observability) f += 3 + (c->planner_gets_spatial_info ? 2 : 0);
     p->FPA = f;
@@ -1214,7 +1247,7 @@ static inline int aie_build_params(const aie_config* c, aie_params* p, aie_tenso
   p->mg_FA = aie__magic(p->FA);
   p->mg_P = aie__magic(p->P);
   p->mg_2P = aie__magic(2 * p->P);
-  p->mg_taxA = aie__magic(p->NB + p->n + 4);
+  p->mg_taxA = aie__magic(AIE_FA_TAX_LEN(p->NB, p->n));
   p->mg_HW = aie__magic(p->HW);
   p->mg_W = aie__magic(p->W);
   p->mg_sub_p = aie__magic(1 + p->sub_p_dim);

@@ -974,6 +974,40 @@ static void current_metrics(ctx_t* c, double* out /* n+1 */) {
 /* ------------------------------------------------------------------------------- */
 static double inv_scale(const aie_params* p) { return p->c.allow_observation_scaling ? 0.01 : 1.0; }
 
+/* PeriodicBracketTax observations (redistribution.py:974-1023): what every agent's and the planner's block shows */
+typedef struct { double is_tax_day, is_first_day, tax_phase, sorted_inc[AIE_MAX_AGENTS_WIDE]; } tax_obs_t;
+static void tax_obs_shared(ctx_t* c, tax_obs_t* t) {
+  const aie_params* p = c->p;
+  if (!p->has_tax) return;
+  const int n = p->n, pos = *I32(c, o_tax_cycle_pos);
+  t->is_tax_day = pos >= p->c.tax_period ? 1.0 : 0.0;
+  t->is_first_day = pos == 1 ? 1.0 : 0.0;
+  t->tax_phase = (double)pos / (double)p->c.tax_period;
+  double* sorted_inc = t->sorted_inc;
+  for (int i = 0; i < n; ++i) sorted_inc[i] = F64(c, o_tax_last_income)[i] / (double)p->c.tax_period;
+  for (int i = 1; i < n; ++i) {
+    double x = sorted_inc[i]; int j = i - 1;
+    while (j >= 0 && sorted_inc[j] > x) { sorted_inc[j + 1] = sorted_inc[j]; --j; }
+    sorted_inc[j + 1] = x;
+  }
+}
+/* the tax block g of an agent with the marginal rate *cmr, or (cmr == NULL) of the planner */
+static void tax_obs_block(ctx_t* c, const tax_obs_t* t, float* g, const double* cmr) {
+  const int NB = c->p->NB, n = c->p->n;
+  for (int b = 0; b < NB; ++b) g[AIE_F_TAX_CURR_RATES + b] = (float)tax_rate_obs(c, b);
+  g[AIE_F_TAX_IS_FIRST_DAY(NB)] = (float)t->is_first_day;
+  g[AIE_F_TAX_IS_TAX_DAY(NB)] = (float)t->is_tax_day;
+  for (int k = 0; k < n; ++k) g[AIE_F_TAX_LAST_INCOMES(NB) + k] = (float)t->sorted_inc[k];
+  if (cmr) g[AIE_FA_TAX_MARGINAL_RATE(NB, n)] = (float)*cmr;
+  g[cmr ? AIE_FA_TAX_PHASE(NB, n) : AIE_FP_TAX_PHASE(NB, n)] = (float)t->tax_phase;
+}
+/* ... and that agent's fragment q of the planner's p{i} */
+static void tax_obs_planner_agent(ctx_t* c, float* q, int i, double cmr) {
+  q[AIE_FPA_TAX_CURR_MARGINAL_RATE] = (float)cmr;
+  q[AIE_FPA_TAX_LAST_INCOME] = (float)(F64(c, o_tax_last_income)[i] / (double)c->p->c.tax_period);
+  q[AIE_FPA_TAX_LAST_MARGINAL_RATE] = (float)F64(c, o_tax_last_marginal_rate)[i];
+}
+
 /* LayoutFromFile.generate_observations :412-517 + component obs + _package */
 static void write_obs(ctx_t* c) {
   const aie_params* p = c->p;
@@ -1067,20 +1101,8 @@ static void write_obs(ctx_t* c) {
       market_rate[r] = dot / (tot > 0.001 ? tot : 0.001);
     }
   }
-  /* ---- tax shared quantities (redistribution.py:974-1023) ---- */
-  double is_tax_day = 0, is_first_day = 0, tax_phase = 0, sorted_inc[AIE_MAX_AGENTS];
-  if (p->has_tax) {
-    int pos = *I32(c, o_tax_cycle_pos);
-    is_tax_day = pos >= p->c.tax_period ? 1.0 : 0.0;
-    is_first_day = pos == 1 ? 1.0 : 0.0;
-    tax_phase = (double)pos / (double)p->c.tax_period;
-    for (int i = 0; i < n; ++i) sorted_inc[i] = F64(c, o_tax_last_income)[i] / (double)p->c.tax_period;
-    for (int i = 1; i < n; ++i) {
-      double x = sorted_inc[i]; int j = i - 1;
-      while (j >= 0 && sorted_inc[j] > x) { sorted_inc[j + 1] = sorted_inc[j]; --j; }
-      sorted_inc[j + 1] = x;
-    }
-  }
+  tax_obs_t tax;
+  tax_obs_shared(c, &tax);
 
   float* aflat = (float*)(c->arena + p->a_obs_a_flat) + (int64_t)e * n * p->FA;
   float* atime = (float*)(c->arena + p->a_obs_a_time) + (int64_t)e * n;
@@ -1098,26 +1120,20 @@ static void write_obs(ctx_t* c) {
         for (int k = 0; k < P; ++k) {
           double mya = U8(c, o_cda_ask_hist)[(r * n + i) * P + k];
           double myb = U8(c, o_cda_bid_hist)[(r * n + i) * P + k];
-          g[0 * P + r * P + k] = (float)(full_asks[r][k] - mya);          /* available_asks */
-          g[2 * P + r * P + k] = (float)(full_bids[r][k] - myb);          /* available_bids */
-          g[4 * P + 2 + r * P + k] = (float)mya;                          /* my_asks        */
-          g[6 * P + 2 + r * P + k] = (float)myb;                          /* my_bids        */
-          g[8 * P + 2 + r * P + k] = (float)(net_ph[r][k] * isc);         /* price_history  */
+          g[AIE_FA_CDA_AVAILABLE_ASKS(P) + r * P + k] = (float)(full_asks[r][k] - mya);
+          g[AIE_FA_CDA_AVAILABLE_BIDS(P) + r * P + k] = (float)(full_bids[r][k] - myb);
+          g[AIE_FA_CDA_MY_ASKS(P) + r * P + k] = (float)mya;
+          g[AIE_FA_CDA_MY_BIDS(P) + r * P + k] = (float)myb;
+          g[AIE_FA_CDA_PRICE_HISTORY(P) + r * P + k] = (float)(net_ph[r][k] * isc);
         }
-      g[4 * P + 0] = (float)market_rate[0];
-      g[4 * P + 1] = (float)market_rate[1];
+      g[AIE_FA_CDA_MARKET_RATE(P) + 0] = (float)market_rate[0];
+      g[AIE_FA_CDA_MARKET_RATE(P) + 1] = (float)market_rate[1];
     }
     if (p->has_gather) f[p->fa_gather] = (float)F64(c, o_bonus_gather_prob)[i]; /* move.py:155-165 */
     double cmr = 0;
     if (p->has_tax) {
-      float* g = f + p->fa_tax;
-      for (int b = 0; b < p->NB; ++b) g[b] = (float)tax_rate_obs(c, b);
-      g[p->NB + 0] = (float)is_first_day;
-      g[p->NB + 1] = (float)is_tax_day;
-      for (int k = 0; k < n; ++k) g[p->NB + 2 + k] = (float)sorted_inc[k];
       cmr = tax_marginal_rate(c, (F64(c, o_inv_coin)[i] + F64(c, o_esc_coin)[i]) - F64(c, o_tax_last_coin)[i]);
-      g[p->NB + 2 + n] = (float)cmr;
-      g[p->NB + 3 + n] = (float)tax_phase;
+      tax_obs_block(c, &tax, f + p->fa_tax, &cmr);
     }
     f[p->fa_time] = (float)tval;
     f[p->fa_world + 0] = (float)(F64(c, o_inv_coin)[i] * isc);
@@ -1130,11 +1146,7 @@ static void write_obs(ctx_t* c) {
     atime[i] = (float)tval;
     /* planner's per-agent view p{i} */
     float* q = pag + i * p->FPA;
-    if (p->has_tax) {
-      q[p->fpa_tax + 0] = (float)cmr;
-      q[p->fpa_tax + 1] = (float)(F64(c, o_tax_last_income)[i] / (double)p->c.tax_period);
-      q[p->fpa_tax + 2] = (float)F64(c, o_tax_last_marginal_rate)[i];
-    }
+    if (p->has_tax) tax_obs_planner_agent(c, q + p->fpa_tax, i, cmr);
     if (!p->c.full_observability) { /* :508-515: only the egocentric branch builds "p<idx>" */
       q[p->fpa_world + 0] = f[p->fa_world + 0];
       q[p->fpa_world + 1] = f[p->fa_world + 1];
@@ -1152,21 +1164,14 @@ static void write_obs(ctx_t* c) {
     const int P = p->P;
     for (int r = 0; r < 2; ++r)
       for (int k = 0; k < P; ++k) {
-        g[0 * P + r * P + k] = (float)full_asks[r][k];
-        g[2 * P + r * P + k] = (float)full_bids[r][k];
-        g[4 * P + 2 + r * P + k] = (float)(net_ph[r][k] * isc);
+        g[AIE_FP_CDA_FULL_ASKS(P) + r * P + k] = (float)full_asks[r][k];
+        g[AIE_FP_CDA_FULL_BIDS(P) + r * P + k] = (float)full_bids[r][k];
+        g[AIE_FP_CDA_PRICE_HISTORY(P) + r * P + k] = (float)(net_ph[r][k] * isc);
       }
-    g[4 * P + 0] = (float)market_rate[0];
-    g[4 * P + 1] = (float)market_rate[1];
+    g[AIE_FP_CDA_MARKET_RATE(P) + 0] = (float)market_rate[0];
+    g[AIE_FP_CDA_MARKET_RATE(P) + 1] = (float)market_rate[1];
   }
-  if (p->has_tax) {
-    float* g = pf + p->fp_tax;
-    for (int b = 0; b < p->NB; ++b) g[b] = (float)tax_rate_obs(c, b);
-    g[p->NB + 0] = (float)is_first_day;
-    g[p->NB + 1] = (float)is_tax_day;
-    for (int k = 0; k < n; ++k) g[p->NB + 2 + k] = (float)sorted_inc[k];
-    g[p->NB + 2 + n] = (float)tax_phase;
-  }
+  if (p->has_tax) tax_obs_block(c, &tax, pf + p->fp_tax, NULL);
   pf[p->fp_time] = (float)tval;
   pf[p->fp_world + 0] = 0.0f; /* the planner's own inventory is always empty */
   pf[p->fp_world + 1] = 0.0f;
@@ -1650,23 +1655,12 @@ static void ose_metrics(ctx_t* c, double* out) {
 
 static void ose_write_obs(ctx_t* c, int at_reset) {
   const aie_params* p = c->p;
-  const int n = p->n, e = c->e, NB = p->NB;
+  const int n = p->n, e = c->e;
   const int t = *I32(c, o_timestep);
   const double time_scale = p->c.allow_observation_scaling ? (double)p->c.episode_length : 1.0;
   const float tval = (float)((double)t / time_scale);
-  double is_tax_day = 0, is_first_day = 0, tax_phase = 0, sorted_inc[AIE_MAX_AGENTS_WIDE];
-  if (p->has_tax) {
-    int pos = *I32(c, o_tax_cycle_pos);
-    is_tax_day = pos >= p->c.tax_period ? 1.0 : 0.0;
-    is_first_day = pos == 1 ? 1.0 : 0.0;
-    tax_phase = (double)pos / (double)p->c.tax_period;
-    for (int i = 0; i < n; ++i) sorted_inc[i] = F64(c, o_tax_last_income)[i] / (double)p->c.tax_period;
-    for (int i = 1; i < n; ++i) {
-      double x = sorted_inc[i]; int j = i - 1;
-      while (j >= 0 && sorted_inc[j] > x) { sorted_inc[j + 1] = sorted_inc[j]; --j; }
-      sorted_inc[j + 1] = x;
-    }
-  }
+  tax_obs_t tax;
+  tax_obs_shared(c, &tax);
   float* aflat = (float*)(c->arena + p->a_obs_a_flat) + (int64_t)e * n * p->FA;
   float* atime = (float*)(c->arena + p->a_obs_a_time) + (int64_t)e * n;
   float* pag = (float*)(c->arena + p->a_obs_p_agents) + (int64_t)e * n * p->FPA;
@@ -1675,32 +1669,16 @@ static void ose_write_obs(ctx_t* c, int at_reset) {
     float* f = aflat + i * p->FA;
     coin[i] = F64(c, o_inv_coin)[i] + F64(c, o_esc_coin)[i];
     if (p->has_tax) {
-      float* g = f + p->fa_tax;
-      for (int b = 0; b < NB; ++b) g[b] = (float)tax_rate_obs(c, b);
-      g[NB + 0] = (float)is_first_day;
-      g[NB + 1] = (float)is_tax_day;
-      for (int k = 0; k < n; ++k) g[NB + 2 + k] = (float)sorted_inc[k];
       double cmr = tax_marginal_rate(c, coin[i] - F64(c, o_tax_last_coin)[i]);
-      g[NB + 2 + n] = (float)cmr;
-      g[NB + 3 + n] = (float)tax_phase;
-      float* q = pag + i * p->FPA;
-      q[0] = (float)cmr;
-      q[1] = (float)(F64(c, o_tax_last_income)[i] / (double)p->c.tax_period);
-      q[2] = (float)F64(c, o_tax_last_marginal_rate)[i];
+      tax_obs_block(c, &tax, f + p->fa_tax, &cmr);
+      tax_obs_planner_agent(c, pag + i * p->FPA + p->fpa_tax, i, cmr);
     }
     if (p->has_labor) f[p->fa_labor] = (float)(F64(c, o_skill)[i] / p->c.labor_pmsm); /* simple_labor.py:128-134 */
     f[p->fa_time] = tval;
     atime[i] = tval;
   }
   float* pf = (float*)(c->arena + p->a_obs_p_flat) + (int64_t)e * p->FP;
-  if (p->has_tax) {
-    float* g = pf + p->fp_tax;
-    for (int b = 0; b < NB; ++b) g[b] = (float)tax_rate_obs(c, b);
-    g[NB + 0] = (float)is_first_day;
-    g[NB + 1] = (float)is_tax_day;
-    for (int k = 0; k < n; ++k) g[NB + 2 + k] = (float)sorted_inc[k];
-    g[NB + 2 + n] = (float)tax_phase;
-  }
+  if (p->has_tax) tax_obs_block(c, &tax, pf + p->fp_tax, NULL);
   pf[p->fp_time] = tval;
   /* one_step_economy.py:161-172: equality, productivity / n / 1000 */
   pf[p->fp_world + 0] = (float)(1 - get_gini_wide(coin, n));
