@@ -251,6 +251,19 @@ def bind(lib):
     return lib
 
 
+def bind_dev(lib):
+    """The development hooks of the -DAIE_DEV build (csrc/aie_capi.hip, not in include/aie.h), on top of bind()."""
+    vp = C.c_void_p
+    for name, args in (("aie_dev_lds_bytes", [vp, vp]), ("aie_dev_set_trace", [vp, vp]), ("aie_dev_set_lds_pad", [vp, C.c_int]),
+                       ("aie_dev_set_draw_window", [vp, C.c_int]), ("aie_dev_set_skip_mask", [vp, C.c_int]),
+                       ("aie_dev_step_route", [vp, C.c_char_p, C.c_int]),
+                       ("aie_test_glibc_math", [C.c_int, vp, vp, vp, C.c_int64, vp])):
+        fn = getattr(lib, name)
+        fn.restype = C.c_int
+        fn.argtypes = args
+    return lib
+
+
 EXPORTED_SYMBOLS = [
     "aie_arena_bytes", "aie_create", "aie_destroy", "aie_last_error", "aie_num_tensors",
     "aie_tensor_at", "aie_get_tensor", "aie_upload", "aie_download", "aie_set_layout",

@@ -25,4 +25,6 @@ def lib(dev=False):
                 "HIP extension {} is not built; run `python -c 'import __graft_entry__ as g; "
                 "g.build()'` (needs hipcc). There is no CPU fallback.".format(path))
         _LIBS[dev] = _cabi.bind(ctypes.CDLL(path))
+        if dev:
+            _cabi.bind_dev(_LIBS[dev])
     return _LIBS[dev]

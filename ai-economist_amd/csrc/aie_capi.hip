@@ -34,6 +34,7 @@ struct aie_env {
   int cv_taps_f32;       // COVID: every uploaded filter tap is a float32 value (aie_upload checks): the window-sum kernel
                          // then keeps its LDS tap table in float32
   int log_active;        // aie_set_dense_log_active: the dense-log replicas record events (default) or run with the rest
+  int dev_generic;       // development (aie_dev_set_draw_window): run the full-featured kernel, whatever instance matches
   char err[512];
 };
 
@@ -43,9 +44,6 @@ static bool aie_jit_eligible(const aie_env* env);
 static int aie_jit_request(aie_env* env);
 
 #define AIE_DEV_API __attribute__((visibility("default")))
-// dev_skip_mask bit that is no phase of the kernel: "run the full-featured kernel, not the traced instance" (set by
-// aie_dev_set_draw_window).  It had been 1 << 20, which now switches the in-place flat vectors off.
-#define AIE_DEV_GENERIC_KERNEL (1 << 30)
 
 #define AIE_HIP_CHECK(env, expr)                                                          \
   do {                                                                                    \
@@ -182,6 +180,204 @@ static inline int aie_workgroups_per_cu(size_t lds) {
   const size_t granules = (lds + 1279) / 1280;
   const size_t fit = granules ? (size_t)128 / granules : 16;
   return (int)(fit < 16 ? fit : 16);
+}
+
+// ---- which kernel a call launches ---------------------------------------------------------------------------------
+// Every gather-trade-build, one-step-economy and COVID step kernel has one signature, and every reset kernel but the
+// one-step-economy's another: a kernel is picked as a pointer (with its name, for aie_dev_step_route) and launched in
+// one place.
+using aie_step_fn = void (*)(const aie_params*, uint8_t*, const int32_t*, const int32_t*, NextActions);
+using aie_reset_fn = void (*)(const aie_params*, uint8_t*, const uint8_t*, int);
+using aie_window_fn = void (*)(const aie_params*, uint8_t*);
+template <typename Fn>
+struct aie_kernel {
+  Fn fn;
+  const char* name;
+};
+#define AIE_KERNEL(...) {__VA_ARGS__, #__VA_ARGS__}
+// One launch.  k.fn == nullptr: `module`, the loaded run-time specialisation's entry point -- or the one-step-economy's
+// reset kernel, which aie_launch_reset names itself.
+template <typename Fn>
+struct aie_route {
+  aie_kernel<Fn> k;
+  bool module;
+  unsigned block;
+  size_t lds;
+};
+
+// the compile-time instances by instance number (aie_spec_generated.h); fn == nullptr: not an instance of that family
+static const struct aie_spec_kernels {
+  aie_kernel<aie_step_fn> step[AIE_N_SPECS], traced[AIE_N_SPECS], ose[AIE_N_SPECS];
+  aie_kernel<aie_reset_fn> reset[AIE_N_SPECS];
+} aie_spec_kernel = [] {
+  aie_spec_kernels t{};
+#define AIE_GTB_ROW(K) t.step[K] = AIE_KERNEL(aie_step_kernel_spec<K>), t.reset[K] = AIE_KERNEL(aie_reset_kernel_spec<K>);
+#define AIE_OSE_ROW(K) t.ose[K] = AIE_KERNEL(aie_ose_step_kernel_spec<K>);
+#define AIE_TRACED_ROW(K) t.traced[K] = AIE_KERNEL(aie_step_kernel_spec_trace<K>);
+  AIE_SPEC_LIST_GTB(AIE_GTB_ROW)
+  AIE_SPEC_LIST_OSE(AIE_OSE_ROW)
+#ifdef AIE_DEV
+  AIE_SPEC_LIST_GTB(AIE_TRACED_ROW)
+#endif
+  return t;
+}();
+// COVID: by the filter count cv_F = 1 .. 8, then by filter_recurrence (step) or by float32-valued taps (window sums)
+#define AIE_CV_TABLE(ROW) {ROW(1), ROW(2), ROW(3), ROW(4), ROW(5), ROW(6), ROW(7), ROW(8)}
+#define AIE_CV_STEP_ROW(F) {AIE_KERNEL(aie_covid_step_kernel<F, false>), AIE_KERNEL(aie_covid_step_kernel<F, true>)}
+#define AIE_CV_WINDOW_ROW(F) {AIE_KERNEL(aie_covid_window_kernel<F, double>), AIE_KERNEL(aie_covid_window_kernel<F, float>)}
+static const aie_kernel<aie_step_fn> aie_cv_step_kernel[AIE_COVID_MAX_FILTERS][2] = AIE_CV_TABLE(AIE_CV_STEP_ROW);
+static const aie_kernel<aie_window_fn> aie_cv_window_kernel[AIE_COVID_MAX_FILTERS][2] = AIE_CV_TABLE(AIE_CV_WINDOW_ROW);
+
+// What aie_step launches for this environment as it stands; the first rule that matches wins (DESIGN.md section 3 has
+// the table).  full: the full-featured kernel whatever the environment runs otherwise (the dense-log replicas while they
+// record, aie_step_range).  AIE_E_UNSUPPORTED / AIE_E_INVALID: there is no such kernel.
+static int aie_select_step(const aie_env* env, bool full, aie_route<aie_step_fn>* out) {
+  const aie_params& P = env->P;
+  const int spec = env->spec;
+  const bool covid = P.c.scenario == AIE_SCN_COVID, ose = P.c.scenario == AIE_SCN_ONE_STEP_ECONOMY;
+  const bool jit = spec == AIE_KERNEL_INSTANCE_JIT, inst = spec >= 0 && spec < AIE_N_SPECS;
+  const bool hooks = P.dev_trace != nullptr || P.dev_skip_mask != 0;  // (development build only)
+  const aie_kernel<aie_step_fn> none = {nullptr, nullptr};
+  aie_kernel<aie_step_fn> k = AIE_KERNEL(aie_step_kernel_log);  // the full-featured kernel
+  if (full) {
+  } else if (covid) {
+    if (P.cv_F < 1 || P.cv_F > AIE_COVID_MAX_FILTERS) return AIE_E_UNSUPPORTED;
+    k = aie_cv_step_kernel[P.cv_F - 1][P.c.covid.filter_recurrence ? 1 : 0];
+  } else if (ose) {
+    if (jit) k = {nullptr, "aie_jit_ose_step"};
+    else if (spec >= 0) k = inst ? aie_spec_kernel.ose[spec] : none;
+    else k = AIE_KERNEL(aie_ose_step_kernel);
+  } else if (inst && hooks && !env->dev_generic) {
+    k = aie_spec_kernel.traced[spec];  // the instance's traced twin honours the hooks (a run-time specialisation has none)
+  } else if (P.saez_stride || P.M > AIE_NT || P.regen_general || hooks || env->dev_generic || P.n_host_a || P.n_host_p) {
+    // (foreign action subspaces: decoded by the full-featured kernel only)
+  } else if (jit) {
+    k = {nullptr, "aie_jit_step"};
+  } else if (spec >= 0) {
+    k = inst ? aie_spec_kernel.step[spec] : none;
+  } else if (aie_workgroups_per_cu(env->lds) <= 12) {
+    k = AIE_KERNEL(aie_step_kernel_r6);
+  } else {
+    k = AIE_KERNEL(aie_step_kernel);
+  }
+  if (!k.name) return AIE_E_INVALID;
+  *out = {k, /*module=*/!k.fn, (unsigned)(covid ? AIE_NT : ose ? OSE_NT : 2 * AIE_NT), env->lds};
+  return AIE_OK;
+}
+
+static int aie_launch_step(aie_env* env, const aie_route<aie_step_fn>& r, unsigned grid, const int32_t* d_actions_a,
+                           const int32_t* d_actions_p, const NextActions& next, hipStream_t st) {
+  if (r.module) {
+    const aie_params* dp = env->d_params;
+    uint8_t* ar = env->arena;
+    NextActions nx = next;
+    void* args[] = {&dp, &ar, &d_actions_a, &d_actions_p, &nx};
+    AIE_HIP_CHECK(env, hipModuleLaunchKernel(env->jit_step, grid, 1, 1, r.block, 1, 1, (unsigned)r.lds, st, args, nullptr));
+  } else {
+    hipLaunchKernelGGL(r.k.fn, dim3(grid), dim3(r.block), r.lds, st, env->d_params, env->arena, d_actions_a, d_actions_p, next);
+  }
+  return AIE_OK;
+}
+
+// The dense-log replicas [0, L) record their episode (they then take the full-featured kernel, a launch of their own):
+// that launch's grid, or 0.  It covers the workgroups that map to the logged replicas and as little else as possible
+// (the others leave at once): replica_of_block is the identity when E is not a multiple of 8, else replica e < E / 8 is
+// workgroup 8 e.
+static unsigned aie_log_grid(const aie_env* env) {
+  if (env->P.c.scenario != AIE_SCN_GTB || env->P.ev_replicas <= 0 || !env->log_active) return 0;
+  const int64_t L = env->P.ev_replicas, E8 = env->P.E >> 3;
+  return (env->P.E & 7) ? (unsigned)L : (L <= E8 ? (unsigned)(8 * (L - 1) + 1) : (unsigned)env->P.E);
+}
+
+// What aie_reset (and an auto-reset) launches.
+static aie_route<aie_reset_fn> aie_select_reset(const aie_env* env) {
+  const aie_params& P = env->P;
+  if (P.c.scenario == AIE_SCN_COVID) return {AIE_KERNEL(aie_covid_reset_kernel), false, AIE_NT, 0};
+  if (P.c.scenario == AIE_SCN_ONE_STEP_ECONOMY) return {{nullptr, "aie_ose_reset_kernel"}, false, OSE_NT, env->lds};
+  // LG_NW wavefronts per replica when the reset draws a new source layout (aie_kernels.hip: layout_generate), else one
+  const bool layout = P.c.layout_gen != AIE_LAYOUT_FIXED;
+  aie_route<aie_reset_fn> r = {AIE_KERNEL(aie_reset_kernel), false, AIE_NT, env->lds + aie::layout_gen_lds_bytes(P)};
+  if (layout) r.k = AIE_KERNEL(aie_reset_kernel_layout), r.block = LG_NW * AIE_NT;
+  if (P.dev_skip_mask == 0 && !env->dev_generic) {  // (the specialised resets have no development hooks)
+    if (env->spec == AIE_KERNEL_INSTANCE_JIT) r.k = {nullptr, "aie_jit_reset"}, r.module = true;
+    else if (env->spec >= 0 && env->spec < AIE_N_SPECS && aie_spec_kernel.reset[env->spec].fn) r.k = aie_spec_kernel.reset[env->spec];
+  }
+  return r;
+}
+
+// the reset of the replicas the mask selects (nullptr: all); keep_rewards: an auto-reset behind a step
+static void aie_launch_reset(aie_env* env, const uint8_t* d_mask, int keep_rewards, void* stream) {
+  const aie_route<aie_reset_fn> r = aie_select_reset(env);
+  const dim3 g((unsigned)env->P.E), b(r.block);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (r.module) {
+    const aie_params* dp = env->d_params;
+    uint8_t* ar = env->arena;
+    void* args[] = {&dp, &ar, &d_mask, &keep_rewards};
+    (void)hipModuleLaunchKernel(env->jit_reset, g.x, 1, 1, b.x, 1, 1, (unsigned)r.lds, st, args, nullptr);
+  } else if (!r.k.fn) {  // (no keep_rewards: the scenario restarts inside its step launch)
+    hipLaunchKernelGGL(aie_ose_reset_kernel, g, b, r.lds, st, env->d_params, env->arena, d_mask);
+  } else {
+    hipLaunchKernelGGL(r.k.fn, g, b, r.lds, st, env->d_params, env->arena, d_mask, keep_rewards);
+  }
+  if (env->P.c.scenario == AIE_SCN_GTB && aie__layout_staged(&env->P.c)) {
+    // generated layouts in the counter-stream mode: drawn ahead of their resets
+    const int threshold = env->P.E >= 4 ? (int)(env->P.E / 4) : 1;
+    hipLaunchKernelGGL(aie_layout_decide_kernel, dim3(1), dim3(1), 0, st, env->d_params, env->arena, threshold);
+    hipLaunchKernelGGL(aie_layout_refill_kernel, g, dim3(LG_NW * AIE_NT), r.lds, st, env->d_params, env->arena);
+  }
+}
+
+// The policy sampler's kernel for these row shapes: the fast instances when every row is one aligned lane segment, else
+// the kernel for rows of any shape.
+template <bool LOGP>
+using aie_policy_fn = void (*)(const aie_sampler_args, uint8_t*, const float*, const float*, uint64_t, int64_t, int32_t*, int32_t*,
+                               int, const SamplerLogp<LOGP>);
+template <bool LOGP>
+static aie_policy_fn<LOGP> aie_policy_sampler(const aie_sampler_args& S) {
+  if (S.ragged || S.agents.len > 64 || S.planner.len > 64) return aie_sample_policy_actions_kernel<LOGP>;
+  static const aie_policy_fn<LOGP> fast[3][3] = {
+      {aie_sample_policy_fast_kernel<4, 4, LOGP>, aie_sample_policy_fast_kernel<4, 5, LOGP>, aie_sample_policy_fast_kernel<4, 6, LOGP>},
+      {aie_sample_policy_fast_kernel<5, 4, LOGP>, aie_sample_policy_fast_kernel<5, 5, LOGP>, aie_sample_policy_fast_kernel<5, 6, LOGP>},
+      {aie_sample_policy_fast_kernel<6, 4, LOGP>, aie_sample_policy_fast_kernel<6, 5, LOGP>, aie_sample_policy_fast_kernel<6, 6, LOGP>}};
+  return fast[S.agents.lsh - 4][S.planner.lsh - 4];
+}
+
+// aie_sample_policy_actions and aie_sample_policy_actions_logp: the same launch, the second on the LOGP instances
+template <bool LOGP>
+static int aie_sample_policy_launch(aie_env* env, const float* d_logits_a, const float* d_logits_p, uint64_t seed,
+                                    int64_t global_env_offset, int32_t* d_actions_a, int32_t* d_actions_p, float* d_logp_a,
+                                    float* d_logp_p, void* stream) {
+  if (!env) return AIE_E_INVALID;
+  if ((d_actions_a && !d_logits_a) || (d_actions_p && !d_logits_p)) {
+    snprintf(env->err, sizeof(env->err), "aie_sample_policy_actions: an action buffer without its logits");
+    return AIE_E_INVALID;
+  }
+  if (LOGP && ((d_actions_a && d_logits_a && !d_logp_a) || (d_actions_p && d_logits_p && !d_logp_p))) {
+    snprintf(env->err, sizeof(env->err), "aie_sample_policy_actions_logp: an action buffer without its log-probability buffer");
+    return AIE_E_INVALID;
+  }
+  if (aie_sampler_check(&env->P, env->err, sizeof(env->err)) != AIE_OK) return AIE_E_UNSUPPORTED;
+  AIE_HIP_CHECK(env, hipSetDevice(env->device));
+  // waves per replica (1, 2 or 4 of a workgroup's four); AIE_SAMPLER_WAVES_LOG2 in the environment is a development knob
+  static const int wpr_log2 = [] {
+    const char* v = getenv("AIE_SAMPLER_WAVES_LOG2");
+    const int k = v ? atoi(v) : 1;
+    int r = k < 0 ? 0 : (k > 2 ? 2 : k);
+#ifdef AIE_DEV  // (AIE_SAMPLER_SKIP_* bits above the wave count: sampler_dev_skip takes them out again)
+    if (const char* sk = getenv("AIE_SAMPLER_DEV_SKIP")) r |= atoi(sk) << 8;
+#endif
+    return r;
+  }();
+  const int rpb = 4 >> (wpr_log2 & 255);
+  const aie_sampler_args S = aie_sampler_args_of(&env->P, env->d_params);
+  SamplerLogp<LOGP> LP;
+  if constexpr (LOGP) LP.a = d_logp_a, LP.p = d_logp_p;
+  hipLaunchKernelGGL(aie_policy_sampler<LOGP>(S), dim3((unsigned)((env->P.E + rpb - 1) / rpb)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), S, env->arena, d_logits_a, d_logits_p, seed, global_env_offset, d_actions_a,
+                     d_actions_p, wpr_log2, LP);
+  AIE_HIP_CHECK(env, hipGetLastError());
+  return AIE_OK;
 }
 
 extern "C" {
@@ -484,45 +680,6 @@ int aie_set_rng_state(aie_env* env, const uint32_t* key, const int32_t* pos) {
   return aie_upload(env, "mt_gauss", zd.data(), E * 8);
 }
 
-// gather-trade-build reset: the compile-time instance of the environment's configuration if it has one
-static void aie_launch_gtb_reset_only(aie_env* env, const uint8_t* d_mask, int keep_rewards, void* stream);
-static void aie_launch_gtb_reset(aie_env* env, const uint8_t* d_mask, int keep_rewards, void* stream) {
-  aie_launch_gtb_reset_only(env, d_mask, keep_rewards, stream);
-  if (aie__layout_staged(&env->P.c)) {  // generated layouts in the counter-stream mode: drawn ahead of their resets
-    const int threshold = env->P.E >= 4 ? (int)(env->P.E / 4) : 1;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(aie_layout_decide_kernel, dim3(1), dim3(1), 0, st, env->d_params, env->arena, threshold);
-    hipLaunchKernelGGL(aie_layout_refill_kernel, dim3((unsigned)env->P.E), dim3(LG_NW * AIE_NT),
-                       env->lds + aie::layout_gen_lds_bytes(env->P), st, env->d_params, env->arena);
-  }
-}
-static void aie_launch_gtb_reset_only(aie_env* env, const uint8_t* d_mask, int keep_rewards, void* stream) {
-  // LG_NW wavefronts per replica when the reset draws a new source layout (aie_kernels.hip: layout_generate), else one
-  const dim3 g((unsigned)env->P.E), b(env->P.c.layout_gen != AIE_LAYOUT_FIXED ? LG_NW * AIE_NT : AIE_NT);
-  const size_t lds = env->lds + aie::layout_gen_lds_bytes(env->P);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (env->spec == AIE_KERNEL_INSTANCE_JIT && env->P.dev_skip_mask == 0) {
-    const aie_params* dp = env->d_params;
-    uint8_t* ar = env->arena;
-    void* args[] = {&dp, &ar, &d_mask, &keep_rewards};
-    (void)hipModuleLaunchKernel(env->jit_reset, g.x, 1, 1, b.x, 1, 1, (unsigned)lds, st, args, nullptr);
-    return;
-  }
-#define AIE_SPEC_LAUNCH_RESET(K) \
-  case K: hipLaunchKernelGGL(aie_reset_kernel_spec<K>, g, b, lds, st, env->d_params, env->arena, d_mask, keep_rewards); return;
-  if (env->spec >= 0 && env->P.dev_skip_mask == 0) {
-    switch (env->spec) {
-      AIE_SPEC_LIST_GTB(AIE_SPEC_LAUNCH_RESET)
-      default: break;
-    }
-  }
-#undef AIE_SPEC_LAUNCH_RESET
-  if (env->P.c.layout_gen != AIE_LAYOUT_FIXED)
-    hipLaunchKernelGGL(aie_reset_kernel_layout, g, b, lds, st, env->d_params, env->arena, d_mask, keep_rewards);
-  else
-    hipLaunchKernelGGL(aie_reset_kernel, g, b, lds, st, env->d_params, env->arena, d_mask, keep_rewards);
-}
-
 int aie_reset(aie_env* env, const uint8_t* d_env_mask, void* stream) {
   if (!env) return AIE_E_INVALID;
   AIE_HIP_CHECK(env, hipSetDevice(env->device));
@@ -535,14 +692,7 @@ int aie_reset(aie_env* env, const uint8_t* d_env_mask, void* stream) {
     else
       (void)hipGetLastError();
   }
-  if (env->P.c.scenario == AIE_SCN_COVID)
-    hipLaunchKernelGGL(aie_covid_reset_kernel, dim3((unsigned)env->P.E), dim3(AIE_NT), 0,
-                       static_cast<hipStream_t>(stream), env->d_params, env->arena, d_env_mask, 0);
-  else if (env->P.c.scenario == AIE_SCN_ONE_STEP_ECONOMY)
-    hipLaunchKernelGGL(aie_ose_reset_kernel, dim3((unsigned)env->P.E), dim3(OSE_NT), env->lds,
-                       static_cast<hipStream_t>(stream), env->d_params, env->arena, d_env_mask);
-  else
-    aie_launch_gtb_reset(env, d_env_mask, 0, stream);
+  aie_launch_reset(env, d_env_mask, 0, stream);
   AIE_HIP_CHECK(env, hipGetLastError());
   return AIE_OK;
 }
@@ -613,27 +763,37 @@ int aie_step_range(aie_env* env, const int32_t* d_actions_a, const int32_t* d_ac
   next.comp_hi = comp_hi;
   next.phase = phases | 32;  // (never 0 = "a whole step": bit 5 marks a ranged launch)
   next.mask = d_env_mask;
-  hipLaunchKernelGGL(aie_step_kernel_log, dim3((unsigned)P.E), dim3(2 * AIE_NT), env->lds, static_cast<hipStream_t>(stream),
-                     env->d_params, env->arena, d_actions_a, d_actions_p, next);
+  aie_route<aie_step_fn> r;  // (ranges and masks: honoured by the full-featured kernel only)
+  if (const int rc = aie_select_step(env, /*full=*/true, &r)) return rc;
+  if (const int rc = aie_launch_step(env, r, (unsigned)P.E, d_actions_a, d_actions_p, next, static_cast<hipStream_t>(stream))) return rc;
   if ((phases & (AIE_STEP_TAIL | AIE_STEP_CLOSE)) && P.auto_reset)  // as behind aie_step: the replicas this step finished restart right behind it
-    aie_launch_gtb_reset(env, env->arena + P.a_done, 1, stream);
+    aie_launch_reset(env, env->arena + P.a_done, 1, stream);
   AIE_HIP_CHECK(env, hipGetLastError());
+  return AIE_OK;
+}
+
+// aie_step_sample_next / aie_step_sample_next_masked: the next step's actions may not alias the current ones
+static int aie_next_actions(aie_env* env, const char* who, const int32_t* d_actions_a, const int32_t* d_actions_p, uint64_t seed,
+                            int64_t global_env_offset, int32_t* d_next_a, int32_t* d_next_p, NextActions* next) {
+  if ((d_next_a && d_next_a == d_actions_a) || (d_next_p && d_next_p == d_actions_p)) {
+    snprintf(env->err, sizeof(env->err), "%s: the next-action buffers must differ from the current ones", who);
+    return AIE_E_INVALID;
+  }
+  next->a = d_next_a;
+  next->p = d_next_p;
+  next->seed = seed;
+  next->env_offset = global_env_offset;
   return AIE_OK;
 }
 
 int aie_step_sample_next(aie_env* env, const int32_t* d_actions_a, const int32_t* d_actions_p, uint64_t seed,
                          int64_t global_env_offset, int32_t* d_next_a, int32_t* d_next_p, void* stream) {
   if (!env) return AIE_E_INVALID;
-  if ((d_next_a && d_next_a == d_actions_a) || (d_next_p && d_next_p == d_actions_p)) {
-    snprintf(env->err, sizeof(env->err), "aie_step_sample_next: the next-action buffers must differ from the current ones");
-    return AIE_E_INVALID;
-  }
-  if (aie_sampler_check(&env->P, env->err, sizeof(env->err)) != AIE_OK) return AIE_E_UNSUPPORTED;
   NextActions next{};
-  next.a = d_next_a;
-  next.p = d_next_p;
-  next.seed = seed;
-  next.env_offset = global_env_offset;
+  if (const int rc = aie_next_actions(env, "aie_step_sample_next", d_actions_a, d_actions_p, seed, global_env_offset, d_next_a,
+                                      d_next_p, &next))
+    return rc;
+  if (aie_sampler_check(&env->P, env->err, sizeof(env->err)) != AIE_OK) return AIE_E_UNSUPPORTED;
   return aie_step_impl(env, d_actions_a, d_actions_p, stream, next);
 }
 
@@ -644,15 +804,10 @@ int aie_step_sample_next_masked(aie_env* env, const int32_t* d_actions_a, const 
     snprintf(env->err, sizeof(env->err), "aie_step_sample_next_masked: COVID scenario only (elsewhere: aie_step + aie_sample_masked_actions)");
     return AIE_E_UNSUPPORTED;
   }
-  if ((d_next_a && d_next_a == d_actions_a) || (d_next_p && d_next_p == d_actions_p)) {
-    snprintf(env->err, sizeof(env->err), "aie_step_sample_next_masked: the next-action buffers must differ from the current ones");
-    return AIE_E_INVALID;
-  }
   NextActions next{};
-  next.a = d_next_a;
-  next.p = d_next_p;
-  next.seed = seed;
-  next.env_offset = global_env_offset;
+  if (const int rc = aie_next_actions(env, "aie_step_sample_next_masked", d_actions_a, d_actions_p, seed, global_env_offset,
+                                      d_next_a, d_next_p, &next))
+    return rc;
   next.masked = 1;
   return aie_step_impl(env, d_actions_a, d_actions_p, stream, next);
 }
@@ -660,120 +815,38 @@ int aie_step_sample_next_masked(aie_env* env, const int32_t* d_actions_a, const 
 static int aie_step_impl(aie_env* env, const int32_t* d_actions_a, const int32_t* d_actions_p, void* stream,
                          const NextActions& next_in) {
   if (!env) return AIE_E_INVALID;
+  const aie_params& P = env->P;
+  hipStream_t st = static_cast<hipStream_t>(stream);
   NextActions next = next_in;
-  next.E = (int32_t)env->P.E;
+  next.E = (int32_t)P.E;
   AIE_HIP_CHECK(env, hipSetDevice(env->device));
-  if (env->P.saez_stride)  // tax_model "saez": the period-start formula runs ahead of the step (aie_kernels_saez.hip)
-    hipLaunchKernelGGL(aie_saez_kernel, dim3((unsigned)env->P.E), dim3(AIE_NT), 0, static_cast<hipStream_t>(stream),
-                       env->d_params, env->arena);
-  if (env->P.c.scenario == AIE_SCN_GTB && env->P.ev_replicas > 0 && env->log_active) {
+  if (P.saez_stride)  // tax_model "saez": the period-start formula runs ahead of the step (aie_kernels_saez.hip)
+    hipLaunchKernelGGL(aie_saez_kernel, dim3((unsigned)P.E), dim3(AIE_NT), 0, st, env->d_params, env->arena);
+  aie_route<aie_step_fn> r;
+  if (const unsigned log_grid = aie_log_grid(env)) {
     // dense-log replicas whose episode is being logged: they -- and only they -- take the full-featured kernel, which
-    // records the AIE_EV_* rows; every other replica runs the environment's fast kernel below, in the same stream
+    // records the AIE_EV_* rows; every other replica runs the environment's own kernel below, in the same stream
     NextActions lg = next;
     lg.e_lo = 0;
-    lg.e_hi = env->P.ev_replicas;
-    // The grid covers the workgroups that map to the logged replicas [0, L) and as little else as possible (the others
-    // leave at once): replica_of_block is the identity when E is not a multiple of 8, else replica e < E / 8 is workgroup 8 e.
-    const int64_t L = env->P.ev_replicas, E8 = env->P.E >> 3;
-    const unsigned log_grid = (env->P.E & 7) ? (unsigned)L : (L <= E8 ? (unsigned)(8 * (L - 1) + 1) : (unsigned)env->P.E);
-    hipLaunchKernelGGL(aie_step_kernel_log, dim3(log_grid), dim3(2 * AIE_NT), env->lds,
-                       static_cast<hipStream_t>(stream), env->d_params, env->arena, d_actions_a, d_actions_p, lg);
-    if (env->P.ev_replicas >= env->P.E) goto stepped;
-    next.e_lo = env->P.ev_replicas;
-    next.e_hi = env->P.E;
+    lg.e_hi = P.ev_replicas;
+    if (const int rc = aie_select_step(env, /*full=*/true, &r)) return rc;
+    if (const int rc = aie_launch_step(env, r, log_grid, d_actions_a, d_actions_p, lg, st)) return rc;
+    next.e_lo = P.ev_replicas;
+    next.e_hi = P.E;
   }
-  if (env->P.c.scenario == AIE_SCN_COVID) {
-    const dim3 g((unsigned)env->P.E), b(AIE_NT);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 gw((unsigned)((env->P.E + AIE_CV_WIN_WAVES - 1) / AIE_CV_WIN_WAVES)), bw(AIE_CV_WIN_WAVES * AIE_NT);
-    const size_t lw = aie_covid_win_lds_bytes(env->P, env->cv_taps_f32 ? 4 : 8);
-    // window sums: the step, then -- a launch of its own -- the upkeep of the change-event lists and the next step's sums
-#define AIE_CV_LAUNCH(FN) \
-  case FN: if (env->P.c.covid.filter_recurrence) hipLaunchKernelGGL((aie_covid_step_kernel<FN, true>), g, b, 0, st, env->d_params, env->arena, d_actions_a, d_actions_p, next); \
-           else { \
-             hipLaunchKernelGGL((aie_covid_step_kernel<FN, false>), g, b, 0, st, env->d_params, env->arena, d_actions_a, d_actions_p, next); \
-             if (env->cv_taps_f32) hipLaunchKernelGGL((aie_covid_window_kernel<FN, float>), gw, bw, lw, st, env->d_params, env->arena); \
-             else hipLaunchKernelGGL((aie_covid_window_kernel<FN, double>), gw, bw, lw, st, env->d_params, env->arena); \
-           } \
-           break
-    switch (env->P.cv_F) {
-      AIE_CV_LAUNCH(1); AIE_CV_LAUNCH(2); AIE_CV_LAUNCH(3); AIE_CV_LAUNCH(4);
-      AIE_CV_LAUNCH(5); AIE_CV_LAUNCH(6); AIE_CV_LAUNCH(7); AIE_CV_LAUNCH(8);
-      default: return AIE_E_UNSUPPORTED;
+  if (next.e_lo < P.E) {  // (unless the logged replicas were all of them)
+    if (const int rc = aie_select_step(env, /*full=*/false, &r)) return rc;
+    if (const int rc = aie_launch_step(env, r, (unsigned)P.E, d_actions_a, d_actions_p, next, st)) return rc;
+    if (P.c.scenario == AIE_SCN_COVID && !P.c.covid.filter_recurrence) {
+      // window sums: a launch of its own behind the step -- the upkeep of the change-event lists and the next step's sums
+      const int f32 = env->cv_taps_f32 ? 1 : 0;
+      hipLaunchKernelGGL(aie_cv_window_kernel[P.cv_F - 1][f32].fn, dim3((unsigned)((P.E + AIE_CV_WIN_WAVES - 1) / AIE_CV_WIN_WAVES)),
+                         dim3(AIE_CV_WIN_WAVES * AIE_NT), aie_covid_win_lds_bytes(P, f32 ? 4 : 8), st, env->d_params, env->arena);
     }
-#undef AIE_CV_LAUNCH
-  } else if (env->P.c.scenario == AIE_SCN_ONE_STEP_ECONOMY && env->spec == AIE_KERNEL_INSTANCE_JIT) {
-    const aie_params* dp = env->d_params;
-    uint8_t* ar = env->arena;
-    NextActions nx = next;
-    void* args[] = {&dp, &ar, &d_actions_a, &d_actions_p, &nx};
-    AIE_HIP_CHECK(env, hipModuleLaunchKernel(env->jit_step, (unsigned)env->P.E, 1, 1, OSE_NT, 1, 1, (unsigned)env->lds,
-                                             static_cast<hipStream_t>(stream), args, nullptr));
-  } else if (env->P.c.scenario == AIE_SCN_ONE_STEP_ECONOMY && env->spec >= 0) {
-    const dim3 g((unsigned)env->P.E), b(OSE_NT);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-#define AIE_SPEC_LAUNCH_OSE(K) \
-  case K: hipLaunchKernelGGL(aie_ose_step_kernel_spec<K>, g, b, env->lds, st, env->d_params, env->arena, d_actions_a, d_actions_p, next); break;
-    switch (env->spec) {
-      AIE_SPEC_LIST_OSE(AIE_SPEC_LAUNCH_OSE)
-      default: return AIE_E_INVALID;
-    }
-#undef AIE_SPEC_LAUNCH_OSE
-  } else if (env->P.c.scenario == AIE_SCN_ONE_STEP_ECONOMY)
-    hipLaunchKernelGGL(aie_ose_step_kernel, dim3((unsigned)env->P.E), dim3(OSE_NT), env->lds,
-                       static_cast<hipStream_t>(stream), env->d_params, env->arena, d_actions_a, d_actions_p, next);
-#ifdef AIE_DEV
-  else if (env->spec >= 0 && !(env->P.dev_skip_mask & AIE_DEV_GENERIC_KERNEL) && (env->P.dev_trace != nullptr || env->P.dev_skip_mask != 0)) {
-    const dim3 g((unsigned)env->P.E), b(2 * AIE_NT);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-#define AIE_SPEC_LAUNCH_TR(K) \
-  case K: hipLaunchKernelGGL(aie_step_kernel_spec_trace<K>, g, b, env->lds, st, env->d_params, env->arena, d_actions_a, d_actions_p, next); break;
-    switch (env->spec) {
-      AIE_SPEC_LIST_GTB(AIE_SPEC_LAUNCH_TR)
-      default: return AIE_E_INVALID;
-    }
-#undef AIE_SPEC_LAUNCH_TR
   }
-#endif
-  else if (env->P.saez_stride || env->P.M > AIE_NT || env->P.regen_general || env->P.dev_skip_mask != 0 ||
-           env->P.dev_trace != nullptr || env->P.n_host_a || env->P.n_host_p)  // (foreign action subspaces: decoded by this kernel only)
-    hipLaunchKernelGGL(aie_step_kernel_log, dim3((unsigned)env->P.E), dim3(2 * AIE_NT), env->lds,
-                       static_cast<hipStream_t>(stream), env->d_params, env->arena, d_actions_a, d_actions_p, next);
-  else if (env->spec == AIE_KERNEL_INSTANCE_JIT) {
-    const aie_params* dp = env->d_params;
-    uint8_t* ar = env->arena;
-    NextActions nx = next;
-    void* args[] = {&dp, &ar, &d_actions_a, &d_actions_p, &nx};
-    AIE_HIP_CHECK(env, hipModuleLaunchKernel(env->jit_step, (unsigned)env->P.E, 1, 1, 2 * AIE_NT, 1, 1, (unsigned)env->lds,
-                                             static_cast<hipStream_t>(stream), args, nullptr));
-  } else if (env->spec >= 0) {
-    const dim3 g((unsigned)env->P.E), b(2 * AIE_NT);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-#define AIE_SPEC_LAUNCH(K) \
-  case K: hipLaunchKernelGGL(aie_step_kernel_spec<K>, g, b, env->lds, st, env->d_params, env->arena, d_actions_a, d_actions_p, next); break;
-    switch (env->spec) {
-      AIE_SPEC_LIST_GTB(AIE_SPEC_LAUNCH)
-      default: return AIE_E_INVALID;
-    }
-#undef AIE_SPEC_LAUNCH
-  } else if (aie_workgroups_per_cu(env->lds) <= 12)
-    hipLaunchKernelGGL(aie_step_kernel_r6, dim3((unsigned)env->P.E), dim3(2 * AIE_NT), env->lds,
-                       static_cast<hipStream_t>(stream), env->d_params, env->arena, d_actions_a, d_actions_p, next);
-  else
-    hipLaunchKernelGGL(aie_step_kernel, dim3((unsigned)env->P.E), dim3(2 * AIE_NT), env->lds,
-                       static_cast<hipStream_t>(stream), env->d_params, env->arena, d_actions_a, d_actions_p, next);
-stepped:
-  if (env->P.auto_reset && env->P.c.scenario != AIE_SCN_ONE_STEP_ECONOMY) {
-    // auto-reset: the replicas this step finished restart right behind it on the same stream (mask = the `done`
-    // tensor the step just wrote; the reset keeps the terminal rewards / done).  one-step-economy does it inside the
-    // step launch itself.
-    const uint8_t* done = env->arena + env->P.a_done;
-    if (env->P.c.scenario == AIE_SCN_COVID)
-      hipLaunchKernelGGL(aie_covid_reset_kernel, dim3((unsigned)env->P.E), dim3(AIE_NT), 0,
-                         static_cast<hipStream_t>(stream), env->d_params, env->arena, done, 1);
-    else
-      aie_launch_gtb_reset(env, done, 1, stream);
-  }
+  // auto-reset: the replicas this step finished restart right behind it on the same stream (mask = the `done` tensor
+  // the step just wrote; the reset keeps the terminal rewards / done).  one-step-economy does it inside the step launch.
+  if (P.auto_reset && P.c.scenario != AIE_SCN_ONE_STEP_ECONOMY) aie_launch_reset(env, env->arena + P.a_done, 1, stream);
   AIE_HIP_CHECK(env, hipGetLastError());
   return AIE_OK;
 }
@@ -820,110 +893,41 @@ int aie_set_auto_reset(aie_env* env, int on) {
   return AIE_OK;
 }
 
+// aie_sample_random_actions and aie_sample_masked_actions: the same launches around two kernels
+static int aie_sample_actions(aie_env* env, decltype(&aie_sample_actions_kernel) kernel, uint64_t seed, int64_t global_env_offset,
+                              int32_t* d_actions_a, int32_t* d_actions_p, void* stream) {
+  if (!env) return AIE_E_INVALID;
+  if (aie_sampler_check(&env->P, env->err, sizeof(env->err)) != AIE_OK) return AIE_E_UNSUPPORTED;
+  AIE_HIP_CHECK(env, hipSetDevice(env->device));
+  const aie_params& P = env->P;
+  const int64_t tot = (int64_t)P.E * (P.n * P.act_a_width + P.act_p_width);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), P, env->arena,
+                     seed, global_env_offset, d_actions_a, d_actions_p);
+  hipLaunchKernelGGL(aie_sample_advance_kernel, dim3((unsigned)((P.E + 255) / 256)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), env->arena, P.a_records, P.rec_bytes, P.o_sample_t, P.E);
+  AIE_HIP_CHECK(env, hipGetLastError());
+  return AIE_OK;
+}
 int aie_sample_random_actions(aie_env* env, uint64_t seed, int64_t global_env_offset, int32_t* d_actions_a,
                               int32_t* d_actions_p, void* stream) {
-  if (!env) return AIE_E_INVALID;
-  if (aie_sampler_check(&env->P, env->err, sizeof(env->err)) != AIE_OK) return AIE_E_UNSUPPORTED;
-  AIE_HIP_CHECK(env, hipSetDevice(env->device));
-  const aie_params& P = env->P;
-  const int64_t tot = (int64_t)P.E * (P.n * P.act_a_width + P.act_p_width);
-  hipLaunchKernelGGL(aie_sample_actions_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), P, env->arena, seed, global_env_offset, d_actions_a, d_actions_p);
-  hipLaunchKernelGGL(aie_sample_advance_kernel, dim3((unsigned)((P.E + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), env->arena, P.a_records, P.rec_bytes, P.o_sample_t, P.E);
-  AIE_HIP_CHECK(env, hipGetLastError());
-  return AIE_OK;
+  return aie_sample_actions(env, aie_sample_actions_kernel, seed, global_env_offset, d_actions_a, d_actions_p, stream);
 }
-
 int aie_sample_masked_actions(aie_env* env, uint64_t seed, int64_t global_env_offset, int32_t* d_actions_a,
                               int32_t* d_actions_p, void* stream) {
-  if (!env) return AIE_E_INVALID;
-  if (aie_sampler_check(&env->P, env->err, sizeof(env->err)) != AIE_OK) return AIE_E_UNSUPPORTED;
-  AIE_HIP_CHECK(env, hipSetDevice(env->device));
-  const aie_params& P = env->P;
-  const int64_t tot = (int64_t)P.E * (P.n * P.act_a_width + P.act_p_width);
-  hipLaunchKernelGGL(aie_sample_masked_actions_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), P, env->arena, seed, global_env_offset, d_actions_a, d_actions_p);
-  hipLaunchKernelGGL(aie_sample_advance_kernel, dim3((unsigned)((P.E + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), env->arena, P.a_records, P.rec_bytes, P.o_sample_t, P.E);
-  AIE_HIP_CHECK(env, hipGetLastError());
-  return AIE_OK;
-}
-
-// aie_sample_policy_actions and aie_sample_policy_actions_logp: the same launch, the second on the LOGP instances
-static int aie_sample_policy_launch(aie_env* env, const float* d_logits_a, const float* d_logits_p, uint64_t seed,
-                                    int64_t global_env_offset, int32_t* d_actions_a, int32_t* d_actions_p, bool with_logp,
-                                    float* d_logp_a, float* d_logp_p, void* stream) {
-  if (!env) return AIE_E_INVALID;
-  if ((d_actions_a && !d_logits_a) || (d_actions_p && !d_logits_p)) {
-    snprintf(env->err, sizeof(env->err), "aie_sample_policy_actions: an action buffer without its logits");
-    return AIE_E_INVALID;
-  }
-  if (with_logp && ((d_actions_a && d_logits_a && !d_logp_a) || (d_actions_p && d_logits_p && !d_logp_p))) {
-    snprintf(env->err, sizeof(env->err), "aie_sample_policy_actions_logp: an action buffer without its log-probability buffer");
-    return AIE_E_INVALID;
-  }
-  if (aie_sampler_check(&env->P, env->err, sizeof(env->err)) != AIE_OK) return AIE_E_UNSUPPORTED;
-  AIE_HIP_CHECK(env, hipSetDevice(env->device));
-  // waves per replica (1, 2 or 4 of a workgroup's four); AIE_SAMPLER_WAVES_LOG2 in the environment is a development knob
-  static const int wpr_log2 = [] {
-    const char* v = getenv("AIE_SAMPLER_WAVES_LOG2");
-    const int k = v ? atoi(v) : 1;
-    int r = k < 0 ? 0 : (k > 2 ? 2 : k);
-#ifdef AIE_DEV
-    if (const char* sk = getenv("AIE_SAMPLER_DEV_SKIP")) r |= atoi(sk) << 8;
-#endif
-    return r;
-  }();
-  const int rpb = 4 >> (wpr_log2 & 255);
-  const aie_sampler_args S = aie_sampler_args_of(&env->P, env->d_params);
-  using sampler_fn = void (*)(const aie_sampler_args, uint8_t*, const float*, const float*, uint64_t, int64_t, int32_t*, int32_t*, int,
-                              const SamplerLogp<false>);
-  sampler_fn fn = aie_sample_policy_actions_kernel<false>;  // rows of any shape
-  if (!S.ragged && S.agents.len <= 64 && S.planner.len <= 64) {  // every row one aligned lane segment: the fast instances
-    static const sampler_fn fast[3][3] = {
-        {aie_sample_policy_fast_kernel<4, 4, false>, aie_sample_policy_fast_kernel<4, 5, false>, aie_sample_policy_fast_kernel<4, 6, false>},
-        {aie_sample_policy_fast_kernel<5, 4, false>, aie_sample_policy_fast_kernel<5, 5, false>, aie_sample_policy_fast_kernel<5, 6, false>},
-        {aie_sample_policy_fast_kernel<6, 4, false>, aie_sample_policy_fast_kernel<6, 5, false>, aie_sample_policy_fast_kernel<6, 6, false>}};
-    fn = fast[S.agents.lsh - 4][S.planner.lsh - 4];
-  }
-  const bool fast_rows = !S.ragged && S.agents.len <= 64 && S.planner.len <= 64;
-  const dim3 grid((unsigned)((env->P.E + rpb - 1) / rpb));
-  if (with_logp) {
-    using logp_fn = void (*)(const aie_sampler_args, uint8_t*, const float*, const float*, uint64_t, int64_t, int32_t*, int32_t*, int,
-                             const SamplerLogp<true>);
-    logp_fn lfn = aie_sample_policy_actions_kernel<true>;
-    if (fast_rows) {
-      static const logp_fn fast[3][3] = {
-          {aie_sample_policy_fast_kernel<4, 4, true>, aie_sample_policy_fast_kernel<4, 5, true>, aie_sample_policy_fast_kernel<4, 6, true>},
-          {aie_sample_policy_fast_kernel<5, 4, true>, aie_sample_policy_fast_kernel<5, 5, true>, aie_sample_policy_fast_kernel<5, 6, true>},
-          {aie_sample_policy_fast_kernel<6, 4, true>, aie_sample_policy_fast_kernel<6, 5, true>, aie_sample_policy_fast_kernel<6, 6, true>}};
-      lfn = fast[S.agents.lsh - 4][S.planner.lsh - 4];
-    }
-    SamplerLogp<true> LP;
-    LP.a = d_logp_a;
-    LP.p = d_logp_p;
-    hipLaunchKernelGGL(lfn, grid, dim3(256), 0, static_cast<hipStream_t>(stream), S, env->arena, d_logits_a, d_logits_p, seed,
-                       global_env_offset, d_actions_a, d_actions_p, wpr_log2, LP);
-  } else {
-    hipLaunchKernelGGL(fn, grid, dim3(256), 0, static_cast<hipStream_t>(stream), S, env->arena, d_logits_a, d_logits_p, seed,
-                       global_env_offset, d_actions_a, d_actions_p, wpr_log2, SamplerLogp<false>());
-  }
-  AIE_HIP_CHECK(env, hipGetLastError());
-  return AIE_OK;
+  return aie_sample_actions(env, aie_sample_masked_actions_kernel, seed, global_env_offset, d_actions_a, d_actions_p, stream);
 }
 
 int aie_sample_policy_actions(aie_env* env, const float* d_logits_a, const float* d_logits_p, uint64_t seed,
                               int64_t global_env_offset, int32_t* d_actions_a, int32_t* d_actions_p, void* stream) {
-  return aie_sample_policy_launch(env, d_logits_a, d_logits_p, seed, global_env_offset, d_actions_a, d_actions_p, false, nullptr,
-                                  nullptr, stream);
+  return aie_sample_policy_launch<false>(env, d_logits_a, d_logits_p, seed, global_env_offset, d_actions_a, d_actions_p, nullptr,
+                                         nullptr, stream);
 }
 
 int aie_sample_policy_actions_logp(aie_env* env, const float* d_logits_a, const float* d_logits_p, uint64_t seed,
                                    int64_t global_env_offset, int32_t* d_actions_a, int32_t* d_actions_p, float* d_logp_a,
                                    float* d_logp_p, void* stream) {
-  return aie_sample_policy_launch(env, d_logits_a, d_logits_p, seed, global_env_offset, d_actions_a, d_actions_p, true, d_logp_a,
-                                  d_logp_p, stream);
+  return aie_sample_policy_launch<true>(env, d_logits_a, d_logits_p, seed, global_env_offset, d_actions_a, d_actions_p, d_logp_a,
+                                        d_logp_p, stream);
 }
 
 // The evaluation kernels' argument: the sampler's row shapes (aie_sampler_args_of), the caller's pointers, B batch elements.
@@ -1301,15 +1305,35 @@ AIE_DEV_API int aie_dev_set_lds_pad(aie_env* env, int bytes) {
 AIE_DEV_API int aie_dev_set_draw_window(aie_env* env, int words) {
   if (!env || words < 0) return AIE_E_INVALID;
   env->P.dev_draw_window = words;
-  env->P.dev_skip_mask = words ? (env->P.dev_skip_mask | AIE_DEV_GENERIC_KERNEL) : (env->P.dev_skip_mask & ~AIE_DEV_GENERIC_KERNEL);
+  env->dev_generic = words ? 1 : 0;
   return aie_dev_push_params(env);
 }
 
-// phases of the step kernel to skip
+// parts of the scenario's step kernel to switch off (aie_layout.h: AIE_DEV_SKIP_* / AIE_OSE_SKIP_* / AIE_CV_SKIP_*)
 AIE_DEV_API int aie_dev_set_skip_mask(aie_env* env, int mask) {
   if (!env) return AIE_E_INVALID;
   env->P.dev_skip_mask = mask;
   return aie_dev_push_params(env);
+}
+// The names of what the next aie_step and the next aie_reset would launch, as the selectors give them:
+// "<step launches, joined by ' + '> | <reset kernel>"; a launch over a replica range reads name[lo,hi)xgrid.
+AIE_DEV_API int aie_dev_step_route(aie_env* env, char* buf, int n) {
+  if (!env || !buf || n < 1) return AIE_E_INVALID;
+  const aie_params& P = env->P;
+  const int lo = aie_log_grid(env) ? P.ev_replicas : 0;
+  std::string s = P.saez_stride ? "aie_saez_kernel + " : "";
+  aie_route<aie_step_fn> r;
+  int rc = AIE_OK;
+  if (lo && (rc = aie_select_step(env, /*full=*/true, &r)) == AIE_OK)
+    s += std::string(r.k.name) + "[0," + std::to_string(lo) + ")x" + std::to_string(aie_log_grid(env)) + (lo < P.E ? " + " : "");
+  if (rc == AIE_OK && lo < P.E && (rc = aie_select_step(env, /*full=*/false, &r)) == AIE_OK) {
+    s += r.k.name + (lo ? "[" + std::to_string(lo) + "," + std::to_string(P.E) + ")" : std::string());
+    if (P.c.scenario == AIE_SCN_COVID && !P.c.covid.filter_recurrence)
+      s += std::string(" + ") + aie_cv_window_kernel[P.cv_F - 1][env->cv_taps_f32 ? 1 : 0].name;
+  }
+  if (rc != AIE_OK) s = "error " + std::to_string(rc);
+  snprintf(buf, (size_t)n, "%s | %s", s.c_str(), aie_select_reset(env).k.name);
+  return AIE_OK;
 }
 #endif  // AIE_DEV
 

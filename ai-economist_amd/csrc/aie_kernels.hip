@@ -2537,7 +2537,7 @@ __device__ __forceinline__ void write_flat_observations(const Ctx& c, uint8_t* _
 
   const int skip = c.skipm;
   // ================= stage A: per-(commodity, price) sums, per-agent scalars ===========
-  if (P.has_cda && !(skip & 64)) {
+  if (P.has_cda && !(skip & AIE_DEV_SKIP_FLAT_STAGE_A)) {
     // lanes over (commodity r, price k): net price history and full bid / ask histograms
     double* net_ph = scr_net_ph(c);
     for (int q = tid; q < 2 * Pp; q += AIE_NT) {
@@ -2552,7 +2552,7 @@ __device__ __forceinline__ void write_flat_observations(const Ctx& c, uint8_t* _
       g[AIE_FP_CDA_PRICE_HISTORY(Pp) + q] = (float)(s * isc);
     }
   }
-  if (tid < n && !(skip & 64)) {
+  if (tid < n && !(skip & AIE_DEV_SKIP_FLAT_STAGE_A)) {
     const int i = tid;
     const int f0 = i * P.FA;
     const AgentScalars a(c, i);
@@ -2591,7 +2591,7 @@ __device__ __forceinline__ void write_flat_observations(const Ctx& c, uint8_t* _
   AIE_WSYNC();
 
   // ================= stage B: fill the vectors, one lane per element =====================
-  if (P.has_cda && !(skip & 128)) {
+  if (P.has_cda && !(skip & AIE_DEV_SKIP_FLAT_CDA)) {
     // continuous_double_auction.py:491-542
     if (tid < 2) {
       const int r = tid;
@@ -2615,7 +2615,7 @@ __device__ __forceinline__ void write_flat_observations(const Ctx& c, uint8_t* _
       AF(fc + AIE_FA_CDA_PRICE_HISTORY(Pp) + q, g[AIE_FP_CDA_PRICE_HISTORY(Pp) + q]);
     }
   }
-  if (P.has_tax && !(skip & 256)) {
+  if (P.has_tax && !(skip & AIE_DEV_SKIP_FLAT_TAX)) {
     // redistribution.py:974-1023; lanes over (agent or planner, element of the fragment)
     const TaxCalendar cal = tax_calendar(c);
     const int fragA = AIE_FA_TAX_LEN(NB, n);
@@ -2642,7 +2642,7 @@ __device__ __forceinline__ void write_flat_observations(const Ctx& c, uint8_t* _
   AIE_WSYNC();
 
   // ---- stream the staged vectors out: 16-byte LDS reads, dword-aligned 16-byte stores ----
-  if (!(skip & 1024)) {
+  if (!(skip & AIE_DEV_SKIP_PLANNER_COPY_OUT)) {
     stream_out(s_pag, reinterpret_cast<float*>(arena + c.R.a_obs_p_agents) + (int64_t)c.e * n * P.FPA, n * P.FPA, tid);
     stream_out(s_pflat, reinterpret_cast<float*>(arena + c.R.a_obs_p_flat) + (int64_t)c.e * P.FP, P.FP, tid);
   }
@@ -2669,21 +2669,21 @@ __device__ __forceinline__ void update_flat_observations(const Ctx& c, uint8_t* 
   float* const pag = reinterpret_cast<float*>(arena + c.R.a_obs_p_agents) + (int64_t)c.e * n * P.FPA;
   const float tval = flat_time_value(c);
   const int skip = c.skipm;
-  if (P.has_cda && !(skip & 64)) {
+  if (P.has_cda && !(skip & AIE_DEV_SKIP_FLAT_STAGE_A)) {
     // lanes over (commodity r, price k): the column's net price history; its order counts where they changed
     double* net_ph = scr_net_ph(c);
     for (int q = tid; q < 2 * Pp; q += AIE_NT) {
       const int r = q >= Pp ? 1 : 0, k = q - r * Pp;
       const double s = price_history_column(c, r, k, [](int) {});
       net_ph[q] = s;
-      if (s != 0 && !(skip & 128)) {
+      if (s != 0 && !(skip & AIE_DEV_SKIP_FLAT_CDA)) {
         const float v = (float)(s * isc);
         pflat[P.fp_cda + AIE_FP_CDA_PRICE_HISTORY(Pp) + q] = v;
         for (int i = 0; i < n; ++i) AF(i * P.FA + P.fa_cda + AIE_FA_CDA_PRICE_HISTORY(Pp) + q, v);
       }
 #pragma unroll
       for (int side = 0; side < 2; ++side) {  // 0: asks, 1: bids
-        if (!hist_col_dirty(P, hist_dirty, r, side, k) || (skip & 128)) continue;
+        if (!hist_col_dirty(P, hist_dirty, r, side, k) || (skip & AIE_DEV_SKIP_FLAT_CDA)) continue;
         const uint8_t* h = side ? R_U8(c, o_cda_bid_hist) : R_U8(c, o_cda_ask_hist);
         int f = 0;
         for (int i = 0; i < n; ++i) f += h[(r * n + i) * Pp + k];
@@ -2698,7 +2698,7 @@ __device__ __forceinline__ void update_flat_observations(const Ctx& c, uint8_t* 
       }
     }
   }
-  if (tid < n && !(skip & 64)) {
+  if (tid < n && !(skip & AIE_DEV_SKIP_FLAT_STAGE_A)) {
     const int i = tid;
     const AgentScalars a(c, i);
     float* q = pag + i * P.FPA;
@@ -2709,7 +2709,7 @@ __device__ __forceinline__ void update_flat_observations(const Ctx& c, uint8_t* 
     pflat[P.fp_time] = tval;
     reinterpret_cast<float*>(arena + c.R.a_obs_p_time)[c.e] = tval;
   }
-  if (P.has_tax && !(skip & 256)) {  // the calendar entries of the n agents' and the planner's tax block
+  if (P.has_tax && !(skip & AIE_DEV_SKIP_FLAT_TAX)) {  // the calendar entries of the n agents' and the planner's tax block
     const TaxCalendar cal = tax_calendar(c);
     for (int i = tid; i <= n; i += AIE_NT) {
       if (i == n) {
@@ -2723,7 +2723,7 @@ __device__ __forceinline__ void update_flat_observations(const Ctx& c, uint8_t* 
       }
     }
   }
-  if (P.has_cda && !(skip & 128)) {
+  if (P.has_cda && !(skip & AIE_DEV_SKIP_FLAT_CDA)) {
     AIE_WSYNC();  // (net_ph)
     if (tid < 2) {
       const int r = tid;
@@ -2748,7 +2748,7 @@ __device__ __forceinline__ void write_action_masks(const Ctx& c, uint8_t* __rest
   const aie_params& P = c.P;
   const int n = P.n, tid = c.tid, Pp = P.P;
   const int skip = c.skipm;
-  if (skip & 512) return;
+  if (skip & AIE_DEV_SKIP_MASKS) return;
   if (!P.o_mask_bits) all = true;
   if (tid < n) {
     const int i = tid;
@@ -2876,8 +2876,7 @@ __device__ __forceinline__ void build_src_list(const Ctx& c, uint8_t* __restrict
 // BaseEnvironment.step, F/base/base_env.py:929-1032: parse actions, timestep += 1,
 // components in list order, scenario_step, observations, masks, rewards, done.
 //
-// A replica is a workgroup of TWO wavefronts sharing the LDS record (NW = 2; the template parameter remains from the
-// one-wave schedule the kernel started with).
+// A replica is a workgroup of TWO wavefronts sharing the LDS record.
 //   both   record HBM -> LDS (alternate 16-byte units)  ||  wave 1 also: the next 128+ tempered MT19937 words ->
 //                                                        ||         the LDS draw window (rows fetched from HBM)
 //   wave 0 action decode, price-history decay          ||  wave 1 occupancy map
@@ -2960,7 +2959,7 @@ __device__ __forceinline__ void step_rewards_and_done(const aie::Ctx& c, uint8_t
   using namespace aie;
   float* const rew_log = close ? rew_log_claim(c.R, R_I32(c, o_rew_slot), R_I32(c, o_rew_epoch), c.R.E, c.P.n, c.tid == 0) : nullptr;
   if (emit) {
-    if (!(skip & 16)) compute_rewards(c, arena, rew_log);
+    if (!(skip & AIE_DEV_SKIP_REWARDS)) compute_rewards(c, arena, rew_log);
   } else if (rew_log && c.tid <= c.P.n) {
     const int n = c.P.n, i = c.tid;
     rew_log[(int64_t)c.e * (n + 2) + i] = i < n ? reinterpret_cast<const float*>(arena + c.R.a_rew_a)[(int64_t)c.e * n + i]
@@ -2978,7 +2977,7 @@ __device__ __forceinline__ void step_rewards_and_done(const aie::Ctx& c, uint8_t
 // configuration -- every dimension, record offset, component list, mask table and magic divisor folds into the
 // instruction stream (no scalar loads of parameters, fully unrolled per-agent loops) -- and only what depends on
 // the batch (R: E, arena offsets) is read at run time.  SPEC < 0: the generic kernel, P == R == *params.
-template <int NW, bool LOG, int SPEC = -1, bool TRACE = LOG>
+template <bool LOG, int SPEC = -1, bool TRACE = LOG>
 __device__ __forceinline__ void step_body(const aie_params* __restrict__ params, uint8_t* __restrict__ arena,
                                           const int32_t* __restrict__ act_a, const int32_t* __restrict__ act_p,
                                           uint8_t* lds, const NextActions& next) {
@@ -2989,13 +2988,12 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
   // time, and most arguments are not needed before the record is on its way; see the sampler for the opposite case)
   const aie_params& R = *params;
   const aie_params& P = aie_spec_params<SPEC>(params);
-  const int wid = NW == 1 ? 0 : uni((int)(threadIdx.x >> 6));
+  const int wid = uni((int)(threadIdx.x >> 6));
 #ifdef AIE_DEV  // phases switched off by aie_dev_set_skip_mask (the generic kernel with hooks and the traced instances)
   const int skip = (LOG || TRACE) ? R.dev_skip_mask : 0;
 #else
   const int skip = 0;
 #endif
-  static_assert(NW == 2, "a replica is a workgroup of two wavefronts");
   const int e_blk = replica_of_block((int)blockIdx.x, next.E);  // (the replica count travels as a kernel argument)
   if (next.e_hi > 0 && (e_blk < next.e_lo || e_blk >= next.e_hi)) return;  // (uniform over the workgroup, ahead of every barrier)
   if (LOG && next.mask && !next.mask[e_blk]) return;  // (likewise: a replica outside an aie_step_range mask, as in reset_body)
@@ -3044,7 +3042,7 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
     A.hist_dirty = 0;
     A.tax_dirty = false;
     int act_err = 0;
-    if (!(skip & (1 << 18))) act_err = decode_actions(c, A, act_a, act_p, arena);  // (c.act_p is LDS scratch)
+    if (!(skip & AIE_DEV_SKIP_ACTION_DECODE)) act_err = decode_actions(c, A, act_a, act_p, arena);  // (c.act_p is LDS scratch)
     else A.act = 0;
     if (TRACE && R.dev_trace && c.tid == 0) R.dev_trace[12 * blockIdx.x] = wall_clock64();
     if (TRACE && R.dev_trace && c.tid == 0) R.dev_trace[12 * blockIdx.x + 9] = wall_clock64();
@@ -3054,7 +3052,7 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
     // the decode: 22.9): 4096 workgroups start together, and what their first microseconds are short of is the memory
     // system's capacity for requests, not patience -- the loop's own pace spreads them)
     MT none;
-    load_record(c, arena, none, 0, NW, /*key_wave=*/-1);
+    load_record(c, arena, none, 0, 2, /*key_wave=*/-1);
     __syncthreads();  // (2) the record is in LDS
     if (TRACE && R.dev_trace && c.tid == 0) R.dev_trace[12 * blockIdx.x + 8] = wall_clock64();
     MTL ml{draw_w, 0, 0u, -AIE_MT_N, 0, 0u, 0u, 0, 0, 0, FAST ? reinterpret_cast<uint32_t*>(c.rec + P.o_mt) : gkey, draw_cap, FAST};
@@ -3071,25 +3069,25 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
 #ifdef AIE_FLAT_FULL  // (A/B builds: every step rewrites the vectors in full, as before round 7)
     const bool flat_in_place = false;
 #else
-    const bool flat_in_place = ph == 0 && uni(*R_I32(c, o_obs_valid)) != 0 && !(skip & (1 << 20));
+    const bool flat_in_place = ph == 0 && uni(*R_I32(c, o_obs_valid)) != 0 && !(skip & AIE_DEV_FLAT_FULL);
 #endif
     if (act_err && c.tid == 0) *R_I32(c, o_error_flags) |= act_err;
     bool cda_in_range = ph == 0;  // (the decay opens ContinuousDoubleAuction.component_step: with the component)
     if (ph != 0)
       for (int k = c_lo; k < c_hi; ++k) cda_in_range |= P.c.components[k] == AIE_COMP_CDA;
-    if (P.has_cda && !(skip & 1) && cda_in_range) cda_decay_price_history(c);
+    if (P.has_cda && !(skip & AIE_DEV_SKIP_COMPONENTS) && cda_in_range) cda_decay_price_history(c);
     __syncthreads();  // (3) occupancy map rebuilt
     if (c.tid == 0 && HEAD) *R_I32(c, o_timestep) += 1;
     if (c.ev && c.tid == 0) c.srcn[2] = 0;
     __builtin_amdgcn_s_setprio(3);  // the serial dynamics are the replica's critical path (at any batch size: round 6 A/B)
     if (TRACE && R.dev_trace && c.tid == 0) R.dev_trace[12 * blockIdx.x + 1] = wall_clock64();
-    if (!(skip & 1)) {
+    if (!(skip & AIE_DEV_SKIP_COMPONENTS)) {
       for (int k = c_lo; k < c_hi; ++k) {
         switch (P.c.components[k]) {
-          case AIE_COMP_BUILD: if (!(skip & 2048)) build_component_step(c, ml, A); break;
-          case AIE_COMP_CDA: if (!(skip & 4096)) cda_component_step(c, A); break;
-          case AIE_COMP_GATHER: if (!(skip & 8192)) gather_component_step(c, ml, A); break;
-          case AIE_COMP_TAX: if (!(skip & 16384)) tax_component_step(c, ml, A); break;
+          case AIE_COMP_BUILD: if (!(skip & AIE_DEV_SKIP_BUILD)) build_component_step(c, ml, A); break;
+          case AIE_COMP_CDA: if (!(skip & AIE_DEV_SKIP_CDA)) cda_component_step(c, A); break;
+          case AIE_COMP_GATHER: if (!(skip & AIE_DEV_SKIP_GATHER)) gather_component_step(c, ml, A); break;
+          case AIE_COMP_TAX: if (!(skip & AIE_DEV_SKIP_TAX)) tax_component_step(c, ml, A); break;
           case AIE_COMP_WEALTH_REDISTRIBUTION: wealth_component_step(c, A); break;
           default: break;
         }
@@ -3114,7 +3112,7 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
       if (c.tid < P.n) R_F64(c, o_tax_last_coin)[c.tid] = R_F64(c, o_inv_coin)[c.tid] + R_F64(c, o_esc_coin)[c.tid];
       AIE_WSYNC();
     }
-    if (!(skip & 8) && (EMIT || OBSERVE)) {
+    if (!(skip & AIE_DEV_SKIP_FLAT_AND_MASKS) && (EMIT || OBSERVE)) {
       // An annealed tax schedule caps the rates by the completions count the reset latches BEHIND its own observations
       // (reset_body: o_tax_last_completions, generate_masks' order): the episode's first step shows new curr_rates
       // although no tax day has passed.
@@ -3133,17 +3131,17 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
     }
     if (w0_tail_prio) __builtin_amdgcn_s_setprio(0);
     __syncthreads();  // (5)
-    if (!(skip & 32)) store_record_step(c, arena, 0, NW);
+    if (!(skip & AIE_DEV_SKIP_RECORD_STORE)) store_record_step(c, arena, 0, 2);
     if (TRACE && R.dev_trace && c.tid == 0) R.dev_trace[12 * blockIdx.x + 7] = wall_clock64();
   } else {
     // ---------------- second wave: generator, occupancy map, regeneration, map observations, masks ----------------
     MT m;
     mt_init(m, P);
     const int gpos = *reinterpret_cast<const int32_t*>(grec + P.o_mt_pos);
-    load_record(c, arena, m, 1, NW, /*key_wave=*/-1);
+    load_record(c, arena, m, 1, 2, /*key_wave=*/-1);
     // behind its share of the copy: the words the components will draw -> the LDS draw window (two or three rows of the
     // generator's state, fetched from HBM; the state itself follows while the components run)
-    if (skip & (1 << 16)) {}  // (development: the load phase without the draw window)
+    if (skip & AIE_DEV_SKIP_DRAW_WINDOW) {}  // (development: the load phase without the draw window)
     else if (FAST) draw_window_publish_fast(draw_w, draw_cap, (uint32_t)uni((int)gkey[0]), (uint32_t)uni((int)gkey[1]), (uint32_t)uni((int)gkey[2]), uni(gpos), c.tid);
     else draw_window_publish_from_hbm(draw_w, draw_cap, gkey, uni(gpos), c.tid);
 
@@ -3154,7 +3152,7 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
       for (int q = c.tid; q < P.MA; q += AIE_NT) const_cast<uint32_t*>(c.mtab)[q] = P.mask_test[q];
     }
     __syncthreads();  // (2)
-    if (!(skip & (1 << 17))) rebuild_locmap(c);
+    if (!(skip & AIE_DEV_SKIP_LOCMAP)) rebuild_locmap(c);
     __syncthreads();  // (3)
     // nothing to do until the components are done but the next step's random actions
     SrcList src;
@@ -3172,7 +3170,7 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
 #endif
     // (tried in round 6: all ten rows with the record burst and the window from the registers -- one dependent round trip
     // and 768 redundant bytes less, but 1.7 KB more in the burst every workgroup starts with: C2 23.0 -> 23.5 us)
-    if (!FAST && !(skip & (1 << 19))) {  // the generator's rows -> registers (re-read after the barrier if the components twisted the state)
+    if (!FAST && !(skip & AIE_DEV_SKIP_GENERATOR_ROWS)) {  // the generator's rows -> registers (re-read after the barrier if the components twisted the state)
 #pragma unroll
       for (int j = 0; j < 9; ++j) m.r[j] = gkey[64 * j + c.tid];
       m.r[9] = c.tid < 48 ? gkey[576 + c.tid] : 0u;
@@ -3208,32 +3206,32 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
     }
     m.pos = uni(*R_I32(c, o_mt_pos));
     if (REGEN) {
-      if (!(skip & 2)) scenario_step_regen(c, m, src);
+      if (!(skip & AIE_DEV_SKIP_REGEN)) scenario_step_regen(c, m, src);
       if (c.tid == 0) {
         *R_I32(c, o_mt_pos) = m.pos;
         if (FAST) R_U32(c, o_mt)[1] = m.fblk;
       }
-      if (!(skip & 32)) store_generator_rows(c, arena, m);  // (the rows' registers are free from here on)
+      if (!(skip & AIE_DEV_SKIP_RECORD_STORE)) store_generator_rows(c, arena, m);  // (the rows' registers are free from here on)
     }
     if (TRACE && R.dev_trace && c.tid == 0) R.dev_trace[12 * blockIdx.x + 6] = wall_clock64();
     AIE_WSYNC();
     // (the masks follow the map observations' rule: in place unless something outside the kernels touched the state)
-    const bool masks_all = OBSERVE || !uni(*R_I32(c, o_obs_valid)) || (skip & (4 | 32768)) != 0;
-    if (!(skip & 4) && (EMIT || OBSERVE)) {
+    const bool masks_all = OBSERVE || !uni(*R_I32(c, o_obs_valid)) || (skip & (AIE_DEV_SKIP_MAP_OBS | AIE_DEV_MAP_OBS_FULL)) != 0;
+    if (!(skip & AIE_DEV_SKIP_MAP_OBS) && (EMIT || OBSERVE)) {
       // the map observations of the previous step are still in the arena: update them in place,
       // unless something outside the kernels touched the state (obs_valid == 0; an AIE_STEP_OBSERVE launch: always)
-      if (uni(*R_I32(c, o_obs_valid)) && !(skip & 32768) && !OBSERVE) update_spatial_observations(c, arena);
+      if (uni(*R_I32(c, o_obs_valid)) && !(skip & AIE_DEV_MAP_OBS_FULL) && !OBSERVE) update_spatial_observations(c, arena);
       else write_spatial_observations(c, arena);
       if (c.tid == 0) *R_I32(c, o_obs_valid) = 1;
     } else if (!EMIT && !OBSERVE && !CLOSE_ONLY && c.tid == 0) {
       *R_I32(c, o_obs_valid) = 0;  // a partial step changed the state and wrote no observations: the launch that does starts over
     }
-    if (!(skip & 8) && (EMIT || OBSERVE)) write_action_masks(c, arena, /*all=*/masks_all);
+    if (!(skip & AIE_DEV_SKIP_FLAT_AND_MASKS) && (EMIT || OBSERVE)) write_action_masks(c, arena, /*all=*/masks_all);
     if (TRACE && R.dev_trace && c.tid == 0) R.dev_trace[12 * blockIdx.x + 11] = wall_clock64();
     if (REW_ON_W1 && (EMIT || CLOSE)) step_rewards_and_done(c, arena, next, skip, EMIT, CLOSE);
     __builtin_amdgcn_s_setprio(0);
     __syncthreads();  // (5)
-    if (!(skip & 32)) store_record_step(c, arena, 1, NW);
+    if (!(skip & AIE_DEV_SKIP_RECORD_STORE)) store_record_step(c, arena, 1, 2);
   }
 }
 
@@ -3242,7 +3240,7 @@ extern "C" __global__ void __launch_bounds__(2 * AIE_NT) __attribute__((amdgpu_w
 aie_step_kernel(const aie_params* __restrict__ params, uint8_t* __restrict__ arena,
                 const int32_t* __restrict__ act_a, const int32_t* __restrict__ act_p, NextActions next) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-  step_body<2, false>(params, arena, act_a, act_p, lds, next);
+  step_body<false>(params, arena, act_a, act_p, lds, next);
 }
 // the same kernel for records whose LDS footprint keeps a CU at 12 workgroups or fewer anyway (aie_capi.hip:
 // aie_step): 6 waves per SIMD buy 80 VGPRs, i.e. no scratch traffic
@@ -3250,14 +3248,14 @@ extern "C" __global__ void __launch_bounds__(2 * AIE_NT) __attribute__((amdgpu_w
 aie_step_kernel_r6(const aie_params* __restrict__ params, uint8_t* __restrict__ arena,
                    const int32_t* __restrict__ act_a, const int32_t* __restrict__ act_p, NextActions next) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-  step_body<2, false>(params, arena, act_a, act_p, lds, next);
+  step_body<false>(params, arena, act_a, act_p, lds, next);
 }
 // the same step for environments with dense-log replicas (aie_config.dense_log_replicas > 0): records AIE_EV_* rows
 extern "C" __global__ void __launch_bounds__(2 * AIE_NT) __attribute__((amdgpu_waves_per_eu(8, 8)))
 aie_step_kernel_log(const aie_params* __restrict__ params, uint8_t* __restrict__ arena,
                     const int32_t* __restrict__ act_a, const int32_t* __restrict__ act_p, NextActions next) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-  step_body<2, true>(params, arena, act_a, act_p, lds, next);
+  step_body<true>(params, arena, act_a, act_p, lds, next);
 }
 // compile-time instances for the configurations listed in ai-economist_amd/_specs.py (BASELINE configs[1], [2], ...)
 #define AIE_SPEC_WAVES(S) aie_spec_image<S>::waves
@@ -3267,7 +3265,7 @@ __attribute__((amdgpu_waves_per_eu(AIE_SPEC_WAVES(SPEC), AIE_SPEC_WAVES(SPEC))))
 aie_step_kernel_spec(const aie_params* __restrict__ params, uint8_t* __restrict__ arena,
                      const int32_t* __restrict__ act_a, const int32_t* __restrict__ act_p, NextActions next) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-  step_body<2, false, SPEC>(params, arena, act_a, act_p, lds, next);
+  step_body<false, SPEC>(params, arena, act_a, act_p, lds, next);
 }
 #ifdef AIE_DEV
 // development: the compile-time instances with per-workgroup clock stamps (tools/block_trace.py, aie_dev_set_trace)
@@ -3277,7 +3275,7 @@ __attribute__((amdgpu_waves_per_eu(aie_spec_image<SPEC>::waves, aie_spec_image<S
 aie_step_kernel_spec_trace(const aie_params* __restrict__ params, uint8_t* __restrict__ arena,
                            const int32_t* __restrict__ act_a, const int32_t* __restrict__ act_p, NextActions next) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-  step_body<2, false, SPEC, true>(params, arena, act_a, act_p, lds, next);
+  step_body<false, SPEC, true>(params, arena, act_a, act_p, lds, next);
 }
 #endif
 #endif  // !AIE_JIT
@@ -4456,6 +4454,18 @@ __device__ __forceinline__ void sampler_item_run(const SamplerItem& d, int lane,
     }
   }
 }
+// development (-DAIE_DEV build): AIE_SAMPLER_DEV_SKIP travels above bit 8 of the sampler kernels' wave-count argument and
+// switches parts of them off (AIE_SAMPLER_SKIP_*, aie_layout.h: what is the launch made of?).  Takes the bits out of the
+// argument and returns them; the shipping build's argument carries none (a compile-time 0: every test of it folds).
+#ifdef AIE_DEV
+__device__ __forceinline__ int sampler_dev_skip(int& wpr_log2) {
+  const int bits = wpr_log2 >> 8;
+  wpr_log2 &= 255;
+  return bits;
+}
+#else
+__device__ constexpr int sampler_dev_skip(int&) { return 0; }
+#endif
 #define AIE_SAMPLER_GROUP 4  // items whose loads a wave has in flight together
 template <bool LOGP>
 __global__ void __launch_bounds__(256)
@@ -4463,13 +4473,8 @@ aie_sample_policy_actions_kernel(const aie_sampler_args S, uint8_t* __restrict__
                                  const float* __restrict__ logits_p, uint64_t seed, int64_t env_offset,
                                  int32_t* __restrict__ act_a, int32_t* __restrict__ act_p, int wpr_log2, const SamplerLogp<LOGP> LP) {
   const int lane = (int)threadIdx.x & 63, wave = aie::uni((int)threadIdx.x >> 6);
-#ifdef AIE_DEV  // development: bits 8.. of the argument switch parts of the kernel off (what is the launch made of?)
-  const int dev_skip = wpr_log2 >> 8;
-  wpr_log2 &= 255;
-  if (dev_skip & 8) return;
-#else
-  constexpr int dev_skip = 0;
-#endif
+  const int dev_skip = sampler_dev_skip(wpr_log2);
+  if (dev_skip & AIE_SAMPLER_SKIP_ALL) return;
   const int wpr = 1 << wpr_log2;
   const int e = (int)blockIdx.x * (4 >> wpr_log2) + (wave >> wpr_log2), w_in = wave & (wpr - 1);
   if (e < S.E) {
@@ -4480,7 +4485,7 @@ aie_sample_policy_actions_kernel(const aie_sampler_args S, uint8_t* __restrict__
     // the kernel waits on memory, not on arithmetic (a wave's items one after the other: 18 us however few instructions):
     // the draw index and a whole group of items' entries are requested before anything is computed
     const int32_t* tfield = reinterpret_cast<const int32_t*>(arena + S.t_off + (int64_t)e * S.rec_bytes);
-    const int32_t t_lane = (dev_skip & 2) ? 0 : *tfield;
+    const int32_t t_lane = (dev_skip & AIE_SAMPLER_SKIP_DRAW_INDEX) ? 0 : *tfield;
     uint32_t base = 0u;
     for (int it0 = w_in; it0 < items; it0 += AIE_SAMPLER_GROUP * wpr) {
       SamplerItem d[AIE_SAMPLER_GROUP];
@@ -4490,7 +4495,7 @@ aie_sample_policy_actions_kernel(const aie_sampler_args S, uint8_t* __restrict__
         const int it = it0 + g * wpr;
         if (it < items) {
           d[g] = sampler_item(S, A, Q, it);
-          if (dev_skip & 1) {
+          if (dev_skip & AIE_SAMPLER_SKIP_LOADS) {
             x0[g] = (float)(lane & 7);
             mv0[g] = 1.0f;
           } else {
@@ -4502,7 +4507,7 @@ aie_sample_policy_actions_kernel(const aie_sampler_args S, uint8_t* __restrict__
 #pragma unroll
       for (int g = 0; g < AIE_SAMPLER_GROUP; ++g)
         if (it0 + g * wpr < items) {
-          if (dev_skip & 4) {
+          if (dev_skip & AIE_SAMPLER_SKIP_ARITHMETIC) {
             if (x0[g] + mv0[g] == 12345.0f) d[g].dst[0] = 1;
           } else {
             float* lp = nullptr;
@@ -4516,7 +4521,7 @@ aie_sample_policy_actions_kernel(const aie_sampler_args S, uint8_t* __restrict__
     }
   }
   __syncthreads();  // every wave of the replica has read the draw index: its first wave advances it
-  if (e < S.E && w_in == 0 && lane == 0 && !(dev_skip & 2)) {
+  if (e < S.E && w_in == 0 && lane == 0 && !(dev_skip & AIE_SAMPLER_SKIP_DRAW_INDEX)) {
     int32_t* tfield = reinterpret_cast<int32_t*>(arena + S.t_off + (int64_t)e * S.rec_bytes);
     *tfield = *tfield + 1;
   }
@@ -4647,13 +4652,8 @@ aie_sample_policy_fast_kernel(const aie_sampler_args S, uint8_t* __restrict__ ar
     lp_a = LP.a;
     lp_p = LP.p;
   }
-#ifdef AIE_DEV  // development: bits 8.. of the argument switch parts of the kernel off (what is the launch made of?)
-  const int dev_skip = wpr_log2 >> 8;
-  wpr_log2 &= 255;
-  if (dev_skip & 8) return;
-#else
-  constexpr int dev_skip = 0;
-#endif
+  const int dev_skip = sampler_dev_skip(wpr_log2);
+  if (dev_skip & AIE_SAMPLER_SKIP_ALL) return;
   const int wpr = 1 << wpr_log2;
   const int e = (int)blockIdx.x * (4 >> wpr_log2) + (wave >> wpr_log2), w_in = wave & (wpr - 1);
   if (e < S.E) {
@@ -4666,7 +4666,7 @@ aie_sample_policy_fast_kernel(const aie_sampler_args S, uint8_t* __restrict__ ar
     const int per_env = S.agents.rows + S.planner.rows;
     // the draw index and a whole turn's entries are requested before anything is computed
     const int32_t* tfield = reinterpret_cast<const int32_t*>(arena + S.t_off + (int64_t)e * S.rec_bytes);
-    const int32_t t_lane = (dev_skip & 2) ? 0 : *tfield;
+    const int32_t t_lane = (dev_skip & AIE_SAMPLER_SKIP_DRAW_INDEX) ? 0 : *tfield;
     // (per turn: two agent items and two planner items of this wave, all their loads ahead of the arithmetic)
     uint32_t base = 0u;
     for (int it_ = w_in; it_ < A.items || it_ < Q.items; it_ += 2 * wpr) {
@@ -4676,7 +4676,7 @@ aie_sample_policy_fast_kernel(const aie_sampler_args S, uint8_t* __restrict__ ar
       float xa[2], ma[2], xq[2], mq[2];
 #pragma unroll
       for (int g = 0; g < 2; ++g) {
-        if (dev_skip & 1) {
+        if (dev_skip & AIE_SAMPLER_SKIP_LOADS) {
           xa[g] = xq[g] = (float)(lane & 7);
           ma[g] = mq[g] = 1.0f;
         } else {
@@ -4685,7 +4685,7 @@ aie_sample_policy_fast_kernel(const aie_sampler_args S, uint8_t* __restrict__ ar
         }
       }
       if (it_ == w_in) base = aie_counter_rng(seed, (uint64_t)(env_offset + e), (uint64_t)(int64_t)aie::uni(t_lane), (uint64_t)per_env);
-      if (dev_skip & 4) {
+      if (dev_skip & AIE_SAMPLER_SKIP_ARITHMETIC) {
         if (xa[0] + ma[0] + xa[1] + ma[1] + xq[0] + mq[0] + xq[1] + mq[1] == 12345.0f) A.dst[0] = 1;
         continue;
       }
@@ -4697,7 +4697,7 @@ aie_sample_policy_fast_kernel(const aie_sampler_args S, uint8_t* __restrict__ ar
     }
   }
   __syncthreads();  // every wave of the replica has read the draw index: its first wave advances it
-  if (e < S.E && w_in == 0 && lane == 0 && !(dev_skip & 2)) {
+  if (e < S.E && w_in == 0 && lane == 0 && !(dev_skip & AIE_SAMPLER_SKIP_DRAW_INDEX)) {
     int32_t* tfield = reinterpret_cast<int32_t*>(arena + S.t_off + (int64_t)e * S.rec_bytes);
     *tfield = *tfield + 1;
   }
@@ -5048,7 +5048,7 @@ __attribute__((amdgpu_waves_per_eu(aie_spec_image<0>::waves, aie_spec_image<0>::
 aie_jit_step(const aie_params* __restrict__ params, uint8_t* __restrict__ arena,
              const int32_t* __restrict__ act_a, const int32_t* __restrict__ act_p, NextActions next) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-  step_body<2, false, 0>(params, arena, act_a, act_p, lds, next);
+  step_body<false, 0>(params, arena, act_a, act_p, lds, next);
 }
 extern "C" __global__ void __launch_bounds__(LG_NW * AIE_NT)
 aie_jit_reset(const aie_params* __restrict__ params, uint8_t* __restrict__ arena,

@@ -21,8 +21,7 @@
 // weighting them by w[s,f] at the end -- a float64 reordering, ~1e-16 relative.
 #pragma clang fp contract(off)
 
-// ablations (tools/covid_ablate.py, -DAIE_DEV build): bits of aie_dev_set_skip_mask -- 1 today's history byte store,
-// 2 history byte loads (constants instead), 4 observation stores, 8 the per-state episode sums, 16 state row stores
+// ablations (tools/covid_ablate.py, -DAIE_DEV build): the AIE_CV_SKIP_* bits of aie_dev_set_skip_mask (aie_layout.h)
 #ifdef AIE_DEV
 #define CV_SKIP(P, bit) (((P).dev_skip_mask & (bit)) != 0)
 #else
@@ -359,7 +358,7 @@ __device__ __forceinline__ void cv_window_tail(const aie_params& P, uint8_t* __r
   // the long history: a replica on event lists gets a state's 16 bytes when their chunk is complete (from the ring); a
   // streaming one every day (51 one-byte stores spread over 816 bytes); the step that switches writes the open chunk's
   // days so far in one piece
-  if (!CV_SKIP(P, 1)) {
+  if (!CV_SKIP(P, AIE_CV_SKIP_HISTORY_STORE)) {
     if (dense && !flush_now) {
       if (on) *cv_hist_at(P, hist, s, L + t) = (uint8_t)level;
     } else if (flush_now) {
@@ -563,7 +562,7 @@ __device__ __forceinline__ void cv_step_body(const aie_params* __restrict__ para
   // ---- ControlUSStateOpenCloseStatus.component_step :180-221 ----
   int act = act_a ? act_a[(int64_t)e * n + sl] : 0;
   if (V.replay_policies) act = (arena + P.a_cv_replay_a)[(int64_t)(t - 1) * 64 + sl];  // :181-186: yesterday's recorded level
-  const int prev_level = CV_SKIP(P, 2) ? 1 : *cv_ring_at(P, rec, sl, L + t - 1);
+  const int prev_level = CV_SKIP(P, AIE_CV_SKIP_HISTORY_LOADS) ? 1 : *cv_ring_at(P, rec, sl, L + t - 1);
   if (act < 0 || act > NL) act = 0;
   CvLane a;
   a.level = act == 0 ? prev_level : act;
@@ -590,7 +589,7 @@ __device__ __forceinline__ void cv_step_body(const aie_params* __restrict__ para
   // ---- sir_step :1477-1515 ----
   const double pop = K[AIE_CV_K_POP * 64 + sl];
   {
-    const int beta_level = CV_SKIP(P, 2) ? 1 : (V.beta_delay <= 31 ? *cv_ring_at(P, rec, sl, L + t - V.beta_delay)
+    const int beta_level = CV_SKIP(P, AIE_CV_SKIP_HISTORY_LOADS) ? 1 : (V.beta_delay <= 31 ? *cv_ring_at(P, rec, sl, L + t - V.beta_delay)
                                                                     : *cv_hist_at(P, hist, sl, L + t - V.beta_delay));  // days before the data: level 1
     const float beta = (float)(K[AIE_CV_K_BETA_INTERCEPT * 64 + sl] + K[AIE_CV_K_BETA_SLOPE * 64 + sl] * (double)beta_level);
     const float s_eps = S1 + 1e-10f;
@@ -644,7 +643,7 @@ __device__ __forceinline__ void cv_step_body(const aie_params* __restrict__ para
       // (history days <= L are the pre-episode days every replica shares: read from the shared table -- one
       // cache-resident 51-byte row per day -- instead of this replica's own copy while t <= L)
       int lev_t, lev_tm1;
-      if (CV_SKIP(P, 2)) lev_t = lev_tm1 = 1;
+      if (CV_SKIP(P, AIE_CV_SKIP_HISTORY_LOADS)) lev_t = lev_tm1 = 1;
       else if (t <= L) {
         const uint8_t* h0 = arena + P.a_cv_hist0;
         lev_t = h0[t * n + sl];
@@ -700,7 +699,7 @@ __device__ __forceinline__ void cv_step_body(const aie_params* __restrict__ para
   // sums stream -- gets today's byte every step only when those sums run (51 one-byte stores spread over 816 bytes:
   // seven partly written lines a step); the recurrence writes a state's 16 bytes once their chunk is complete
   *cv_ring_at(P, rec, s, L + t) = on ? (uint8_t)a.level : (uint8_t)0;
-  if (RECUR && !CV_SKIP(P, 1) && ((L + t) & 15) == 15) {  // (window sums: the tail writes the long history)
+  if (RECUR && !CV_SKIP(P, AIE_CV_SKIP_HISTORY_STORE) && ((L + t) & 15) == 15) {  // (window sums: the tail writes the long history)
     uint32_t w[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int j = 0; j < 15; ++j) w[j >> 2] |= (uint32_t)*cv_ring_at(P, rec, sl, L + t - 15 + j) << (8 * (j & 3));
@@ -710,7 +709,7 @@ __device__ __forceinline__ void cv_step_body(const aie_params* __restrict__ para
   }
   if (on) {
     cool[s] = a.cooldown;
-    if (!CV_SKIP(P, 16)) {
+    if (!CV_SKIP(P, AIE_CV_SKIP_STATE_ROWS)) {
       st[AIE_CV_ST_S * PT + s] = a.S;
       st[AIE_CV_ST_I * PT + s] = a.I;
       st[AIE_CV_ST_R * PT + s] = a.R;
@@ -721,7 +720,7 @@ __device__ __forceinline__ void cv_step_body(const aie_params* __restrict__ para
       st[AIE_CV_ST_SUBSIDY * PT + s] = a.subsidy;
     }
     // per-state sums over the days of the episode, for scenario_metrics :1613-1687
-    if (!CV_SKIP(P, 8)) {
+    if (!CV_SKIP(P, AIE_CV_SKIP_EPISODE_SUMS)) {
       sums[AIE_CV_SUM_UNEMPLOYED * PT + s] = sum_u0 + (double)a.U;
       sums[AIE_CV_SUM_STRINGENCY * PT + s] = sum_s0 + (double)a.level;
       sums[AIE_CV_SUM_PRODUCTIVITY * PT + s] = sum_p0 + (double)a.prod;
@@ -779,7 +778,7 @@ __device__ __forceinline__ void cv_step_body(const aie_params* __restrict__ para
   }
 
   // ---- observations + masks for the new timestep ----
-  if (!CV_SKIP(P, 4)) cv_write_observations(P, arena, e, s, t, a, sub_level, lag_level);
+  if (!CV_SKIP(P, AIE_CV_SKIP_OBS)) cv_write_observations(P, arena, e, s, t, a, sub_level, lag_level);
   if (next.a || next.p) {  // aie_step_sample_next: the uniform random policy's draw for the next step, one lane per slot
     const int per_env = P.n * P.act_a_width + P.act_p_width;
     if (next.masked) {

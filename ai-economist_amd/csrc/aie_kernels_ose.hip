@@ -22,8 +22,7 @@
   do {                                                                                                         \
     if ((c).R.dev_trace && (c).tid == 0) (c).R.dev_trace[12 * blockIdx.x + (k)] = wall_clock64();              \
   } while (0)
-// ablations (tools/ose_ablate.py): bits of aie_dev_set_skip_mask -- 1 flat rows, 2 mask rows, 4 metrics atomics,
-// 8 the small observation tensors, 16 record store, 32 record load (the LDS image is then garbage: timing only)
+// ablations (tools/ose_ablate.py): the AIE_OSE_SKIP_* bits of aie_dev_set_skip_mask (aie_layout.h)
 #define OSE_SKIP(c, bit) (((c).R.dev_skip_mask & (bit)) != 0)
 #else
 #define OSE_STAMP(c, k) do { } while (0)
@@ -208,7 +207,7 @@ __device__ __forceinline__ void ose_load_record(const Ctx& c, const uint8_t* __r
   // HBM reads mixed into the launch's store stream cost about twice their byte share (tools/phase_overlap.hip).
   const bool dead = c.P.has_tax && c.P.c.tax_period == 1;
   const int dead_lo = (c.P.o_tax_last_income + 15) >> 4, dead_hi = (c.P.o_tax_last_marginal_rate + 8 * c.P.n) >> 4;
-  const int nq_eff = OSE_SKIP(c, 32) ? 0 : nq;
+  const int nq_eff = OSE_SKIP(c, AIE_OSE_SKIP_RECORD_LOAD) ? 0 : nq;
 #define OSE_LIVE(k) (q0 + (k) * OSE_NT < nq_eff && !(dead && q0 + (k) * OSE_NT >= dead_lo && q0 + (k) * OSE_NT < dead_hi))
 #define OSE_LD(k) if (OSE_LIVE(k)) v##k = src[q0 + (k) * OSE_NT];
 #define OSE_ST(k) if (OSE_LIVE(k)) dst[q0 + (k) * OSE_NT] = v##k;
@@ -313,7 +312,7 @@ __device__ __forceinline__ void ose_tax_component_step(const Ctx& c, const OseSc
           if (income >= c.R.c.tax_bracket_cutoffs[b] && (b + 1 == c.P.NB || income < c.R.c.tax_bracket_cutoffs[b + 1])) { bin = b; break; }
       if (k) { L.met_inc1 += income > 0 ? income : 0.0; L.met_paid1 += eff; bin1 = bin; }
       else { L.met_inc0 += income > 0 ? income : 0.0; L.met_paid0 += eff; bin0 = bin; }
-      if (!OSE_SKIP(c, 4)) {
+      if (!OSE_SKIP(c, AIE_OSE_SKIP_METRICS)) {
         reinterpret_cast<double*>(c.met + c.P.mo_tax_income)[i] = k ? L.met_inc1 : L.met_inc0;
         reinterpret_cast<double*>(c.met + c.P.mo_tax_paid)[i] = k ? L.met_paid1 : L.met_paid0;
       }
@@ -324,7 +323,7 @@ __device__ __forceinline__ void ose_tax_component_step(const Ctx& c, const OseSc
         const int cnt = __popcll(__ballot(bin0 == b)) + __popcll(__ballot(bin1 == b));
         mine = c.tid == b ? cnt : mine;
       }
-      if (c.tid < c.P.NB && mine && !OSE_SKIP(c, 4)) atomicAdd(reinterpret_cast<int32_t*>(c.met + c.P.mo_tax_occ) + c.tid, mine);
+      if (c.tid < c.P.NB && mine && !OSE_SKIP(c, AIE_OSE_SKIP_METRICS)) atomicAdd(reinterpret_cast<int32_t*>(c.met + c.P.mo_tax_occ) + c.tid, mine);
     }
     if (c.tid < c.P.NB) unsafeAtomicAdd(reinterpret_cast<double*>(c.met + c.P.mo_tax_sched) + c.tid, tax_rate(c, c.tid));
     if (c.ev && c.tid < c.P.NB) {  // the day's schedule: AIE_EV_TAX_BRACKET rows first
@@ -560,7 +559,7 @@ __device__ __forceinline__ void ose_store_agent_masks(const Ctx& c, const OseScr
   __syncthreads();  // the row template goes through the agent template area
   for (int q = c.tid; q < P.MA; q += OSE_NT) s.tmpl_a[q] = (q == 0 || P.n_sub_a == 0) ? 1.0f : on;
   __syncthreads();
-  if (!OSE_SKIP(c, 2)) ose_store_rows(g, P.n, P.MA, s.tmpl_a, c.tid, -1, nullptr, -1, nullptr);
+  if (!OSE_SKIP(c, AIE_OSE_SKIP_MASK_ROWS)) ose_store_rows(g, P.n, P.MA, s.tmpl_a, c.tid, -1, nullptr, -1, nullptr);
   __syncthreads();
 }
 
@@ -622,10 +621,10 @@ __device__ __forceinline__ void ose_write_observations(const Ctx& c, const OseSc
       OSE_MY_AGENTS(k, i, n) s.part[i] = (double)L.skobs(k);  // (float)(skill / pmsm), simple_labor.py:128-134
       __syncthreads();
     }
-    if (!OSE_SKIP(c, 1)) ose_store_rows(g, n, P.FA, s.tmpl_a, tid, i_mr, s.tmp, i_sk, s.part);
+    if (!OSE_SKIP(c, AIE_OSE_SKIP_FLAT_ROWS)) ose_store_rows(g, n, P.FA, s.tmpl_a, tid, i_mr, s.tmp, i_sk, s.part);
     float* gt = reinterpret_cast<float*>(arena + c.R.a_obs_a_time) + (int64_t)c.e * n;
-    if (!OSE_SKIP(c, 8)) for (int i = tid; i < n; i += OSE_NT) gt[i] = tval;
-    if (P.FPA && !OSE_SKIP(c, 8)) {
+    if (!OSE_SKIP(c, AIE_OSE_SKIP_SMALL_OBS)) for (int i = tid; i < n; i += OSE_NT) gt[i] = tval;
+    if (P.FPA && !OSE_SKIP(c, AIE_OSE_SKIP_SMALL_OBS)) {
       float* gp = reinterpret_cast<float*>(arena + c.R.a_obs_p_agents) + (int64_t)c.e * n * P.FPA;
       for (int i = tid; i < n; i += OSE_NT) {
         float* q = gp + i * P.FPA + P.fpa_tax;
@@ -634,7 +633,7 @@ __device__ __forceinline__ void ose_write_observations(const Ctx& c, const OseSc
         q[AIE_FPA_TAX_LAST_MARGINAL_RATE] = (float)R_F64(c, o_tax_last_marginal_rate)[i];
       }
     }
-    if (!OSE_SKIP(c, 8)) stream_out(s.tmpl_p, reinterpret_cast<float*>(arena + c.R.a_obs_p_flat) + (int64_t)c.e * P.FP, P.FP, tid);
+    if (!OSE_SKIP(c, AIE_OSE_SKIP_SMALL_OBS)) stream_out(s.tmpl_p, reinterpret_cast<float*>(arena + c.R.a_obs_p_flat) + (int64_t)c.e * P.FP, P.FP, tid);
   }
   OSE_STAMP(c, 6);
   // ---- masks ----
@@ -682,7 +681,7 @@ __device__ __forceinline__ void ose_store_record(const Ctx& c, uint8_t* __restri
   uint4* dst = reinterpret_cast<uint4*>(g);
   const uint4* src = reinterpret_cast<const uint4*>(c.rec);
   const int nq = rec_lds_bytes(c.P) >> 4;
-  if (OSE_SKIP(c, 16)) return;
+  if (OSE_SKIP(c, AIE_OSE_SKIP_RECORD_STORE)) return;
   for (int q = c.tid; q < nq; q += OSE_NT) dst[q] = src[q];
 }
 

@@ -52,6 +52,53 @@ enum {
   AIE_N_SUB_SLOTS = 8
 };
 
+/* ---- development switches (-DAIE_DEV build only: the shipping kernels compile every test of them to "off") ----
+ * aie_params.dev_skip_mask, set by aie_dev_set_skip_mask, switches parts of the scenario's step kernel off so that a
+ * launch can be timed without them; the results are then wrong by design.  One bit set per kernel family, named here
+ * once: the kernels test these names and tools/devlib.py reads them out of this file.
+ *
+ * Gather-trade-build (step_body: the full-featured kernel and the traced instances). */
+#define AIE_DEV_SKIP_COMPONENTS (1 << 0)       /* every component step, and the CDA price-history decay ahead of them */
+#define AIE_DEV_SKIP_REGEN (1 << 1)            /* the resource regeneration (scenario_step_regen) */
+#define AIE_DEV_SKIP_MAP_OBS (1 << 2)          /* the map observations; the masks are then rewritten in full */
+#define AIE_DEV_SKIP_FLAT_AND_MASKS (1 << 3)   /* BOTH the flat observation vectors (first wave) and the mask writer (second wave) */
+#define AIE_DEV_SKIP_REWARDS (1 << 4)          /* compute_rewards (the reward log's slot and `done` are still written) */
+#define AIE_DEV_SKIP_RECORD_STORE (1 << 5)     /* record LDS -> HBM of both waves, and the generator's rows */
+#define AIE_DEV_SKIP_FLAT_STAGE_A (1 << 6)     /* flat vectors: the per-(commodity, price) sums and the per-agent scalars */
+#define AIE_DEV_SKIP_FLAT_CDA (1 << 7)         /* flat vectors: the CDA fill (market rates, order counts, price history) */
+#define AIE_DEV_SKIP_FLAT_TAX (1 << 8)         /* flat vectors: the tax fill (rates, calendar, sorted incomes) */
+#define AIE_DEV_SKIP_MASKS (1 << 9)            /* the action masks alone (write_action_masks returns at once) */
+#define AIE_DEV_SKIP_PLANNER_COPY_OUT (1 << 10) /* full flat rewrite: the planner's staged vectors LDS -> HBM */
+#define AIE_DEV_SKIP_BUILD (1 << 11)           /* the Build component */
+#define AIE_DEV_SKIP_CDA (1 << 12)             /* the ContinuousDoubleAuction component (its decay still runs) */
+#define AIE_DEV_SKIP_GATHER (1 << 13)          /* the Gather component */
+#define AIE_DEV_SKIP_TAX (1 << 14)             /* the PeriodicBracketTax component */
+#define AIE_DEV_MAP_OBS_FULL (1 << 15)         /* no skip: map observations and masks rewritten in full, not in place */
+#define AIE_DEV_SKIP_DRAW_WINDOW (1 << 16)     /* second wave: publishing the components' draw window */
+#define AIE_DEV_SKIP_LOCMAP (1 << 17)          /* second wave: the occupancy map (rebuild_locmap) */
+#define AIE_DEV_SKIP_ACTION_DECODE (1 << 18)   /* first wave: decode_actions (every agent then does nothing) */
+#define AIE_DEV_SKIP_GENERATOR_ROWS (1 << 19)  /* second wave: the MT19937 rows HBM -> registers */
+#define AIE_DEV_FLAT_FULL (1 << 20)            /* no skip: flat vectors rewritten in full, not updated in place */
+/* One-step-economy (aie_kernels_ose.hip). */
+#define AIE_OSE_SKIP_FLAT_ROWS (1 << 0)        /* the agents' flat observation rows */
+#define AIE_OSE_SKIP_MASK_ROWS (1 << 1)        /* the agents' mask rows */
+#define AIE_OSE_SKIP_METRICS (1 << 2)          /* the metrics block's atomics */
+#define AIE_OSE_SKIP_SMALL_OBS (1 << 3)        /* the small observation tensors (time, planner's per-agent and flat rows) */
+#define AIE_OSE_SKIP_RECORD_STORE (1 << 4)     /* record LDS -> HBM */
+#define AIE_OSE_SKIP_RECORD_LOAD (1 << 5)      /* record HBM -> LDS (the image is then garbage: timing only) */
+/* COVID (aie_kernels_covid.hip). */
+#define AIE_CV_SKIP_HISTORY_STORE (1 << 0)     /* today's stringency-history byte (and the long history's tail write) */
+#define AIE_CV_SKIP_HISTORY_LOADS (1 << 1)     /* the history byte loads (a constant level instead) */
+#define AIE_CV_SKIP_OBS (1 << 2)               /* the observation stores */
+#define AIE_CV_SKIP_EPISODE_SUMS (1 << 3)      /* the per-state episode sums (read-modify-write) */
+#define AIE_CV_SKIP_STATE_ROWS (1 << 4)        /* the state row stores */
+/* Policy sampler: not in dev_skip_mask -- AIE_SAMPLER_DEV_SKIP in the environment, which travels above bit 8 of the
+ * kernels' wave-count argument (sampler_dev_skip). */
+#define AIE_SAMPLER_SKIP_LOADS (1 << 0)        /* the logit / mask entry loads (made-up values instead) */
+#define AIE_SAMPLER_SKIP_DRAW_INDEX (1 << 1)   /* reading and advancing the replica's draw index */
+#define AIE_SAMPLER_SKIP_ARITHMETIC (1 << 2)   /* everything behind the loads */
+#define AIE_SAMPLER_SKIP_ALL (1 << 3)          /* an empty kernel */
+
 /* Everything a kernel needs, passed BY VALUE as the kernel argument. */
 typedef struct aie_params {
   aie_config c;
@@ -132,8 +179,6 @@ typedef struct aie_params {
    * q < 2^32 / d (d >= 2); see aie__magic() */
   uint32_t mg_WV2, mg_WV, mg_MA, mg_FA, mg_P, mg_2P, mg_taxA, mg_HW, mg_W, mg_sub_p, mg_sub_p_dim;
 
-  /* development only: phases of the step kernel to skip when profiling
-   * (tools/phase_profile.py); always 0 in normal operation */
   /* per-replica episode accumulators behind env.metrics (component get_metrics): touched only
    * when a trade executes / on tax days, so they live outside the streamed record */
   /* regen_halfwidth > 0 (dynamic_layout.py:446-463): the regeneration probability of a source block
@@ -195,7 +240,7 @@ typedef struct aie_params {
   /* flattened agent action mask, element m: allowed iff ((mask_bits >> sh) & msk) >= thr with
    * sh = test & 31, msk = (test >> 8) & 0xff, thr = test >> 16 (mask_bits: write_action_masks) */
   uint32_t mask_test[AIE_MAX_MASK];
-  int32_t dev_skip_mask;
+  int32_t dev_skip_mask; /* development: AIE_DEV_SKIP_* / AIE_OSE_SKIP_* / AIE_CV_SKIP_* bits (above); 0 in normal operation */
   uint64_t* dev_trace;   /* development: 8 clock stamps per workgroup (start, components.., regen, end), or NULL */
   /* aie_set_reward_log: the caller's reward log, f32 [rew_slots][E][n + 2] = agents' rewards, the planner's reward, done --
    * or NULL.  In the device-side block (not a kernel argument) so that a launch captured in a hipGraph sees a later

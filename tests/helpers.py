@@ -88,6 +88,17 @@ def dev_library():
             os.environ["AIE_DEV_LIB"] = old
 
 
+def dev_switches():
+    """The development switches by name ({"AIE_DEV_SKIP_REGEN": 2, ...}): tools/devlib.py reads them out of
+    csrc/aie_layout.h."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("devlib", os.path.join(ROOT, "tools", "devlib.py"))
+    devlib = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(devlib)
+    return devlib.switches()
+
+
 def state_from_golden(g, prefix, t=None):
     out = {}
     for k, v in g.items():

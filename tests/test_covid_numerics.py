@@ -11,7 +11,6 @@ CPU tests: the band holds the live reference's recorded days (tests/golden/c4_co
 GPU tests: rollouts, eta near 1 and at 1, reward normalisation and health-priority edges, and injected states
 (S = 0, S below the day's vaccines, I = 0, no new deaths, a negative planner CRRA input, extreme filter responses).
 Run with -s for the measured ulps, band widths and deviations."""
-import ctypes
 import os
 import sys
 
@@ -239,9 +238,6 @@ def _dev_math(fn, x, y=None):
     from ai_economist_amd import _native
 
     lib = _native.lib(dev=True)
-    vp = ctypes.c_void_p
-    lib.aie_test_glibc_math.restype = ctypes.c_int
-    lib.aie_test_glibc_math.argtypes = [ctypes.c_int, vp, vp, vp, ctypes.c_int64, vp]
     tx = torch.as_tensor(np.asarray(x, np.float64), device="cuda:0")
     ty = torch.as_tensor(np.asarray(y, np.float64), device="cuda:0") if y is not None else None
     out = torch.empty_like(tx)

@@ -4,13 +4,12 @@ calendar always, a histogram column when the auction touched it, the tax block's
 the two steps of a period that change them.  Everything here compares the observation tensors, rewards and done with the
 CPU oracle (or with a twin that takes the full path) after EVERY step, bit for bit: an entry the in-place path forgets
 keeps the previous step's value, which no tolerance would notice for long."""
-import ctypes
 
 import numpy as np
 import pytest
 
 import rich_states as R
-from helpers import C2, dev_library, make_env, oracle_host_pre_reset
+from helpers import C2, dev_library, dev_switches, make_env, oracle_host_pre_reset
 
 pytestmark = pytest.mark.gpu
 
@@ -230,7 +229,7 @@ def _market_actions(env, be, seed, t, info):
 
 
 def test_development_switch_equals_the_in_place_path():
-    """-DAIE_DEV build: skip bit 1 << 20 rewrites the flat vectors in full on every step; its twin does not."""
+    """-DAIE_DEV build: the switch AIE_DEV_FLAT_FULL rewrites the flat vectors in full on every step; its twin does not."""
     import torch
 
     with dev_library():
@@ -239,8 +238,7 @@ def test_development_switch_equals_the_in_place_path():
             env.seed(15)
             env.reset()
     full, inc = envs[0].backend, envs[1].backend
-    full.lib.aie_dev_set_skip_mask.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    assert full.lib.aie_dev_set_skip_mask(full.handle, 1 << 20) == 0
+    assert full.lib.aie_dev_set_skip_mask(full.handle, dev_switches()["AIE_DEV_FLAT_FULL"]) == 0
     info = R.Info(envs[0])
     for t in range(60):
         a, p = _market_actions(envs[1], inc, 15, t, info)

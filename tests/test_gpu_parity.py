@@ -1057,7 +1057,6 @@ def test_compile_time_instance_equals_generic_kernel(case):
     from ai_economist_amd import _specs
 
     lds = (ctypes.c_int64 * 6)()
-    env_s.backend.lib.aie_dev_lds_bytes.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     assert env_s.backend.lib.aie_dev_lds_bytes(env_s.backend.handle, lds) == 0
     assert -(-2 * lds[5] // 4) == _specs.SPECS[k_inst][4], "instance %d: %d B of LDS -> %d workgroups per CU" % (k_inst, lds[0], lds[5])
     pair = [make_env(cfg, n_envs=512, device="cuda:0") for _ in range(2)]
@@ -1295,8 +1294,6 @@ def test_draw_window_refills_do_not_change_the_stream(words):
     """The components draw from a small LDS window of tempered MT19937 words; running past it refills it from the
     state in HBM (with a twist when word 623 is passed).  With the window cut down to `words` every step of a 10-agent
     environment refills several times: the arena must stay bit-identical to the default window's."""
-    import ctypes
-
     import torch
 
     cfg = dict(C2, n_agents=10, episode_length=60)
@@ -1306,7 +1303,6 @@ def test_draw_window_refills_do_not_change_the_stream(words):
             env.seed(8)
             env.reset()
     lib = small.backend.lib
-    lib.aie_dev_set_draw_window.argtypes = [ctypes.c_void_p, ctypes.c_int]
     assert lib.aie_dev_set_draw_window(small.backend.handle, words) == 0
     for t in range(130):  # two episode ends
         a, p = ref.backend.sample_random_actions(seed=9)

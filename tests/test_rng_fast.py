@@ -496,8 +496,6 @@ def test_hip_fast_mode_draw_window_refills(words):
     """The components' draw window cut down to `words` (development hook; the environment then runs the full-featured
     kernel): every step of a 10-agent environment refills it several times from the counter stream -- block changes
     included -- and still equals the oracle, which knows no window."""
-    import ctypes
-
     import torch
     from helpers import dev_library
     from oracle_lib import OracleEnv
@@ -509,7 +507,6 @@ def test_hip_fast_mode_draw_window_refills(words):
         env.seed(8)
         env.reset()
     be = env.backend
-    be.lib.aie_dev_set_draw_window.argtypes = [ctypes.c_void_p, ctypes.c_int]
     assert be.lib.aie_dev_set_draw_window(be.handle, words) == 0
     oracle = OracleEnv(env.build_config(), env.layout_planes())
     oracle.seed(8)

@@ -3,18 +3,14 @@
 to see launch stagger / tail effects.  GPU only."""
 import ctypes
 import os
-
-os.environ["AIE_DEV_LIB"] = "1"  # the aie_dev_* hooks live in libaie_hip_dev.so (-DAIE_DEV) only
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")):
-    sys.path.insert(0, p)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import numpy as np
+import torch
 
-import bench  # noqa: E402
-from helpers import make_env  # noqa: E402
+import devlib
+
+bench, make_env = devlib.setup()
 
 E = 4096
 N_AGENTS = int(sys.argv[1]) if len(sys.argv) > 1 else 4
@@ -31,14 +27,12 @@ if len(sys.argv) > 2 and sys.argv[2] == "generic":
     be.lib.aie_select_step_kernel(be.handle, 1)
 print("n_agents", N_AGENTS, "step kernel instance", be.lib.aie_step_kernel_instance(be.handle))
 lds = (ctypes.c_int64 * 6)()
-be.lib.aie_dev_lds_bytes.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 be.lib.aie_dev_lds_bytes(be.handle, lds)
 print("LDS bytes per workgroup %d: record %d, location map %d, f64 scratch %d, staging %d -> %d workgroups per CU" % tuple(lds))
 for _ in range(300):
     a, p = be.sample_random_actions(1234)
     be.step(a, p)
 buf = torch.zeros(12 * E, dtype=torch.int64, device="cuda")
-be.lib.aie_dev_set_trace.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 be.lib.aie_dev_set_trace(be.handle, ctypes.c_void_p(buf.data_ptr()))
 names = ["start", "loaded", "build", "cda", "gather", "tax", "regen", "end", "rec_in_lds", "srcn_zeroed", "flat_done(w0)", "spatial+masks(w1)"]
 for rep in range(2):

@@ -2,19 +2,13 @@
 """Development tool: where a replica's reset-time layout generation (BASELINE configs[0]'s scenario, four wavefronts per
 replica) spends its time: per-replica phase clocks through the -DAIE_DEV build.  GPU only."""
 import ctypes
-import os
 
-os.environ["AIE_DEV_LIB"] = "1"
-import sys
+import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import devlib
 
-import bench  # noqa: E402
-from helpers import make_env  # noqa: E402
+bench, make_env = devlib.setup()
 
 E = 4096
 env = make_env(dict(bench.C1_CFG), n_envs=E, device="cuda:0")
@@ -22,7 +16,6 @@ env.seed(1)
 env.reset()
 be = env.backend
 buf = torch.zeros(12 * E, dtype=torch.int64, device="cuda")
-be.lib.aie_dev_set_trace.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 be.lib.aie_dev_set_trace(be.handle, ctypes.c_void_p(buf.data_ptr()))
 part = (torch.arange(E, device="cuda") % 50 == 0).to(torch.uint8)
 for rep in range(3):

@@ -1,24 +1,16 @@
 #!/usr/bin/env python
 """Development tool: launch time of the COVID step kernel (BASELINE configs[3], recurrence instantiation) with parts of
 its memory traffic switched off (CV_SKIP in csrc/aie_kernels_covid.hip, -DAIE_DEV build).  GPU only."""
-import ctypes
-import os
+import torch
 
-os.environ["AIE_DEV_LIB"] = "1"
-import sys
+import devlib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
-import torch  # noqa: E402
-
-import bench  # noqa: E402
+bench, _ = devlib.setup()
 
 E = 8192
 env = bench.make_env(bench._c4_cfg(), n_envs=E, device="cuda:0")
 env.reset()
 be = env.backend
-be.lib.aie_dev_set_skip_mask.argtypes = [ctypes.c_void_p, ctypes.c_int]
 cur = [be.sample_random_actions(1234, 0, slot=0), 0]
 
 
@@ -38,12 +30,11 @@ def timed(n):
     return ev0.elapsed_time(ev1) / n * 1e3
 
 
-NAMES = {1: "today's history byte store", 2: "history byte loads", 4: "observation stores", 8: "episode sums (RMW)",
-         16: "state row stores"}
+NAMES = {v: k[len("AIE_CV_SKIP_"):].lower().replace("_", " ") for k, v in devlib.switches("AIE_CV_SKIP_").items()}  # csrc/aie_layout.h
 for _ in range(20):
     step()
 base = None
-for mask in (0, 1, 2, 3, 4, 8, 16, 31, 0):
+for mask in (0, 1, 2, 3, 4, 8, 16, sum(NAMES), 0):
     be.lib.aie_dev_set_skip_mask(be.handle, mask)
     for _ in range(5):
         step()

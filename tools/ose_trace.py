@@ -3,19 +3,14 @@
 through the -DAIE_DEV build (OSE_STAMP in csrc/aie_kernels_ose.hip).  GPU only.
   python tools/ose_trace.py [n_envs] [auto|noauto]"""
 import ctypes
-import os
-
-os.environ["AIE_DEV_LIB"] = "1"  # the aie_dev_* hooks live in libaie_hip_dev.so (-DAIE_DEV) only
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")):
-    sys.path.insert(0, p)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import numpy as np
+import torch
 
-import bench  # noqa: E402
-from helpers import make_env  # noqa: E402
+import devlib
+
+bench, make_env = devlib.setup()
 
 E = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
 auto = not (len(sys.argv) > 2 and sys.argv[2] == "noauto")
@@ -31,7 +26,6 @@ for _ in range(10):
     cur = be.step_sample_next(cur[0], cur[1], 1234, 0, next_slot=slot ^ 1)
     slot ^= 1
 buf = torch.zeros(12 * E, dtype=torch.int64, device="cuda")
-be.lib.aie_dev_set_trace.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 be.lib.aie_dev_set_trace(be.handle, ctypes.c_void_p(buf.data_ptr()))
 names = ["start", "loaded+parsed", "labor(perm)", "tax", "obs:sort+tmpl", "obs:gini", "obs:flat rows", "obs:masks", "obs done",
          "metrics", "rewards", "end"]

@@ -1,19 +1,13 @@
 #!/usr/bin/env python
 """Development tool: times aie_step_kernel with individual phases skipped
 (aie_dev_set_skip_mask) to see where a launch spends its time.  GPU only."""
-import ctypes
-import os
-
-os.environ["AIE_DEV_LIB"] = "1"  # the aie_dev_* hooks live in libaie_hip_dev.so (-DAIE_DEV) only
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")):
-    sys.path.insert(0, p)
-import torch  # noqa: E402
+import torch
 
-import bench  # noqa: E402
-from helpers import make_env  # noqa: E402
+import devlib
+
+bench, make_env = devlib.setup()
 
 E = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 cfg = dict(bench.C2_CFG)
@@ -23,7 +17,6 @@ env = make_env(cfg, n_envs=E, device="cuda:0")
 env.seed(1)
 env.reset()
 be = env.backend
-be.lib.aie_dev_set_skip_mask.argtypes = [ctypes.c_void_p, ctypes.c_int]
 for _ in range(300):
     a, p = be.sample_random_actions(1234)
     be.step(a, p)
@@ -47,11 +40,13 @@ def timeit(mask, n=200):
     return s.elapsed_time(e) / n * 1e3
 
 
-names = {0: "full", 1: "-serial components", 2: "-regen", 4: "-spatial obs", 8: "-flat obs+masks",
-         16: "-rewards", 32: "-record store", 63: "only load+decode+locmap+decay",
-         62: "only serial", 61: "only regen", 59: "only spatial", 55: "only flat", 47: "only rewards"}
-names.update({64: "-flat stageA", 128: "-flat cda fill", 256: "-flat tax fill", 512: "-flat masks",
-              1024: "-flat copy-out", 2048: "-build", 4096: "-cda", 8192: "-gather", 16384: "-tax"})
+S = {k[len("AIE_DEV_SKIP_"):]: v for k, v in devlib.switches("AIE_DEV_SKIP_").items()}  # csrc/aie_layout.h
+PHASES = ["COMPONENTS", "REGEN", "MAP_OBS", "FLAT_AND_MASKS", "REWARDS"]
+ALL = sum(S[k] for k in PHASES) | S["RECORD_STORE"]
+names = {0: "full", ALL: "only load+decode+locmap"}
+names.update({S[k]: "-" + k.lower() for k in PHASES + ["RECORD_STORE"]})
+names.update({ALL & ~S[k]: "only " + k.lower() for k in PHASES})
+names.update({S[k]: "-" + k.lower() for k in ("FLAT_STAGE_A", "FLAT_CDA", "FLAT_TAX", "MASKS", "PLANNER_COPY_OUT", "BUILD", "CDA", "GATHER", "TAX")})
 full = timeit(0)
 for m, nm in names.items():
     t = timeit(m)

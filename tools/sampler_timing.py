@@ -1,20 +1,17 @@
 #!/usr/bin/env python
-"""Development: the policy sampler's launch time with parts of the kernel switched off (dev library,
-AIE_SAMPLER_DEV_SKIP bits: 1 no entry loads, 2 no draw index, 4 no arithmetic, 8 empty kernel), one process per setting.
+"""Development: the policy sampler's launch time with parts of the kernel switched off (dev library, AIE_SAMPLER_DEV_SKIP =
+a sum of csrc/aie_layout.h's AIE_SAMPLER_SKIP_* bits), one process per setting.
    python tools/sampler_timing.py            (GPU only)"""
 import os
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import devlib
+
 if len(sys.argv) > 1 and sys.argv[1] == "child":
-    os.environ["AIE_DEV_LIB"] = "1"
-    for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")):
-        sys.path.insert(0, p)
     import torch
 
-    import bench
-    from helpers import make_env
+    bench, make_env = devlib.setup()
 
     E = 4096
     env = make_env(dict(bench.C2_CFG), n_envs=E, device="cuda:0")
@@ -39,8 +36,10 @@ if len(sys.argv) > 1 and sys.argv[1] == "child":
         b.record()
     torch.cuda.synchronize()
     ts = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
+    skip = int(os.environ.get("AIE_SAMPLER_DEV_SKIP", "0"))
+    off = [k[len("AIE_SAMPLER_SKIP_"):].lower() for k, v in devlib.switches("AIE_SAMPLER_SKIP_").items() if skip & v]
     print("skip %s wpr_log2 %s %s: median %.1f us, p10 %.1f, p90 %.1f (event to event, one launch)" % (
-        os.environ.get("AIE_SAMPLER_DEV_SKIP", "0"), os.environ.get("AIE_SAMPLER_WAVES_LOG2", "1"), "flushed" if flush else "warm",
+        "+".join(off) or "nothing", os.environ.get("AIE_SAMPLER_WAVES_LOG2", "1"), "flushed" if flush else "warm",
         ts[N // 2], ts[N // 10], ts[9 * N // 10]))
 else:
     import csv

@@ -6,34 +6,37 @@ instruction counts of the same launches (parse with tools/spec_ablate_report.py)
 
    python tools/spec_ablate.py [n_agents ...]        (default: 4 10)
 """
-import ctypes
 import os
-
-os.environ["AIE_DEV_LIB"] = "1"
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")):
-    sys.path.insert(0, p)
-import torch  # noqa: E402
+import torch
 
-import bench  # noqa: E402
-from helpers import make_env  # noqa: E402
+import devlib
 
-SK = 63 | 512  # the skeleton: record in, decode, occupancy map (nothing else, no record store)
-MASKS = [0, 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384, 32768, 1 << 20, 8 | 16, 2 | 4 | 512, 31 | 512, SK,
-         SK | 1 << 16, SK | 1 << 17, SK | 1 << 18, SK | 1 << 19, SK | 15 << 16, 0]
+bench, make_env = devlib.setup()
+
+S = {k[len("AIE_DEV_"):]: v for k, v in devlib.switches("AIE_DEV_").items()}  # csrc/aie_layout.h
+SHOW = {"SKIP_COMPONENTS": "-components", "SKIP_REGEN": "-regen", "SKIP_MAP_OBS": "-map observations",
+        "SKIP_FLAT_AND_MASKS": "-flat vectors -masks", "SKIP_REWARDS": "-rewards", "SKIP_RECORD_STORE": "-record store",
+        "SKIP_FLAT_STAGE_A": "-flat stage A", "SKIP_FLAT_CDA": "-flat cda", "SKIP_FLAT_TAX": "-flat tax", "SKIP_MASKS": "-masks",
+        "SKIP_PLANNER_COPY_OUT": "-planner copy-out", "SKIP_BUILD": "-build", "SKIP_CDA": "-cda", "SKIP_GATHER": "-gather",
+        "SKIP_TAX": "-tax", "MAP_OBS_FULL": "full map rewrite instead of in-place", "FLAT_FULL": "flat vectors rewritten in full",
+        "SKIP_DRAW_WINDOW": "skeleton - draw window", "SKIP_LOCMAP": "skeleton - occupancy map",
+        "SKIP_ACTION_DECODE": "skeleton - action decode", "SKIP_GENERATOR_ROWS": "skeleton - generator rows to registers"}
+LOAD = ["SKIP_DRAW_WINDOW", "SKIP_LOCMAP", "SKIP_ACTION_DECODE", "SKIP_GENERATOR_ROWS"]  # what the skeleton still does
+SINGLE = [k for k in SHOW if k not in LOAD]
+TAILS = S["SKIP_COMPONENTS"] | S["SKIP_REGEN"] | S["SKIP_MAP_OBS"] | S["SKIP_FLAT_AND_MASKS"] | S["SKIP_REWARDS"] | S["SKIP_MASKS"]
+SK = TAILS | S["SKIP_RECORD_STORE"]  # the skeleton: record in, decode, occupancy map (nothing else, no record store)
+ALL_LOAD = sum(S[k] for k in LOAD)
+NAMES = {0: "full", TAILS: "record in, decode, occupancy map, record out only", SK: "record in, decode, occupancy map only",
+         S["SKIP_FLAT_AND_MASKS"] | S["SKIP_REWARDS"]: "-flat -rewards (wave 0 tail)",
+         S["SKIP_REGEN"] | S["SKIP_MAP_OBS"] | S["SKIP_MASKS"]: "-regen -map obs -masks (wave 1 tail)", SK | ALL_LOAD: "skeleton - all four"}
+NAMES.update({S[k]: SHOW[k] for k in SINGLE})
+NAMES.update({SK | S[k]: SHOW[k] for k in LOAD})
+SKELETON = [TAILS, SK] + [SK | S[k] for k in LOAD] + [SK | ALL_LOAD, 0]
+MASKS = [0] + [S[k] for k in SINGLE] + [S["SKIP_FLAT_AND_MASKS"] | S["SKIP_REWARDS"], S["SKIP_REGEN"] | S["SKIP_MAP_OBS"] | S["SKIP_MASKS"]] + SKELETON
 if os.environ.get("ABLATE_SKELETON"):
-    MASKS = [0, 31 | 512, SK, SK | 1 << 16, SK | 1 << 17, SK | 1 << 18, SK | 1 << 19, SK | 15 << 16, 0]
-SK = 63 | 512
-NAMES = {0: "full", 1: "-components", 2: "-regen", 4: "-map observations", 8: "-flat vectors -masks", 16: "-rewards",
-         31 | 512: "record in, decode, occupancy map, record out only", 63 | 512: "record in, decode, occupancy map only",
-         32: "-record store", 64: "-flat stage A", 128: "-flat cda", 256: "-flat tax", 512: "-masks",
-         1024: "-planner copy-out", 2048: "-build", 4096: "-cda", 8192: "-gather", 16384: "-tax",
-         32768: "full map rewrite instead of in-place", 1 << 20: "flat vectors rewritten in full", 24: "-flat -rewards (wave 0 tail)",
-         2 | 4 | 512: "-regen -map obs -masks (wave 1 tail)",
-         SK | 1 << 16: "skeleton - draw window", SK | 1 << 17: "skeleton - occupancy map", SK | 1 << 18: "skeleton - action decode",
-         SK | 1 << 19: "skeleton - generator rows to registers", SK | 15 << 16: "skeleton - all four"}
+    MASKS = [0] + SKELETON
 LAUNCHES = 30
 E = 4096
 
@@ -48,7 +51,6 @@ def main():
         env.seed(1)
         env.reset()
         be = env.backend
-        be.lib.aie_dev_set_skip_mask.argtypes = [ctypes.c_void_p, ctypes.c_int]
         print("n_agents", n, "step kernel instance", be.lib.aie_step_kernel_instance(be.handle), flush=True)
         for _ in range(300):
             a, p = be.sample_random_actions(1234)
