@@ -10,7 +10,9 @@
 // (aie_layout.h: a_saez), which the step kernel's tax component copies into the record at the period
 // start (or draws np.random.uniform rates instead while the buffer is short); elasticity estimates and
 // the running average are updated here.  f64 throughout; the 2x2 OLS normal equations are solved in
-// closed form (the reference calls np.linalg.inv: agreement ~1e-12 relative, stated in DESIGN.md).
+// closed form (the reference calls np.linalg.inv).  Both lose about u * (mean / sd)^2 of log(1 - tau) in the
+// determinant, u = 2^-53: a few u on spread-out marginal rates, ~1e-9 at sd 1e-3, ~1e-6 at sd 1e-5; everything else
+// stays at a few u.  tests/saez_exact.py derives the band every output has to lie in ("Saez").
 #pragma once
 #include "aie_kernels.hip"
 

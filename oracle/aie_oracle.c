@@ -622,7 +622,8 @@ static void saez_estimate_elasticity(const double* buf, int len, double elas_tm1
     free(d);
     if (!(sd < 1e-6)) {
       /* OLS of log income on [log(1 - marginal rate), 1]; the 2x2 normal equations in closed form
-       * (the reference goes through np.linalg.inv: agreement to ~1e-12 relative, not bitwise) */
+       * (the reference goes through np.linalg.inv: not bitwise; both lose ~u * (mean / sd)^2 of log(1 - tau) in the
+       * determinant -- tests/saez_exact.py derives the band both stay in) */
       double sxx = 0, sx = 0, sxy = 0, sy = 0;
       for (int k = 0; k < m; ++k) {
         double t1 = 1 - taus[k]; if (t1 < 1e-9) t1 = 1e-9;
