@@ -173,6 +173,16 @@ class AieTrajSegment(C.Structure):
 TRAJ_MAX_SEGMENTS = 16  # AIE_TRAJ_MAX_SEGMENTS
 
 
+class AiePpoClass(C.Structure):  # aie_ppo_class
+    _fields_ = [(k, C.c_void_p) for k in ("logits", "values", "masks", "actions", "logp_old", "adv", "values_old", "returns",
+                                          "adv_moments", "grad_logits", "grad_values", "stats")] + \
+               [(k, C.c_float) for k in ("clip", "vf_clip", "vf_coef", "ent_coef")]
+
+
+PPO_N_STATS = 8       # AIE_PPO_N_STATS
+PPO_MAX_WAVES = 8192  # AIE_PPO_MAX_WAVES
+
+
 def bind(lib):
     """Declares the prototypes of every symbol include/aie.h exports."""
     vp = C.c_void_p
@@ -220,6 +230,10 @@ def bind(lib):
     lib.aie_policy_evaluate_backward.argtypes = [vp, C.c_int64] + [vp] * 13
     lib.aie_gae.restype = C.c_int
     lib.aie_gae.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp]
+    lib.aie_ppo_workspace_bytes.restype = C.c_int64
+    lib.aie_ppo_workspace_bytes.argtypes = [vp, C.c_int64]
+    lib.aie_ppo_loss.restype = C.c_int
+    lib.aie_ppo_loss.argtypes = [vp, C.c_int64, C.POINTER(AiePpoClass), C.POINTER(AiePpoClass), vp, vp, C.c_int64, vp]
     lib.aie_trajectory_store.restype = C.c_int
     lib.aie_trajectory_store.argtypes = [vp, C.POINTER(AieTrajSegment), C.c_int32, C.c_int32, vp, vp]
     lib.aie_sample_random_actions.restype = C.c_int
@@ -271,7 +285,7 @@ EXPORTED_SYMBOLS = [
     "aie_sample_masked_actions", "aie_sample_policy_actions", "aie_step_sample_next", "aie_step_sample_next_masked", "aie_set_reward_log", "aie_set_auto_reset",
     "aie_set_dense_log_active", "aie_step_kernel_instance", "aie_select_step_kernel", "aie_specialize", "aie_set_global_saez_buffer", "aie_sizeof_config",
     "aie_arena_info", "aie_step_range", "aie_sample_policy_actions_logp", "aie_policy_evaluate", "aie_policy_evaluate_backward",
-    "aie_gae", "aie_trajectory_store",
+    "aie_gae", "aie_trajectory_store", "aie_ppo_workspace_bytes", "aie_ppo_loss",
 ]
 STEP_HEAD, STEP_TAIL, STEP_OBSERVE, STEP_REBASE, STEP_RETAX = 1, 2, 4, 8, 16  # AIE_STEP_*
 STEP_REGEN, STEP_EMIT, STEP_CLOSE = 64, 128, 256  # the end of a step in three parts (scenario hooks run between them)

@@ -10,6 +10,7 @@
 #include "aie_kernels.hip"
 #include "aie_kernels_ose.hip"
 #include "aie_kernels_saez.hip"
+#include "aie_kernels_ppo.hip"
 #include "aie_kernels_covid.hip"  // last: switches FP contraction off for the rest of the TU
 #include "aie_jit.h"
 
@@ -1080,6 +1081,109 @@ int aie_gae(aie_env* env, int32_t T, const float* d_log, int32_t n_slots, int32_
   A.gl = aie_gae_gl(gamma, lambda);
   AIE_HIP_CHECK(env, hipSetDevice(env->device));
   hipLaunchKernelGGL(aie_gae_kernel, dim3((unsigned)((row + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream), A);
+  AIE_HIP_CHECK(env, hipGetLastError());
+  return AIE_OK;
+}
+
+// The wavefronts aie_ppo_loss launches for B batch elements of `items` work items each, and its workspace: a record each.
+static uint32_t aie_ppo_waves(int64_t work, int64_t bound) { return (uint32_t)(work < bound ? work : bound); }
+int64_t aie_ppo_workspace_bytes(const aie_env* env, int64_t B) {
+  if (!env || B < 1) return AIE_E_INVALID;
+  // (at most one work item per actor: n agents and the planner)
+  const int64_t per = (int64_t)env->P.n + 1;
+  const int64_t work = B > AIE_PPO_MAX_WAVES / per ? (int64_t)AIE_PPO_MAX_WAVES : B * per;
+  return (int64_t)aie_ppo_waves(work, AIE_PPO_MAX_WAVES) * AIE_PPO_RECORD * (int64_t)sizeof(double);
+}
+int aie_ppo_loss(aie_env* env, int64_t B, const aie_ppo_class* agents, const aie_ppo_class* planner, const int32_t* d_index,
+                 void* d_workspace, int64_t workspace_bytes, void* stream) {
+  if (!env) return AIE_E_INVALID;
+  const aie_ppo_class* cls[2] = {agents, planner};
+  for (int c = 0; c < 2; ++c) {
+    const aie_ppo_class* k = cls[c];
+    if (!k) continue;
+    if (!k->logits || !k->masks || !k->actions || !k->logp_old || !k->adv || !k->grad_logits || !k->stats ||
+        (k->values && (!k->values_old || !k->returns || !k->grad_values)) || (!k->values && k->grad_values) || !(k->clip > 0.0f)) {
+      snprintf(env->err, sizeof(env->err), "aie_ppo_loss: the %s class needs logits, masks, actions, logp_old, adv, grad_logits and "
+               "stats, with values also values_old, returns and grad_values (and no grad_values without), and clip > 0 (%g)",
+               c ? "planner's" : "agents'", (double)k->clip);
+      return AIE_E_INVALID;
+    }
+  }
+  // the rows' shape is the evaluator's (B < 1 and the samplers' refusals are its own)
+  aie_policy_eval_args E;
+  const int rc = aie_policy_eval_args_of(env, "aie_ppo_loss", B, agents ? agents->logits : nullptr, planner ? planner->logits : nullptr,
+                                         agents ? agents->masks : nullptr, planner ? planner->masks : nullptr, &E);
+  if (rc != AIE_OK) return rc;
+  if (!E.items) return AIE_OK;
+  aie_ppo_args A;
+  memset(&A, 0, sizeof(A));
+  const aie_policy_eval_group* eg[2] = {&E.agents, &E.planner};
+  aie_ppo_group* pg[2] = {&A.agents, &A.planner};
+  const int width[2] = {env->P.act_a_width, env->P.act_p_width};
+  for (int c = 0; c < 2; ++c) {
+    const aie_ppo_class* k = cls[c];
+    if (!k) continue;
+    const aie_policy_eval_group& e = *eg[c];
+    aie_ppo_group& G = *pg[c];
+    G.lg = k->logits;
+    G.val = k->values;
+    G.mk = k->masks;
+    G.act = k->actions;
+    G.lp_old = k->logp_old;
+    G.adv = k->adv;
+    G.val_old = k->values_old;
+    G.ret = k->returns;
+    G.mom = k->adv_moments;
+    G.grad = k->grad_logits;
+    G.grad_v = k->grad_values;
+    G.stats = k->stats;
+    G.lg_bstride = e.lg_bstride;
+    G.len = e.len;
+    G.lrs = e.lrs;
+    G.lsh = e.lsh;
+    G.rows = e.rows;
+    G.w = width[c] > 0 ? width[c] : 1;
+    G.actors = e.rows / G.w;
+    if (G.w > 64 || G.actors * G.w != e.rows) {
+      snprintf(env->err, sizeof(env->err), "aie_ppo_loss: %d action slots per actor (%d rows) are more than a wavefront holds", G.w, e.rows);
+      return AIE_E_UNSUPPORTED;
+    }
+    G.generic = e.generic || G.w > 1;
+    const int rpw = G.generic ? 1 : 64 >> e.lsh;
+    G.items = G.generic ? G.actors : (e.rows + rpw - 1) / rpw;
+    G.clip = k->clip;
+    G.vf_clip = k->vf_clip;
+    G.vf_coef = k->vf_coef;
+    G.ent_coef = k->ent_coef;
+    G.scale = aie_ppo_scale(B * (int64_t)G.actors);
+    G.g_H = -aie_ppo_product(G.scale, k->ent_coef);
+    G.kv = aie_ppo_product(G.scale, k->vf_coef);
+  }
+  A.params = env->d_params;
+  A.index = d_index;
+  A.ws = static_cast<double*>(d_workspace);
+  A.B = (uint32_t)B;
+  A.items = (uint32_t)(A.agents.items + A.planner.items);
+  A.act_a_width = E.act_a_width;
+  A.ragged = E.ragged;
+  const int64_t work = B * (int64_t)A.items;
+  if (work > 0x7fffff00ll) {
+    snprintf(env->err, sizeof(env->err), "aie_ppo_loss: B = %lld is more than one call takes (%u work items per batch element)",
+             (long long)B, A.items);
+    return AIE_E_INVALID;
+  }
+  AIE_HIP_CHECK(env, hipSetDevice(env->device));
+  // (the whole bound, although 89 registers leave only 5120 wavefronts resident at once: sized to residency the kernel took
+  // 2.4 x as long on a fragment of 819 200 rows -- DESIGN_HISTORY.md, item 10 -- it lives on loads in flight, not on rounds)
+  A.waves = aie_ppo_waves(work, AIE_PPO_MAX_WAVES);
+  const int64_t need = (int64_t)A.waves * AIE_PPO_RECORD * (int64_t)sizeof(double);
+  if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 7u) || workspace_bytes < need) {
+    snprintf(env->err, sizeof(env->err), "aie_ppo_loss: the workspace (%p, %lld bytes) must be device memory, 8-byte aligned, of at "
+             "least %lld bytes (aie_ppo_workspace_bytes)", d_workspace, (long long)workspace_bytes, (long long)need);
+    return AIE_E_INVALID;
+  }
+  hipLaunchKernelGGL(aie_ppo_loss_kernel, dim3((A.waves + 3u) / 4u), dim3(256), 0, static_cast<hipStream_t>(stream), A);
+  hipLaunchKernelGGL(aie_ppo_reduce_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), A);
   AIE_HIP_CHECK(env, hipGetLastError());
   return AIE_OK;
 }

@@ -1771,6 +1771,150 @@ typedef struct aie_gae_args {
   int32_t T, slots, first, E, n;
   float gamma, gl;
 } aie_gae_args;
+/* The PPO loss (include/aie.h: aie_ppo_loss), stated once -- the kernels call these helpers, tests/test_ppo_loss_cpu.py
+ * compiles them, tests/ppo_ref.py transcribes this comment.  float32, every operation rounded on its own (nothing fused
+ * outside aie_sampler_expf / aie_sampler_logf), selects instead of min / max so that a NaN takes one stated way.
+ * An ACTOR is one agent, or the planner, of one batch element, with w action slots (act_a_width / act_p_width) whose rows
+ * are the evaluator's: slot s gives logp_s (aie_policy_row_logp) and H_s (aie_policy_row_stats) with their conventions.
+ *   joint terms   ln = logp_0, then ln = ln + logp_s for s = 1 .. w - 1;  lo: the same sum over the stored old
+ *                 log-probabilities;  He: the same sum over H_s;  d = ln - lo;
+ *                 valid = every logp_s and every stored old logp finite, and |d| <= 80;
+ *   advantage     A' = A, or (A - mean) * rstd with moments {mean, rstd} given;
+ *   ratio         r = aie_sampler_expf(d) (exactly 1 at d = 0; good to 2.7 ulp over -80 .. 80);
+ *                 lo_c = 1 - clip, hi_c = 1 + clip;  rc = r < lo_c ? lo_c : r, then rc > hi_c ? hi_c : rc;
+ *                 u = r * A';  c = rc * A';  unclipped = (u <= c) (a tie goes to u, a NaN gives false);
+ *                 surr = unclipped ? u : c;
+ *   per actor     valid: policy term -surr, kl term -d, clip flag (r < lo_c || r > hi_c), |d|;  not valid: 0 each, and the
+ *                 actor counts as skipped;
+ *   slot gradient g_logp = (valid && unclipped) ? -(scale * u) : 0 for every slot of the actor;
+ *                 g_H = -(scale * ent_coef) for every slot of every actor (the product formed once per call);
+ *                 an entry's gradient is aie_policy_entry_grad with these two (aie_policy_row_backward is the row's loop
+ *                 over it): exactly 0 at entries that are not allowed;
+ *                 scale = 1.0f / (float)N, N = B x the class's actors per batch element;
+ *   value         e1 = v - ret;  q1 = e1 * e1;  with vf_clip <= 0: vf = q1, dq = e1;  with vf_clip > 0:
+ *                 dv = v - v_old;  dc = dv < -vf_clip ? -vf_clip : dv, then dc > vf_clip ? vf_clip : dc;  vc = v_old + dc;
+ *                 e2 = vc - ret;  q2 = e2 * e2;  first = (q1 >= q2);  vf = first ? q1 : q2;
+ *                 dq = first ? e1 : (dc == dv ? e2 : 0);
+ *                 grad_v = kv * (dq + dq), kv = scale * vf_coef (formed once per call); for every actor, valid or not;
+ *   statistics    float64 sums over the float32 terms of all N actors (an actor that is not valid adds 0 to the policy, kl
+ *                 and clip sums), each mean = sum / N in float64 rounded once to float32 (aie_ppo_finish_stats):
+ *                 [0] loss = P + vf_coef V - ent_coef E from the float64 means, rounded once;  [1] P, the mean policy term;
+ *                 [2] V, the mean vf (0 without values);  [3] E, the mean He;  [4] the mean kl term;  [5] the mean clip
+ *                 flag;  [6] the number of skipped actors;  [7] the maximum |d| over valid actors (0 if none).
+ * Non-finite advantages, values and returns are the caller's own: they propagate. */
+AIE_HD static inline int aie_ppo_finite(float x) {
+  uint32_t b;
+  memcpy(&b, &x, 4);
+  return (b & 0x7f800000u) != 0x7f800000u;
+}
+/* one step of a joint term (ln, lo, He): slot s's value joins the sum of the slots before it */
+AIE_HD static inline float aie_ppo_joint_add(float acc, float term, int s) {
+  AIE_NOCONTRACT
+  return s ? acc + term : term;
+}
+AIE_HD static inline float aie_ppo_scale(int64_t N) { return 1.0f / (float)N; }
+AIE_HD static inline float aie_ppo_product(float a, float b) {  /* scale * ent_coef, scale * vf_coef: one rounded product */
+  AIE_NOCONTRACT
+  return a * b;
+}
+AIE_HD static inline float aie_ppo_advantage(float A, int has_moments, float mean, float rstd) {
+  AIE_NOCONTRACT
+  const float c = A - mean;
+  const float s = c * rstd;
+  return has_moments ? s : A;
+}
+typedef struct aie_ppo_actor {
+  float pol, kl, clipf, absd, g_logp; /* the per-actor terms (0 for an actor that is not valid); every slot's g_logp */
+  int32_t valid;
+} aie_ppo_actor;
+/* finite: every logp_s and every stored old logp of the actor is finite (aie_ppo_finite) */
+AIE_HD static inline aie_ppo_actor aie_ppo_actor_terms(float ln, float lo, int finite, float Ap, float clip, float scale) {
+  AIE_NOCONTRACT
+  aie_ppo_actor R;
+  const float d = ln - lo;
+  const int valid = finite && fabsf(d) <= 80.0f;
+  const float r = aie_sampler_expf(valid ? d : 0.0f);
+  const float lo_c = 1.0f - clip, hi_c = 1.0f + clip;
+  float rc = r < lo_c ? lo_c : r;
+  rc = rc > hi_c ? hi_c : rc;
+  const float u = r * Ap;
+  const float c = rc * Ap;
+  const int unclipped = u <= c;
+  const float surr = unclipped ? u : c;
+  const float su = scale * u;
+  R.valid = valid;
+  R.pol = valid ? -surr : 0.0f;
+  R.kl = valid ? -d : 0.0f;
+  R.clipf = (valid && (r < lo_c || r > hi_c)) ? 1.0f : 0.0f;
+  R.absd = valid ? fabsf(d) : 0.0f;
+  R.g_logp = (valid && unclipped) ? -su : 0.0f;
+  return R;
+}
+typedef struct aie_ppo_value {
+  float vf, grad;
+} aie_ppo_value;
+AIE_HD static inline aie_ppo_value aie_ppo_value_terms(float v, float v_old, float ret, float vf_clip, float kv) {
+  AIE_NOCONTRACT
+  aie_ppo_value R;
+  const float e1 = v - ret;
+  const float q1 = e1 * e1;
+  float vf = q1, dq = e1;
+  if (vf_clip > 0.0f) {
+    const float dv = v - v_old;
+    float dc = dv < -vf_clip ? -vf_clip : dv;
+    dc = dc > vf_clip ? vf_clip : dc;
+    const float vc = v_old + dc;
+    const float e2 = vc - ret;
+    const float q2 = e2 * e2;
+    const int first = q1 >= q2;
+    vf = first ? q1 : q2;
+    dq = first ? e1 : (dc == dv ? e2 : 0.0f);
+  }
+  const float dq2 = dq + dq;
+  R.vf = vf;
+  R.grad = kv * dq2;
+  return R;
+}
+/* sums: the class's eight float64 totals ([1] .. [5] sums of the terms, [6] the skipped count, [7] the maximum; [0] unused) */
+AIE_HD static inline void aie_ppo_finish_stats(const double* sums, double N, float vf_coef, float ent_coef, float* stats) {
+  AIE_NOCONTRACT
+  const double P = sums[1] / N, V = sums[2] / N, E = sums[3] / N;
+  const double cv = (double)vf_coef * V, ce = (double)ent_coef * E;
+  const double pv = P + cv;
+  stats[0] = (float)(pv - ce);
+  stats[1] = (float)P;
+  stats[2] = (float)V;
+  stats[3] = (float)E;
+  stats[4] = (float)(sums[4] / N);
+  stats[5] = (float)(sums[5] / N);
+  stats[6] = (float)sums[6];
+  stats[7] = (float)sums[7];
+}
+/* The kernels' argument (aie_ppo_loss fills it; the rows' shape is the evaluator's, aie_policy_eval_group).  Batch element
+ * b reads logits, values and writes both gradients at row b; everything stored (masks in the logits' layout, actions, old
+ * logp, advantages, old values, returns) at row index[b] (index NULL: b).  An actor has w slots; items = wavefront-sized
+ * work items per batch element: whole single-slot rows in aligned segments of 1 << lsh lanes, or (generic: w > 1, ragged
+ * rows, rows of more than 64 entries) one actor each.  `waves` wavefronts (at most AIE_PPO_MAX_WAVES, at most the work
+ * items) stride over B x items work items and leave one
+ * record of 2 x 8 float64 (agents, planner) each in the workspace; the second launch adds the records in index order. */
+typedef struct aie_ppo_group {
+  const float *lg, *val, *mk;
+  const int32_t* act;
+  const float *lp_old, *adv, *val_old, *ret, *mom;
+  float *grad, *grad_v, *stats;
+  float clip, vf_clip, vf_coef, ent_coef, scale, g_H, kv;
+  uint32_t lg_bstride;
+  int32_t len, lrs, lsh, rows, w, actors, items, generic;
+} aie_ppo_group;
+typedef struct aie_ppo_args {
+  aie_ppo_group agents, planner;
+  const aie_params* params; /* the device copy: read for multi-action agents only */
+  const int32_t* index;
+  double* ws;
+  uint32_t B, items, waves;
+  int32_t act_a_width, ragged;
+} aie_ppo_args;
+#define AIE_PPO_RECORD 16 /* float64 per wavefront's record */
 /* aie_trajectory_store's kernel argument: the caller's segments (include/aie.h: aie_traj_segment, 32 bytes each) with the
  * copy width decided on the host: wide != 0 = 16-byte lane accesses (source, destination, stride and size allow it for
  * every replica and slot), else 4-byte ones. */

@@ -489,6 +489,114 @@ class DeviceBackend:
                                      self._stream()))
         return tuple(out)
 
+    def ppo_loss(self, logits_a, logits_p, values_a, values_p, batch, index=None, clip=0.3, vf_clip=50.0, vf_coef=0.05,
+                 ent_coef=0.025, coeffs_p=None, adv_moments=None, out=None):
+        """aie_ppo_loss: the PPO loss of both actor classes with its gradients, two launches on the current stream.
+        logits_a [B, n, MA] / logits_p [B, MP] and values_a [B, n] / values_p [B] are the networks' outputs for B batch
+        elements (either class None: left out; values None: no value term).  `batch` holds the STORED operands as
+        contiguous device tensors of R rows -- masks_a / masks_p (float32, the logits' layout), actions_* (int32),
+        logp_old_*, adv_*, values_old_*, returns_* (float32; Trajectory.ppo_batch() makes the dict) -- read at row index[b]
+        (index: int32 [B] on the device) or, with index None, at row b (R == B): a minibatch is an index, nothing is
+        copied and nothing is converted (a tensor of another dtype, device or layout is an error).
+        clip, vf_clip, vf_coef, ent_coef: the agents' coefficients, and the planner's unless coeffs_p (a dict of any of
+        them) says otherwise.  adv_moments: None or (moments_a, moments_p), each None or a float32 device tensor
+        {mean, rstd}: the advantage enters as (adv - mean) * rstd.
+        Returns ((stats_a, grad_logits_a, grad_values_a), (stats_p, grad_logits_p, grad_values_p)); a class that is left
+        out is None, grad_values is None without values.  stats: float32 [_cabi.PPO_N_STATS] (include/aie.h); the
+        gradients are those of stats[0].  Only the two gradients, the statistics and (once per backend, 1 MiB: calls of
+        one backend share it and must not run at the same time on two streams) the workspace are allocated -- out=((stats_a, grad_logits_a, grad_values_a), (stats_p, ...)) to fill the caller's own instead."""
+        torch = _torch()
+        per_a = self.tensors["obs_a_action_mask"].numel() // self.E
+        per_p = self.tensors["obs_p_action_mask"].numel() // self.E
+        aa, ap = self._action_buffers(0)
+        act_a, act_p = aa.numel() // self.E, ap.numel() // self.E
+        f = dict(dtype=torch.float32, device=self.device)
+
+        def net(t, per, what):  # a network output: made contiguous float32 here if it is not
+            if t is None:
+                return None
+            t = t.detach().to(**f).contiguous()
+            if t.numel() == 0 or t.numel() % per:
+                raise ValueError("ppo_loss: %s has %d elements, not a multiple of the %d per batch element" % (what, t.numel(), per))
+            return t
+
+        def stored(name, dtype, per):  # a stored operand: used where it lies
+            t = batch.get(name)
+            if t is None:
+                raise ValueError("ppo_loss: the batch has no %r" % name)
+            if (not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != self.device or not t.is_contiguous()
+                    or t.numel() == 0 or t.numel() % per):
+                raise ValueError("ppo_loss: %s must be a contiguous %s device tensor of R x %d elements" % (name, dtype, per))
+            return t
+
+        la, lp = net(logits_a, per_a, "logits_a"), net(logits_p, per_p, "logits_p")
+        if la is None and lp is None:
+            raise ValueError("ppo_loss: no actor class")
+        va = net(values_a, self.n, "values_a") if la is not None else None
+        vp = net(values_p, 1, "values_p") if lp is not None else None
+        Bs = {t.numel() // per for t, per in ((la, per_a), (lp, per_p), (va, self.n), (vp, 1)) if t is not None}
+        if len(Bs) != 1:
+            raise ValueError("ppo_loss: logits and values disagree on the batch size (%s)" % sorted(Bs))
+        B = Bs.pop()
+        if index is not None and (index.dtype != torch.int32 or index.device != self.device or not index.is_contiguous()
+                                  or index.numel() != B):
+            raise ValueError("ppo_loss: index must be a contiguous int32 device tensor of B = %d elements" % B)
+        mom = adv_moments if adv_moments is not None else (None, None)
+        coef_a = dict(clip=clip, vf_clip=vf_clip, vf_coef=vf_coef, ent_coef=ent_coef)
+        coef_p = dict(coef_a, **(coeffs_p or {}))
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        classes, outs, keep, Rs = [], [], [], set()
+        for who, lg, val, per, act, actors, co, mo in (("a", la, va, per_a, act_a, self.n, coef_a, mom[0]),
+                                                       ("p", lp, vp, per_p, act_p, 1, coef_p, mom[1])):
+            if lg is None:
+                classes.append(None)
+                outs.append(None)
+                continue
+            ops = dict(masks=stored("masks_" + who, torch.float32, per), actions=stored("actions_" + who, torch.int32, act),
+                       logp_old=stored("logp_old_" + who, torch.float32, act), adv=stored("adv_" + who, torch.float32, actors))
+            pers = dict(masks=per, actions=act, logp_old=act, adv=actors, values_old=actors, returns=actors)
+            if val is not None:
+                ops["values_old"] = stored("values_old_" + who, torch.float32, actors)
+                ops["returns"] = stored("returns_" + who, torch.float32, actors)
+            Rs |= {t.numel() // pers[k] for k, t in ops.items()}
+            if mo is not None and (mo.dtype != torch.float32 or mo.device != self.device or not mo.is_contiguous() or mo.numel() != 2):
+                raise ValueError("ppo_loss: adv_moments are float32 device tensors {mean, rstd}")
+            if out is not None:
+                stats, grad, grad_v = out[who == "p"]
+                for t, like, what in ((stats, None, "stats"), (grad, lg, "grad_logits"), (grad_v, val, "grad_values")):
+                    numel = _cabi.PPO_N_STATS if like is None else like.numel()
+                    if (t is None) != (what == "grad_values" and val is None) or (
+                            t is not None and (t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous()
+                                               or t.numel() != numel)):
+                        raise ValueError("ppo_loss: out's %s_%s must be a contiguous float32 device tensor of %d elements (None "
+                                         "for grad_values without values)" % (what, who, numel))
+            else:
+                stats = torch.empty(_cabi.PPO_N_STATS, **f)
+                grad = torch.empty_like(lg)
+                grad_v = torch.empty_like(val) if val is not None else None
+            c = _cabi.AiePpoClass(logits=ptr(lg), values=ptr(val), masks=ptr(ops["masks"]), actions=ptr(ops["actions"]),
+                                  logp_old=ptr(ops["logp_old"]), adv=ptr(ops["adv"]), values_old=ptr(ops.get("values_old")),
+                                  returns=ptr(ops.get("returns")), adv_moments=ptr(mo), grad_logits=ptr(grad),
+                                  grad_values=ptr(grad_v), stats=ptr(stats), clip=co["clip"], vf_clip=co["vf_clip"],
+                                  vf_coef=co["vf_coef"], ent_coef=co["ent_coef"])
+            classes.append(c)
+            outs.append((stats, grad, grad_v))
+            keep.append(ops)
+        if len(Rs) != 1 or (index is None and Rs != {B}):
+            raise ValueError("ppo_loss: the stored operands have %s rows; all must agree, and without an index equal B = %d"
+                             % (sorted(Rs), B))
+        # the workspace: the largest any B needs (1 MiB), allocated once per backend and never replaced -- a captured call
+        # keeps its pointer.  Calls of one backend share it: they must not overlap (two streams: two backends' worth of
+        # workspace through the C ABI)
+        ws = getattr(self, "_ppo_ws", None)
+        if ws is None:
+            ws = self._ppo_ws = torch.empty(_cabi.PPO_MAX_WAVES * 16, dtype=torch.float64, device=self.device)
+        ref = lambda c: C.byref(c) if c is not None else None  # noqa: E731
+        self._check(self.lib.aie_ppo_loss(self.handle, C.c_int64(B), ref(classes[0]), ref(classes[1]),
+                                          C.c_void_p(index.data_ptr()) if index is not None else None,
+                                          C.c_void_p(ws.data_ptr()), C.c_int64(ws.numel() * 8), self._stream()))
+        return outs[0], outs[1]
+
     def _action_buffers(self, slot):
         torch = _torch()
         if self._rand_a is None:

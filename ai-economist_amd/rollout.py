@@ -215,6 +215,25 @@ class Trajectory:
         out["done"] = self.log[..., -1].flatten(0, 1)
         return out
 
+    def ppo_batch(self, adv_a, adv_p, ret_a, ret_p):
+        """The stored operands of rollout.ppo_loss / Backend.ppo_loss as [T * E, ...] views (nothing is copied): masks_*,
+        actions_*, logp_old_* (the stored logp), values_old_* (the stored values, rows 0 .. T - 1), adv_* and returns_*
+        (what advantages() returned, or the caller's own of those shapes).  A minibatch is an int32 index into its rows."""
+        if not (self.has_logp and self.has_values):
+            raise ValueError("Trajectory.ppo_batch: this trajectory keeps no logp or no values")
+        T, E, n = self.T, self.be.E, self.be.n
+        out = {}
+        for who, adv, ret, shape in (("a", adv_a, ret_a, (T, E, n)), ("p", adv_p, ret_p, (T, E))):
+            for name, t in (("adv_", adv), ("returns_", ret)):
+                if tuple(t.shape) != shape or not t.is_contiguous():
+                    raise ValueError("Trajectory.ppo_batch: %s%s must be a contiguous tensor of shape %s" % (name, who, shape))
+                out[name + who] = t.flatten(0, 1)
+            out["masks_" + who] = getattr(self, "masks_" + who).flatten(0, 1)
+            out["actions_" + who] = getattr(self, "actions_" + who).flatten(0, 1)
+            out["logp_old_" + who] = getattr(self, "logp_" + who).flatten(0, 1)
+            out["values_old_" + who] = getattr(self, "values_" + who)[:T].flatten(0, 1)
+        return out
+
 
 def _masked_categorical():
     """The autograd Function, built at first use (torch is imported lazily everywhere in this package)."""
@@ -258,9 +277,70 @@ def _masked_categorical():
 _MaskedCategorical = None
 
 
-def __getattr__(name):  # rollout.MaskedCategorical: the class itself, made when first asked for
+def _ppo_loss_function():
+    """The autograd Function of ppo_loss, built at first use."""
+    global _PPOLoss
+    if _PPOLoss is not None:
+        return _PPOLoss
+    import torch
+
+    class PPOLoss(torch.autograd.Function):
+        """Both classes' PPO loss, differentiable in the logits and the values: forward = ONE Backend.ppo_loss call
+        (aie_ppo_loss: two launches, forward and backward together), which already leaves the gradients of the two
+        losses; backward multiplies them by the incoming scalars.  apply(be, logits_a, logits_p, values_a, values_p, batch,
+        index, coefficients, coeffs_p, adv_moments) -> (loss_a, loss_p, stats_a, stats_p)."""
+
+        @staticmethod
+        def forward(ctx, be, logits_a, logits_p, values_a, values_p, batch, index, coefs, coeffs_p, adv_moments):
+            out_a, out_p = be.ppo_loss(logits_a, logits_p, values_a, values_p, batch, index=index, coeffs_p=coeffs_p,
+                                       adv_moments=adv_moments, **coefs)
+            ctx.grads = []
+            res = []
+            for out, lg, val in ((out_a, logits_a, values_a), (out_p, logits_p, values_p)):
+                if out is None:
+                    ctx.grads.append((None, None))
+                    res.append((None, None))
+                    continue
+                stats, g, gv = out
+                ctx.grads.append((g.view(lg.shape), None if gv is None else gv.view(val.shape)))
+                res.append((stats[0].clone(), stats))
+            stats = [r[1] for r in res if r[1] is not None]
+            ctx.mark_non_differentiable(*stats)
+            return res[0][0], res[1][0], res[0][1], res[1][1]
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable  # (the stored gradients are constants: a double backward raises)
+        def backward(ctx, g_loss_a, g_loss_p, _sa, _sp):
+            out = []
+            for (g, gv), up in zip(ctx.grads, (g_loss_a, g_loss_p)):
+                out.append((None if g is None or up is None else g * up, None if gv is None or up is None else gv * up))
+            return None, out[0][0], out[1][0], out[0][1], out[1][1], None, None, None, None, None
+
+    _PPOLoss = PPOLoss
+    return PPOLoss
+
+
+_PPOLoss = None
+
+
+def ppo_loss(be, logits_a, logits_p, values_a, values_p, batch, index=None, clip=0.3, vf_clip=50.0, vf_coef=0.05, ent_coef=0.025,
+             coeffs_p=None, adv_moments=None):
+    """(loss_a, loss_p, stats_a, stats_p): the PPO loss of both actor classes -- the clipped surrogate over the joint
+    log-probability of an actor's action slots, the clipped value loss, the entropy bonus -- as 0-dim tensors that are
+    differentiable in the logits and the values, and each class's statistics (float32 [8]: loss, policy, value, entropy,
+    kl, clip fraction, skipped actors, max |log-ratio|; include/aie.h).  One library call of two launches computes the
+    losses AND their gradients, whatever the batch size; `batch` holds the stored operands (Trajectory.ppo_batch()) and
+    `index` (int32 [B] on the device, or None) picks the minibatch's rows out of them without a copy.  Operands and
+    coefficients: Backend.ppo_loss.  A class whose logits are None gives (None, None)."""
+    coefs = dict(clip=clip, vf_clip=vf_clip, vf_coef=vf_coef, ent_coef=ent_coef)
+    return _ppo_loss_function().apply(be, logits_a, logits_p, values_a, values_p, batch, index, coefs, coeffs_p, adv_moments)
+
+
+def __getattr__(name):  # rollout.MaskedCategorical, rollout.PPOLoss: the classes themselves, made when first asked for
     if name == "MaskedCategorical":
         return _masked_categorical()
+    if name == "PPOLoss":
+        return _ppo_loss_function()
     raise AttributeError(name)
 
 

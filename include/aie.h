@@ -664,6 +664,52 @@ int aie_gae(aie_env* env, int32_t T, const float* d_log, int32_t n_slots, int32_
             const float* d_values_p, float gamma, float lambda, float* d_adv_a, float* d_adv_p, float* d_ret_a, float* d_ret_p,
             void* stream);
 
+/* The PPO loss of both actor classes with its gradients, two launches: the clipped surrogate over the JOINT log-probability
+ * of an actor's action slots, the clipped value loss and the entropy bonus (the loss RLlib's PPO is configured with in the
+ * reference's tutorials: clip_param 0.3, vf_clip_param 50, vf_loss_coeff 0.05, entropy_coeff 0.025; vf_clip = 0 is the plain
+ * squared error), forward and backward together -- what a trainer otherwise writes as several dozen elementwise torch
+ * launches with their autograd twins around aie_policy_evaluate and its backward.
+ *   B batch elements, any B >= 1, not tied to the environment's E.  An ACTOR is one agent, or the planner, of one batch
+ *   element; it has width_a / width_p action slots whose rows are aie_policy_evaluate's.  Per class (aie_ppo_class):
+ *   logits [B, n, MA] / [B, MP], values [B, n] / [B] (NULL: no value term): the network's outputs for batch element b;
+ *   the STORED operands -- masks (the logits' layout), actions and logp_old (int32 / float32 [R, n, width_a] /
+ *   [R, width_p]), adv, values_old, returns (float32 [R, n] / [R]) -- are read at row d_index[b] of tensors of R rows
+ *   (a whole fragment, say), or at row b with d_index NULL: a minibatch is an index, not a copy.  d_index: int32 [B] in
+ *   device memory; a row outside the stored tensors is the caller's error, like a bad pointer;
+ *   adv_moments: NULL, or {mean, rstd} in DEVICE memory: the advantage enters as (A - mean) * rstd;
+ *   grad_logits (the logits' shape), grad_values ([B, n] / [B]; NULL exactly when values is): the gradient of stats[0]
+ *   with respect to the logits and the values, every entry written (exactly 0 at entries the mask does not allow);
+ *   stats: AIE_PPO_N_STATS float32: [0] loss = P + vf_coef V - ent_coef E, [1] P the mean policy term, [2] V the mean value
+ *   term, [3] E the mean joint entropy, [4] the mean of logp_old - logp (the kl estimate), [5] the fraction of actors whose
+ *   ratio left [1 - clip, 1 + clip], [6] the number of skipped actors, [7] the largest |logp - logp_old| of the others.
+ * The means are over all N = B x actors of the class.  An actor whose joint logp or stored old logp is not finite, or whose
+ * log-ratio exceeds 80 in magnitude, is SKIPPED: it adds 0 to [1], [4], [5] and has no policy gradient, but keeps its
+ * entropy and value terms.  csrc/aie_layout.h states every operation (float32, each rounded on its own, in the sampler's
+ * arithmetic: a step evaluated under the logits it was sampled from has ratio exactly 1); the sums are float64 over the
+ * float32 terms in an order that is fixed for a given B, so two runs give the same bits; no atomics.
+ * d_workspace: device memory, 8-byte aligned, the call's own until it has run: calls that may run at the same time (two
+ * streams) need one each, and a captured call keeps the pointer.  Each wavefront (at most AIE_PPO_MAX_WAVES) leaves one partial record of 128 bytes there; the second launch adds them.  The size to give is
+ * what the workspace_bytes function returns for B: never more than AIE_PPO_MAX_WAVES * 128 (1 MiB, enough for every B), or
+ * the negative AIE_E_INVALID for a NULL env or B < 1.
+ * Either class may be NULL; with both NULL the call checks B and the samplers' refusals, launches nothing and returns AIE_OK.  All scenarios.  Asynchronous on `stream`, no allocation, no synchronisation, capturable in a
+ * hipGraph.  AIE_E_INVALID for B < 1, a class without logits, masks, actions, logp_old, adv, grad_logits or stats, values
+ * without values_old, returns or grad_values (or grad_values without values), clip <= 0, a workspace that is NULL,
+ * misaligned or too small; aie_sample_policy_actions' refusals (AIE_E_UNSUPPORTED) apply. */
+#define AIE_PPO_N_STATS 8
+#define AIE_PPO_MAX_WAVES 8192
+typedef struct aie_ppo_class {          /* one actor class; layouts as aie_policy_evaluate, B for E */
+  const float *logits, *values;         /* row b: the network's outputs for batch element b; values NULL: no value term */
+  const float* masks;                   /* the "stored" operands: row d_index[b] */
+  const int32_t* actions;
+  const float *logp_old, *adv, *values_old, *returns;
+  const float* adv_moments;             /* NULL, or 2 floats in device memory {mean, rstd} */
+  float *grad_logits, *grad_values, *stats;   /* the logits' shape, [B, actors], AIE_PPO_N_STATS; grad_values NULL iff values NULL */
+  float clip, vf_clip, vf_coef, ent_coef;
+} aie_ppo_class;
+int64_t aie_ppo_workspace_bytes(const aie_env* env, int64_t B);
+int aie_ppo_loss(aie_env* env, int64_t B, const aie_ppo_class* agents, const aie_ppo_class* planner, const int32_t* d_index,
+                 void* d_workspace, int64_t workspace_bytes, void* stream);
+
 /* Trajectory storage with the slot index on the device: one launch per step copies up to AIE_TRAJ_MAX_SEGMENTS per-replica
  * blocks (observations, masks, actions, log-probabilities, values -- any device memory, arena tensors included) into
  * replica e's slot d_slot[e] of the caller's ring buffers, then d_slot[e] becomes (d_slot[e] + 1) % n_slots.

@@ -1,0 +1,296 @@
+"""The PPO loss, CPU side (csrc/aie_layout.h: aie_ppo_actor_terms, aie_ppo_value_terms, aie_ppo_advantage,
+aie_ppo_finish_stats over aie_policy_row_stats / _logp / _backward -- the twin of aie_ppo_loss):
+
+  * bits: the header's helpers, compiled here with the host C compiler and strung together per actor as the header's
+    comment says, against the Python transcription (tests/ppo_ref.py): per-actor terms, slot gradients and value
+    gradients bit for bit, on row shapes (50,), 7 x (22,), (11,) and a ragged multi-action row set, with every edge of
+    ppo_ref.EDGES planted, r exactly on either clip bound, vf_clip = 0, moments given and absent;
+  * accuracy: gradients and loss against the float64 torch formulation of the same loss (masked_fill(-inf), log_softmax,
+    gather, the sum over slots, the clipped minimum, the clipped value loss, the entropy, autograd), with torch-float32's
+    own error against the same float64 reference as the yardstick: at most 3 x its maximum error, per quantity;
+  * identities: fresh samples give kl 0, clip fraction 0, |d| maximum 0 and the policy gradient
+    -scale A' ([k = a] - p_k) in the header's operation order; masked entries have gradient exactly 0; an invalid actor
+    has no policy gradient but keeps its entropy and value gradients.
+
+Measured ratios (this transcription's max error / torch-float32's max error; 20 calls of 200 actors per set, the maxima
+over all calls -- a call has one loss, and one number's error is no maximum):
+
+    set                     logits' gradient   values' gradient   loss
+    (50,)                   0.92               1.00               0.43
+    7 x (22,)               0.76               1.00               0.66
+    (11,)                   0.96               1.00               0.63
+    ragged (5, 12, 3, 23)   1.02               1.00               0.59
+"""
+import ctypes
+import math
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import policy_eval_ref as pref
+import ppo_ref as ref
+from helpers import ROOT
+
+CSRC = os.path.join(ROOT, "ai-economist_amd", "csrc")
+f32 = np.float32
+
+# The class loss from the header's helpers, actor by actor (sums in actor order: the device's order is its own).
+SHIM = r"""
+#include "aie_layout.h"
+void shim_ppo(const float* x, const float* mask, long N, int W, int w, const int* row_off, const int* row_len, const int* act,
+              const float* lp_old, const float* adv, const float* moments, const float* v, const float* v_old, const float* ret,
+              float clip, float vf_clip, float vf_coef, float ent_coef, float* terms, float* grad, float* grad_v, float* stats) {
+  const float scale = aie_ppo_scale(N), g_H = -aie_ppo_product(scale, ent_coef), kv = aie_ppo_product(scale, vf_coef);
+  double sums[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (long i = 0; i < N; ++i) {
+    const float *xi = x + i * W, *mi = mask + i * W;
+    aie_policy_row R[64];
+    float ln = 0, lo = 0, He = 0;
+    int fin = 1;
+    for (int s = 0; s < w; ++s) {
+      R[s] = aie_policy_row_stats(xi + row_off[s], mi + row_off[s], 1, row_len[s]);
+      const float lp = aie_policy_row_logp(&R[s], xi + row_off[s], mi + row_off[s], 1, row_len[s], act[i * w + s]);
+      const float lold = lp_old[i * w + s];
+      ln = aie_ppo_joint_add(ln, lp, s);
+      lo = aie_ppo_joint_add(lo, lold, s);
+      He = aie_ppo_joint_add(He, R[s].H, s);
+      fin = fin && aie_ppo_finite(lp) && aie_ppo_finite(lold);
+    }
+    const float Ap = aie_ppo_advantage(adv[i], moments != 0, moments ? moments[0] : 0.0f, moments ? moments[1] : 1.0f);
+    const aie_ppo_actor t = aie_ppo_actor_terms(ln, lo, fin, Ap, clip, scale);
+    for (int s = 0; s < w; ++s)
+      aie_policy_row_backward(&R[s], xi + row_off[s], mi + row_off[s], 1, row_len[s], act[i * w + s], t.g_logp, g_H,
+                              grad + i * W + row_off[s]);
+    float vf = 0;
+    if (v) {
+      const aie_ppo_value q = aie_ppo_value_terms(v[i], v_old[i], ret[i], vf_clip, kv);
+      vf = q.vf;
+      grad_v[i] = q.grad;
+    }
+    float* o = terms + 8 * i;
+    o[0] = t.pol; o[1] = t.kl; o[2] = t.clipf; o[3] = t.absd; o[4] = t.g_logp; o[5] = (float)t.valid; o[6] = He; o[7] = vf;
+    sums[1] += t.pol; sums[2] += vf; sums[3] += He; sums[4] += t.kl; sums[5] += t.clipf; sums[6] += !t.valid;
+    sums[7] = t.absd > sums[7] ? t.absd : sums[7];
+  }
+  aie_ppo_finish_stats(sums, (double)N, vf_coef, ent_coef, stats);
+}
+"""
+
+SHAPES = {"(50,)": [(0, 50)], "7 x (22,)": [(22 * s, 22) for s in range(7)], "(11,)": [(0, 11)],
+          "ragged (5, 12, 3, 23)": [(0, 5), (5, 12), (17, 3), (20, 23)]}
+COEFS = dict(clip=0.3, vf_clip=50.0, vf_coef=0.05, ent_coef=0.025)
+
+
+@pytest.fixture(scope="module")
+def shim():
+    with tempfile.TemporaryDirectory() as d:
+        src, so = os.path.join(d, "shim.c"), os.path.join(d, "shim.so")
+        with open(src, "w") as f:
+            f.write(SHIM)
+        subprocess.run(["gcc", "-O2", "-mfma", "-ffp-contract=off", "-shared", "-fPIC", "-I" + CSRC,
+                        "-I" + os.path.join(ROOT, "include"), src, "-o", so, "-lm"], check=True)
+        lib = ctypes.CDLL(so)
+        fp, ip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)
+        lib.shim_ppo.argtypes = [fp, fp, ctypes.c_long, ctypes.c_int, ctypes.c_int, ip, ip, ip, fp, fp, fp, fp, fp, fp,
+                                 ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, fp, fp, fp, fp]
+        yield lib
+
+
+def _fp(a):
+    return None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
+def _ip(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+
+
+def bits(a):
+    return np.ascontiguousarray(a, f32).view(np.uint32)
+
+
+def c_ppo(lib, rows, batch, clip, vf_clip, vf_coef, ent_coef, moments=None, values=True):
+    """The header's loss of a batch ([B, A, ...] operands) -> (terms [N, 8], grad, grad_v, stats)."""
+    B, A, W = batch["logits"].shape
+    N, w = B * A, len(rows)
+    c = {k: np.ascontiguousarray(v, np.int32 if k == "actions" else f32) for k, v in batch.items()}
+    off, ln = np.array([r[0] for r in rows], np.int32), np.array([r[1] for r in rows], np.int32)
+    mom = None if moments is None else np.array(moments, f32)
+    terms, grad, grad_v, stats = np.empty((N, 8), f32), np.full((N, W), np.nan, f32), np.full(N, np.nan, f32), np.empty(8, f32)
+    lib.shim_ppo(_fp(c["logits"]), _fp(c["masks"]), N, W, w, _ip(off), _ip(ln), _ip(c["actions"]), _fp(c["logp_old"]), _fp(c["adv"]),
+                 _fp(mom), _fp(c["values"]) if values else None, _fp(c["values_old"]), _fp(c["returns"]), clip, vf_clip, vf_coef,
+                 ent_coef, _fp(terms), _fp(grad), _fp(grad_v), _fp(stats))
+    return terms, grad.reshape(B, A, W), grad_v.reshape(B, A) if values else None, stats
+
+
+def _want(rows, batch, clip, vf_clip, vf_coef, ent_coef, moments=None, values=True):
+    return ref.ppo_class(rows, batch["logits"], batch["masks"], batch["actions"], batch["logp_old"], batch["adv"],
+                         batch["values"] if values else None, batch["values_old"], batch["returns"], clip, vf_clip, vf_coef,
+                         ent_coef, moments)
+
+
+def _hold(got, want, what):
+    terms, grad, grad_v, stats = got
+    for j, k in enumerate(("pol", "kl", "clipf", "absd", "g_logp")):
+        bad = np.flatnonzero(bits(terms[:, j]) != bits(want[k]))
+        assert bad.size == 0, "%s: per-actor %s differs at actors %s" % (what, k, bad[:5])
+    assert np.array_equal(terms[:, 5] != 0, want["valid"]), what
+    assert np.array_equal(bits(terms[:, 6]), bits(want["He"])), what
+    assert np.array_equal(bits(terms[:, 7]), bits(want["vf"])), what
+    assert np.array_equal(bits(grad), bits(want["grad"])), what + ": slot gradients"
+    if want["grad_v"] is not None:
+        assert np.array_equal(bits(grad_v), bits(want["grad_v"])), what + ": value gradients"
+    assert stats[6] == want["stats"][6] and bits(stats[7]) == bits(want["stats"][7]), what
+    err = np.abs(stats[:6].astype(np.float64) - want["stats"][:6].astype(np.float64))
+    assert (err <= want["tol"][:6]).all(), "%s: stats %s, want %s, bound %s" % (what, stats[:6], want["stats"][:6], want["tol"][:6])
+
+
+@pytest.mark.parametrize("moments", [None, (0.3, 1.7)], ids=["no_moments", "moments"])
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_header_equals_its_transcription_bit_for_bit(shim, shape, moments):
+    rows = SHAPES[shape]
+    W = sum(ln for _, ln in rows)
+    batch = ref.random_batch(rows, W, 20, 3, seed=len(shape))
+    where = ref.plant_edges(rows, batch, seed=5, vf_clip=COEFS["vf_clip"], moments=moments)
+    assert set(where) == set(ref.EDGES)
+    # r exactly on a clip bound: 1 - r and r - 1 are exact in float32 (r within a factor 2 of 1)
+    r_lo, r_hi = ref.ratio_of(rows, batch, where["r_at_lo"]), ref.ratio_of(rows, batch, where["r_at_hi"])
+    assert 0.5 < r_lo < 1 < r_hi < 2
+    for what, co in (("reference coefficients", COEFS), ("r at lo_c", dict(COEFS, clip=float(f32(1) - r_lo))),
+                     ("r at hi_c", dict(COEFS, clip=float(r_hi - f32(1)))), ("vf_clip 0", dict(COEFS, vf_clip=0.0)),
+                     ("no values", COEFS)):
+        values = what != "no values"
+        want = _want(rows, batch, moments=moments, values=values, **co)
+        _hold(c_ppo(shim, rows, batch, moments=moments, values=values, **co), want, "%s, %s" % (shape, what))
+        i = where
+        valid, r = want["valid"], want["r"]
+        # ---- the edges are what they are meant to be ----
+        for e in ("disallowed_action", "action_past_row", "action_negative", "old_logp_minus_inf", "d_outside_plus", "d_outside_minus"):
+            assert not valid[i[e]], e
+        for e in ("nan_logits", "masked_slot", "masked_all", "d_inside_plus", "d_inside_minus", "adv_zero", "fresh", "r_at_lo", "r_at_hi"):
+            assert valid[i[e]], e
+        assert want["stats"][6] == 6
+        assert 79.8 < want["d"][i["d_inside_plus"]] <= 80 and -80 <= want["d"][i["d_inside_minus"]] < -79.8
+        assert want["d"][i["d_outside_plus"]] > 80 and want["d"][i["d_outside_minus"]] < -80
+        assert want["logp"][i["masked_slot"], 0] == 0 and want["H"][i["masked_slot"], 0] == 0
+        assert not want["grad"].reshape(len(valid), W)[i["masked_all"]].any() and want["He"][i["masked_all"]] == 0
+        assert want["Ap"][i["adv_zero"]] == 0 and want["pol"][i["adv_zero"]] == 0 and want["unclipped"][i["adv_zero"]]
+        assert r[i["fresh"]] == 1 and want["d"][i["fresh"]] == 0 and want["unclipped"][i["fresh"]]  # u == c: the tie goes to u
+        if what == "r at lo_c":
+            assert r[i["r_at_lo"]] == want["lo_c"] and want["clipf"][i["r_at_lo"]] == 0 and want["unclipped"][i["r_at_lo"]]
+        if what == "r at hi_c":
+            assert r[i["r_at_hi"]] == want["hi_c"] and want["clipf"][i["r_at_hi"]] == 0 and want["unclipped"][i["r_at_hi"]]
+        if what == "reference coefficients":
+            # a clipped ratio keeps its gradient exactly when the unclipped product is the smaller one
+            assert want["clipf"][i["clipped_low_adv_pos"]] == 1 and want["unclipped"][i["clipped_low_adv_pos"]]
+            assert want["clipf"][i["clipped_low_adv_neg"]] == 1 and not want["unclipped"][i["clipped_low_adv_neg"]]
+            assert want["clipf"][i["clipped_high_adv_pos"]] == 1 and not want["unclipped"][i["clipped_high_adv_pos"]]
+            assert want["clipf"][i["clipped_high_adv_neg"]] == 1 and want["unclipped"][i["clipped_high_adv_neg"]]
+            assert want["g_logp"][i["clipped_low_adv_neg"]] == 0 and want["g_logp"][i["clipped_high_adv_neg"]] != 0
+            gv, kv = want["grad_v"].reshape(-1), want["kv"]
+            v, vo, rt = (batch[k].reshape(-1) for k in ("values", "values_old", "returns"))
+            for e in ("q_tie", "dv_at_plus_clip", "dv_at_minus_clip", "dv_past_clip_first"):  # the gradient flows: kv * 2 e1
+                e1 = f32(v[i[e]] - rt[i[e]])
+                assert bits(gv[i[e]]) == bits(f32(kv * f32(e1 + e1))), e
+            assert abs(v[i["dv_at_plus_clip"]] - vo[i["dv_at_plus_clip"]]) == f32(50) == abs(v[i["dv_at_minus_clip"]] - vo[i["dv_at_minus_clip"]])
+            assert gv[i["dv_past_clip_second"]] == 0 and want["vf"][i["dv_past_clip_second"]] > 0
+        if what == "vf_clip 0":
+            gv, v, rt = want["grad_v"].reshape(-1), batch["values"].reshape(-1), batch["returns"].reshape(-1)
+            e1 = (v - rt).astype(f32)
+            assert np.array_equal(bits(gv), bits((want["kv"] * (e1 + e1).astype(f32)).astype(f32)))
+            assert np.array_equal(bits(want["vf"]), bits((e1 * e1).astype(f32)))
+        if what == "no values":
+            assert want["stats"][2] == 0
+
+
+def _torch_loss(rows, batch, clip, vf_clip, vf_coef, ent_coef, dtype):
+    """The same loss as plain torch in `dtype`: (loss, d loss / d logits, d loss / d values) as float64 numpy."""
+    import torch
+
+    B, A, W = batch["logits"].shape
+    x = torch.tensor(batch["logits"], dtype=dtype, requires_grad=True)
+    v = torch.tensor(batch["values"], dtype=dtype, requires_grad=True)
+    allowed = torch.tensor(batch["masks"] > 0.5)
+    act = torch.tensor(batch["actions"], dtype=torch.int64)
+    t = lambda k: torch.tensor(batch[k], dtype=dtype)  # noqa: E731
+    logp = ent = 0
+    for s, (lo, ln) in enumerate(rows):
+        ok = allowed[..., lo:lo + ln]
+        lsm = torch.log_softmax(x[..., lo:lo + ln].masked_fill(~ok, -math.inf), -1)
+        logp = logp + lsm.gather(-1, act[..., s:s + 1])[..., 0]
+        ent = ent - (lsm.exp() * lsm.masked_fill(~ok, 0.0)).sum(-1)
+    ratio = (logp - t("logp_old").sum(-1)).exp()
+    adv = t("adv")
+    pol = -torch.min(ratio * adv, ratio.clamp(1 - clip, 1 + clip) * adv).mean()
+    vc = t("values_old") + (v - t("values_old")).clamp(-vf_clip, vf_clip)
+    vf = torch.max((v - t("returns")) ** 2, (vc - t("returns")) ** 2).mean()
+    loss = pol + vf_coef * vf - ent_coef * ent.mean()
+    loss.backward()
+    return float(loss.detach().double()), x.grad.double().numpy(), v.grad.double().numpy()
+
+
+ACTORS = 4000
+BATCHES = 20
+FACTOR = 3.0  # the project's yardstick (tests/test_policy_evaluate_cpu.py): <= 3 x torch-float32's own max error
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_accuracy_against_float64_with_torch_float32_as_the_yardstick(shape):
+    import torch
+
+    rows = SHAPES[shape]
+    W = sum(ln for _, ln in rows)
+    names = ("loss", "logits' gradient", "values' gradient")
+    eo, et = np.zeros(3), np.zeros(3)
+    # BATCHES calls of ACTORS / BATCHES actors each: a call has ONE loss, and one number's error is no maximum
+    for k in range(BATCHES):
+        batch = ref.random_batch(rows, W, ACTORS // BATCHES // 4, 4, seed=100 * k + len(shape))  # nothing invalid, no ties
+        # the float64 reference takes the float32 inputs as they are (its old logp: the float32 slots, summed in float64)
+        ours = _want(rows, batch, **COEFS)
+        assert ours["valid"].all() and not (ours["r"] == 1).any()
+        want = _torch_loss(rows, batch, dtype=torch.float64, **COEFS)
+        t32 = _torch_loss(rows, batch, dtype=torch.float32, **COEFS)
+        got = (float(ours["stats"][0]), ours["grad"].astype(np.float64), ours["grad_v"].astype(np.float64))
+        assert not ours["grad"][batch["masks"] < 0.5].any()
+        for j, (o, t, w) in enumerate(zip(got, t32, want)):
+            eo[j], et[j] = max(eo[j], np.abs(np.asarray(o) - w).max()), max(et[j], np.abs(np.asarray(t) - w).max())
+    for j, name in enumerate(names):
+        print("%s %-18s ours %.3e  torch-float32 %.3e  ratio %.2f" % (shape, name, eo[j], et[j], eo[j] / et[j]))
+    for j, name in enumerate(names):
+        assert eo[j] <= FACTOR * et[j], "%s %s: %.2f x torch-float32's max error" % (shape, name, eo[j] / et[j])
+
+
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_identities(shim, shape):
+    rows = SHAPES[shape]
+    W = sum(ln for _, ln in rows)
+    batch = ref.random_batch(rows, W, 30, 2, seed=3)
+    N = 60
+    x, m, act = batch["logits"].reshape(N, W), batch["masks"].reshape(N, W), batch["actions"].reshape(N, len(rows))
+    batch["logp_old"] = ref.slot_terms(rows, x, m, act)[0].reshape(batch["logp_old"].shape)  # fresh samples
+    terms, grad, grad_v, stats = c_ppo(shim, rows, batch, **COEFS)
+    assert stats[4] == 0 and stats[5] == 0 and stats[6] == 0 and stats[7] == 0
+    assert not terms[:, 1].any() and terms[:, 5].all()
+    # the policy gradient is -scale A' ([k = a] - p_k) in the header's order: the same call without the entropy term
+    t2, g_pol, _, _ = c_ppo(shim, rows, batch, **dict(COEFS, ent_coef=0.0))
+    scale = f32(f32(1.0) / f32(N))
+    gl = (-(scale * (f32(1.0) * batch["adv"].reshape(N))).astype(f32)).astype(f32)
+    assert np.array_equal(bits(t2[:, 4]), bits(gl))
+    for s, (lo, ln) in enumerate(rows):
+        S = pref.rows_stats(x[:, lo:lo + ln], m[:, lo:lo + ln])
+        p = (S["w"] / S["Ts"][:, None]).astype(f32)
+        ind = (np.arange(ln)[None, :] == act[:, s:s + 1]).astype(f32)
+        a1 = (gl[:, None] * (ind - p).astype(f32)).astype(f32)
+        want = np.where(S["ok"], (a1 - f32(0.0)).astype(f32), f32(0.0))  # (t3 = -0 * t2: a1 - 0 whatever its sign)
+        assert np.array_equal(want, g_pol.reshape(N, W)[:, lo:lo + ln]), (shape, s)
+    assert not grad.reshape(N, W)[m < 0.5].any() and np.array_equal(bits(grad.reshape(N, W)[m < 0.5]), np.zeros((m < 0.5).sum(), np.uint32))
+    # an invalid actor: no policy gradient, but its entropy and value gradients stay
+    batch["logp_old"].reshape(N, -1)[7, 0] = -np.inf
+    terms, grad, grad_v, stats = c_ppo(shim, rows, batch, **COEFS)
+    assert stats[6] == 1 and terms[7, 5] == 0 and terms[7, 4] == 0 and terms[7, 0] == 0
+    only_entropy = ref.ppo_class(rows, batch["logits"], batch["masks"], batch["actions"], batch["logp_old"], np.zeros_like(batch["adv"]),
+                                 batch["values"], batch["values_old"], batch["returns"], **COEFS)
+    assert np.array_equal(bits(grad.reshape(N, W)[7]), bits(only_entropy["grad"].reshape(N, W)[7])) and grad.reshape(N, W)[7].any()
+    assert bits(grad_v.reshape(N)[7]) == bits(only_entropy["grad_v"].reshape(N)[7]) and grad_v.reshape(N)[7] != 0
