@@ -11,6 +11,7 @@
 #include "aie_kernels_ose.hip"
 #include "aie_kernels_saez.hip"
 #include "aie_kernels_ppo.hip"
+#include "aie_kernels_mlp.hip"
 #include "aie_kernels_covid.hip"  // last: switches FP contraction off for the rest of the TU
 #include "aie_jit.h"
 
@@ -1184,6 +1185,65 @@ int aie_ppo_loss(aie_env* env, int64_t B, const aie_ppo_class* agents, const aie
   }
   hipLaunchKernelGGL(aie_ppo_loss_kernel, dim3((A.waves + 3u) / 4u), dim3(256), 0, static_cast<hipStream_t>(stream), A);
   hipLaunchKernelGGL(aie_ppo_reduce_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), A);
+  AIE_HIP_CHECK(env, hipGetLastError());
+  return AIE_OK;
+}
+
+int aie_policy_mlp_forward(aie_env* env, int64_t B, const aie_mlp_class* agents, const aie_mlp_class* planner, void* stream) {
+  if (!env) return AIE_E_INVALID;
+  if (B < 1) {
+    snprintf(env->err, sizeof(env->err), "aie_policy_mlp_forward: B = %lld (needs B >= 1)", (long long)B);
+    return AIE_E_INVALID;
+  }
+  constexpr int TM = AIE_MLP_TILE_ROWS;
+  static_assert(TM == 32 || TM == 64, "the kernel's row tile is 2 or 4 MFMA tiles");
+  const aie_mlp_class* cls[2] = {agents, planner};
+  aie_mlp_args A;
+  memset(&A, 0, sizeof(A));
+  aie_mlp_group* grp[2] = {&A.agents, &A.planner};
+  size_t lds = 0;
+  int64_t blocks = 0;
+  for (int c = 0; c < 2; ++c) {
+    const aie_mlp_class* k = cls[c];
+    if (!k) continue;
+    const char* who = c ? "planner's" : "agents'";
+    if (k->F < 1 || k->F > 1024 || k->M < 1 || k->M > 1024 || k->x_ld < k->F || !k->x || !k->w1 || !k->b1 || !k->w2 || !k->b2 ||
+        !k->w3 || !k->b3 || !k->logits || (k->wv != nullptr) != (k->values != nullptr) || (k->wv != nullptr) != (k->bv != nullptr)) {
+      snprintf(env->err, sizeof(env->err), "aie_policy_mlp_forward: the %s class needs F (%d) and M (%d) in 1 .. 1024, x_ld (%lld) >= F, "
+               "x, w1, b1, w2, b2, w3, b3 and logits, and wv, bv and values all three or none", who, k->F, k->M, (long long)k->x_ld);
+      return AIE_E_INVALID;
+    }
+    if (k->H < 16 || k->H > 256 || (k->H & 15)) {
+      snprintf(env->err, sizeof(env->err), "aie_policy_mlp_forward: the %s hidden width %d is not a multiple of 16 in 16 .. 256", who, k->H);
+      return AIE_E_UNSUPPORTED;
+    }
+    aie_mlp_group& G = *grp[c];
+    G.x = k->x, G.x_ld = k->x_ld;
+    G.w1 = k->w1, G.b1 = k->b1, G.w2 = k->w2, G.b2 = k->b2, G.w3 = k->w3, G.b3 = k->b3, G.wv = k->wv, G.bv = k->bv;
+    G.logits = k->logits, G.values = k->values;
+    G.F = k->F, G.H = k->H, G.M = k->M;
+    G.rows = c ? B : B * (int64_t)env->P.n;
+    const int kpad = (k->F + 3) & ~3, chunk = kpad < AIE_MLP_CHUNK ? kpad : AIE_MLP_CHUNK;
+    G.lds_a = (chunk > k->H ? chunk : k->H) + 2;
+    G.lds_h = k->H + 2;
+    const int64_t nb = (G.rows + TM - 1) / TM;
+    if (nb > 0x3fffffffll) {
+      snprintf(env->err, sizeof(env->err), "aie_policy_mlp_forward: B = %lld is more than one launch takes", (long long)B);
+      return AIE_E_INVALID;
+    }
+    G.blocks = (int32_t)nb;
+    blocks += nb;
+    const size_t need = (size_t)TM * (size_t)(G.lds_a + G.lds_h) * sizeof(float);
+    lds = need > lds ? need : lds;
+  }
+  if (!blocks) return AIE_OK;
+  if (blocks > 0x7fffff00ll) {
+    snprintf(env->err, sizeof(env->err), "aie_policy_mlp_forward: B = %lld is more than one launch takes (%lld workgroups)",
+             (long long)B, (long long)blocks);
+    return AIE_E_INVALID;
+  }
+  AIE_HIP_CHECK(env, hipSetDevice(env->device));
+  hipLaunchKernelGGL(aie_policy_mlp_kernel, dim3((unsigned)blocks), dim3(256), lds, static_cast<hipStream_t>(stream), A);
   AIE_HIP_CHECK(env, hipGetLastError());
   return AIE_OK;
 }

@@ -1915,6 +1915,52 @@ typedef struct aie_ppo_args {
   int32_t act_a_width, ragged;
 } aie_ppo_args;
 #define AIE_PPO_RECORD 16 /* float64 per wavefront's record */
+
+/* The policy network's forward pass (include/aie.h: aie_policy_mlp_forward), stated once -- the kernel's MFMA chains equal
+ * these helpers value for value, tests/test_policy_mlp_cpu.py compiles them with the host compiler against an independent
+ * transcription (tests/policy_mlp_ref.py).  A row x[F] goes through two hidden layers of width H and a head of width M,
+ * with an optional value column; every number is float32:
+ *   chain(c; a, w) = acc, where acc = c and then, for k = 0, 1, ... ascending, acc = fmaf(a[k], w[k], acc): ONE accumulator,
+ *                    one rounding per term, nothing wider in between and no other order;
+ *   relu(v)        = v > 0 ? v : 0 (so a NaN becomes 0);
+ *   h1[j] = relu(chain(b1[j]; x, column j of W1)),  h2[j] = relu(chain(b2[j]; h1, column j of W2)),
+ *   logits[j] = chain(b3[j]; h2, column j of W3),   value = chain(bv; h2, wv).
+ * Weights are row-major [in, out] with a leading dimension (entry (k, j) at w[k * ld + j]): what x @ w takes.
+ * A kernel may append terms with a zero weight behind the real ones (K padded to the MFMA's depth): fmaf(a, 0, acc) = acc
+ * for finite a, except that an accumulator of -0 becomes +0 -- so the device equals these helpers under float ==, with no
+ * NaN anywhere, not in the bit pattern of an exact zero.  It may not split K across accumulators. */
+AIE_HD static inline float aie_mlp_relu(float v) { return v > 0.0f ? v : 0.0f; }
+AIE_HD static inline float aie_mlp_chain(float c, const float* a, const float* w, int64_t w_ld, int K) {
+  float acc = c;
+  for (int k = 0; k < K; ++k) acc = fmaf(a[k], w[(int64_t)k * w_ld], acc);
+  return acc;
+}
+/* one row; h1 and h2 are the caller's scratch of H floats each; wv NULL: no value (value is not written) */
+AIE_HD static inline void aie_mlp_row(const float* x, int F, int H, int M, const float* w1, const float* b1, const float* w2,
+                                      const float* b2, const float* w3, const float* b3, const float* wv, const float* bv,
+                                      float* h1, float* h2, float* logits, float* value) {
+  for (int j = 0; j < H; ++j) h1[j] = aie_mlp_relu(aie_mlp_chain(b1[j], x, w1 + j, H, F));
+  for (int j = 0; j < H; ++j) h2[j] = aie_mlp_relu(aie_mlp_chain(b2[j], h1, w2 + j, H, H));
+  for (int j = 0; j < M; ++j) logits[j] = aie_mlp_chain(b3[j], h2, w3 + j, M, H);
+  if (wv) *value = aie_mlp_chain(bv[0], h2, wv, 1, H);
+}
+/* The kernel's argument (aie_policy_mlp_forward fills it).  A workgroup owns AIE_MLP_TILE_ROWS rows of one class: workgroups
+ * [0, agents.blocks) the agents' tiles, the rest the planner's.  lds_a / lds_h: the row strides (floats) of its two LDS
+ * images, [tile][lds_a] (the observation chunk, later h2) and [tile][lds_h] (h1); both are 2 mod 4, which spreads a
+ * fragment read's 16 rows x 2 columns over 32 banks. */
+#ifndef AIE_MLP_TILE_ROWS
+#define AIE_MLP_TILE_ROWS 32   /* rows per workgroup, 32 or 64 (DESIGN.md section 3 has the measurement behind the choice) */
+#endif
+#define AIE_MLP_CHUNK 256      /* observation columns staged at a time: F <= 256 is one chunk */
+typedef struct aie_mlp_group {
+  const float *x, *w1, *b1, *w2, *b2, *w3, *b3, *wv, *bv;
+  float *logits, *values;
+  int64_t x_ld, rows;
+  int32_t F, H, M, blocks, lds_a, lds_h;
+} aie_mlp_group;
+typedef struct aie_mlp_args {
+  aie_mlp_group agents, planner;
+} aie_mlp_args;
 /* aie_trajectory_store's kernel argument: the caller's segments (include/aie.h: aie_traj_segment, 32 bytes each) with the
  * copy width decided on the host: wide != 0 = 16-byte lane accesses (source, destination, stride and size allow it for
  * every replica and slot), else 4-byte ones. */

@@ -597,6 +597,72 @@ class DeviceBackend:
                                           C.c_void_p(ws.data_ptr()), C.c_int64(ws.numel() * 8), self._stream()))
         return outs[0], outs[1]
 
+    def policy_mlp_forward(self, x_a, x_p, weights_a, weights_p, out=None):
+        """aie_policy_mlp_forward: both classes' policy network -- x -> relu -> H -> relu -> H -> logits (+ value) -- in ONE
+        launch on the current stream.  x_a [B * n, F_a] (or [B, n, F_a]) and x_p [B, F_p]: float32 device tensors whose rows
+        are contiguous (any row stride: an arena tensor, a sliced view); a class whose x is None is left out.  weights_*:
+        a mapping (or rollout.mlp_weights) with float32 device tensors w1 [F, H], b1 [H], w2 [H, H], b2 [H], w3 [H, M],
+        b3 [M], contiguous, and optionally wv [H] (or [H, 1]) with bv [1]: the value column.  The library reads them where
+        they lie at every launch: update them in place and the next launch, or graph replay, sees the new values.
+        Returns (logits_a [rows, M_a], logits_p [B, M_p], value_a [rows], value_p [B]) -- None for a class left out and for a
+        value without wv; out=(logits_a, logits_p, value_a, value_p) fills the caller's contiguous float32 tensors instead
+        (nothing is allocated).  The arithmetic contract (one ascending fmaf chain per output) is include/aie.h's."""
+        torch = _torch()
+        f = dict(dtype=torch.float32, device=self.device)
+        out = tuple(out) if out is not None else (None,) * 4
+        classes, res, Bs = [], [], set()
+        for who, x, w, per, o_l, o_v in (("a", x_a, weights_a, self.n, out[0], out[2]), ("p", x_p, weights_p, 1, out[1], out[3])):
+            if x is None:
+                classes.append(None)
+                res.append((None, None))
+                continue
+            get = w.get if hasattr(w, "get") else lambda k, w=w: getattr(w, k, None)  # noqa: E731
+            if x.dim() == 3:  # [B, n, F] with one row stride throughout: a view, never a copy
+                if x.shape[0] > 1 and x.stride(0) != x.shape[1] * x.stride(1):
+                    raise ValueError("policy_mlp_forward: x_%s [B, n, F] needs one row stride throughout (strides %s)"
+                                     % (who, tuple(x.stride())))
+                x = x.as_strided((x.shape[0] * x.shape[1], x.shape[2]), (x.stride(1), x.stride(2)), x.storage_offset())
+            if x.dim() != 2 or x.dtype != torch.float32 or x.device != self.device or (x.shape[1] > 1 and x.stride(1) != 1) \
+                    or x.shape[0] == 0 or x.shape[0] % per:
+                raise ValueError("policy_mlp_forward: x_%s is a float32 device tensor [B x %d, F] with contiguous rows" % (who, per))
+            rows, F = int(x.shape[0]), int(x.shape[1])
+            x_ld = int(x.stride(0)) if rows > 1 else F
+            t = {k: get(k) for k in ("w1", "b1", "w2", "b2", "w3", "b3", "wv", "bv")}
+            H = int(t["w1"].shape[-1]) if t["w1"] is not None and t["w1"].dim() == 2 else 0
+            M = int(t["w3"].shape[-1]) if t["w3"] is not None and t["w3"].dim() == 2 else 0
+            for k, shape in (("w1", (F, H)), ("b1", (H,)), ("w2", (H, H)), ("b2", (H,)), ("w3", (H, M)), ("b3", (M,)),
+                             ("wv", (H,)), ("bv", (1,))):
+                v = t[k]
+                if v is None and k in ("wv", "bv"):
+                    continue
+                if (v is None or v.dtype != torch.float32 or v.device != self.device or not v.is_contiguous()
+                        or v.numel() != int(np.prod(shape)) or (v.dim() == 2 and k != "wv" and tuple(v.shape) != shape)):
+                    raise ValueError("policy_mlp_forward: weights_%s[%r] must be a contiguous float32 device tensor of shape %s"
+                                     % (who, k, shape))
+            if (t["wv"] is None) != (t["bv"] is None):
+                raise ValueError("policy_mlp_forward: weights_%s needs wv and bv together" % who)
+            has_v = t["wv"] is not None
+            for o, numel, what in ((o_l, rows * M, "logits"), (o_v, rows, "value")):
+                if o is not None and (o.dtype != torch.float32 or o.device != self.device or not o.is_contiguous() or o.numel() != numel):
+                    raise ValueError("policy_mlp_forward: out's %s_%s must be a contiguous float32 device tensor of %d elements"
+                                     % (what, who, numel))
+            logits = o_l if o_l is not None else torch.empty((rows, M), **f)
+            value = (o_v if o_v is not None else torch.empty((rows,), **f)) if has_v else None
+            ptr = lambda v: v.data_ptr() if v is not None else None  # noqa: E731
+            classes.append(_cabi.AieMlpClass(x=x.data_ptr(), x_ld=x_ld, w1=ptr(t["w1"]), b1=ptr(t["b1"]), w2=ptr(t["w2"]),
+                                             b2=ptr(t["b2"]), w3=ptr(t["w3"]), b3=ptr(t["b3"]), wv=ptr(t["wv"]), bv=ptr(t["bv"]),
+                                             logits=logits.data_ptr(), values=ptr(value), F=F, H=H, M=M))
+            res.append((logits, value))
+            Bs.add(rows // per)
+        if not Bs:
+            raise ValueError("policy_mlp_forward: no actor class")
+        if len(Bs) != 1:
+            raise ValueError("policy_mlp_forward: the classes disagree on the batch size (%s)" % sorted(Bs))
+        ref = lambda c: C.byref(c) if c is not None else None  # noqa: E731
+        self._check(self.lib.aie_policy_mlp_forward(self.handle, C.c_int64(Bs.pop()), ref(classes[0]), ref(classes[1]),
+                                                    self._stream()))
+        return res[0][0], res[1][0], res[0][1], res[1][1]
+
     def _action_buffers(self, slot):
         torch = _torch()
         if self._rand_a is None:

@@ -353,6 +353,50 @@ def masked_logp_entropy(be, logits_a, logits_p, masks_a, masks_p, actions_a, act
     return _masked_categorical().apply(be, logits_a, logits_p, masks_a, masks_p, actions_a, actions_p)
 
 
+class mlp_weights:
+    """The [in, out] float32 tensors Backend.policy_mlp_forward takes, made from three torch.nn.Linear (plus an optional
+    value Linear of one output) -- or from their (weight, bias) tensor pairs in Linear's [out, in] layout: transposed
+    COPIES on the module's device, so refresh() must be called after every optimizer step (it copies in place: the
+    tensors keep their addresses, a captured launch sees the new values on its next replay).  A trainer that keeps its
+    parameters as [in, out] needs none of this: it hands a dict of its own tensors to policy_mlp_forward, no copy.
+    Attributes (and get(name)): w1, b1, w2, b2, w3, b3, wv, bv (the last two None without a value layer)."""
+
+    NAMES = ("w1", "b1", "w2", "b2", "w3", "b3", "wv", "bv")
+
+    def __init__(self, l1, l2, l3, value=None):
+        import torch
+
+        def pair(m):
+            return (m.weight, m.bias) if hasattr(m, "weight") else tuple(m)
+
+        self._src = [pair(m) for m in (l1, l2, l3)] + ([pair(value)] if value is not None else [])
+        for w, b in self._src:
+            if w.dim() != 2 or b is None or w.dtype != torch.float32:
+                raise ValueError("mlp_weights: float32 Linear layers with a bias")
+        if value is not None and self._src[3][0].shape[0] != 1:
+            raise ValueError("mlp_weights: the value layer has one output")
+        self.wv = self.bv = None
+        with torch.no_grad():
+            for i, (w, b) in enumerate(self._src):
+                wt = torch.empty((w.shape[1], w.shape[0]), dtype=w.dtype, device=w.device).copy_(w.detach().t())  # (never a view)
+                name = ("1", "2", "3", "v")[i]
+                setattr(self, "w" + name, wt.view(-1) if name == "v" else wt)
+                setattr(self, "b" + name, b.detach().clone().view(-1))
+
+    def get(self, name, default=None):
+        return getattr(self, name, default) if name in self.NAMES else default
+
+    def refresh(self):
+        """Copies the modules' current parameters into the same tensors, in place."""
+        import torch
+
+        with torch.no_grad():
+            for (w, b), name in zip(self._src, ("1", "2", "3", "v")):
+                getattr(self, "w" + name).view(w.shape[1], w.shape[0]).copy_(w.detach().t())
+                getattr(self, "b" + name).copy_(b.detach().view(-1))
+        return self
+
+
 class MaskedMLPPolicy:
     """A small policy network of the shape the reference's trainers use on the flat observations (fully connected
     trunk, one categorical head per action subspace, `action_mask` applied to the logits: base_env.py:141-145,
@@ -367,10 +411,15 @@ class MaskedMLPPolicy:
     actor class) for comparison.
     value_head=True: one more output column per actor class (the critic), written in place on every call into the fixed
     float32 tensors `value_a` [E, n] and `value_p` [E] -- what rollout.Trajectory stores beside the actions.  Its weights
-    are drawn behind the six layers', so the policy's own weights do not depend on it."""
+    are drawn behind the six layers', so the policy's own weights do not depend on it.
+    network="library": logits() is ONE Backend.policy_mlp_forward call (aie_policy_mlp_forward: both classes' three
+    layers and value columns in one launch, float32, every output one ascending fmaf chain from its bias) that reads the
+    arena's observations and this object's weight tensors where they lie and writes the fixed buffers `logits_a` /
+    `logits_p` and `value_a` / `value_p` in place; a call of the policy is then two launches, the network and the sampler.
+    float32 only.  The default "torch" path is unchanged."""
 
     def __init__(self, be, hidden=128, seed=0, dtype=None, sampler="library", sample_seed=1234, record_logp=False,
-                 value_head=False):
+                 value_head=False, network="torch"):
         import torch
 
         self.torch = torch
@@ -419,6 +468,20 @@ class MaskedMLPPolicy:
             aa, ap = be._action_buffers(0)
             self.logp_a = torch.zeros(aa.shape, dtype=torch.float32, device=dev)
             self.logp_p = torch.zeros(ap.shape, dtype=torch.float32, device=dev)
+        if network not in ("torch", "library"):
+            raise ValueError("MaskedMLPPolicy: network is 'torch' or 'library'")
+        self.network = network
+        if network == "library":
+            if dtype != torch.float32:
+                raise ValueError("MaskedMLPPolicy(network='library'): float32 weights (dtype %s given)" % dtype)
+            names = ("w1", "b1", "w2", "b2", "w3", "b3")
+            self.weights_a = dict(zip(names, (self.wa1, self.ba1, self.wa2, self.ba2, self.wa3, self.ba3)))
+            self.weights_p = dict(zip(names, (self.wp1, self.bp1, self.wp2, self.bp2, self.wp3, self.bp3)))
+            if self.value_head:  # (views of the [hidden, 1] columns: an in-place update reaches them)
+                self.weights_a.update(wv=self.wav.view(-1), bv=self.bav)
+                self.weights_p.update(wv=self.wpv.view(-1), bv=self.bpv)
+            self.logits_a = torch.zeros((be.E * be.n, MA), dtype=torch.float32, device=dev)
+            self.logits_p = torch.zeros((be.E, MP), dtype=torch.float32, device=dev)
         self._fused_relu = None  # decided at the first call (outside any capture: GraphedStep warms the policy up first)
         self.counter = torch.zeros((), dtype=torch.float32, device=dev)
         if sampler == "torch":
@@ -451,6 +514,13 @@ class MaskedMLPPolicy:
     def logits(self, tensors):
         """(agents' logits [E * n, MA], planner's logits [E, MP]) in the layout of the flattened action masks."""
         torch = self.torch
+        if self.network == "library":
+            xa, xp = tensors["obs_a_flat"], tensors["obs_p_flat"]
+            if xa.dtype != torch.float32 or xp.dtype != torch.float32:
+                raise ValueError("MaskedMLPPolicy(network='library'): float32 observations")
+            self.be.policy_mlp_forward(xa, xp, self.weights_a, self.weights_p,
+                                       out=(self.logits_a, self.logits_p, self.value_a, self.value_p))
+            return self.logits_a, self.logits_p
         xa = tensors["obs_a_flat"].to(self.dtype).reshape(-1, self.wa1.shape[0])
         h = self._layer(self.ba1, xa, self.wa1)
         h = self._layer(self.ba2, h, self.wa2)

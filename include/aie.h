@@ -710,6 +710,35 @@ int64_t aie_ppo_workspace_bytes(const aie_env* env, int64_t B);
 int aie_ppo_loss(aie_env* env, int64_t B, const aie_ppo_class* agents, const aie_ppo_class* planner, const int32_t* d_index,
                  void* d_workspace, int64_t workspace_bytes, void* stream);
 
+/* The policy network's forward pass for both actor classes, ONE launch: per row x[F] -> relu -> H -> relu -> H -> M logits
+ * and, optionally, one value -- the two-hidden-layer MLP a rollout evaluates between two environment steps, which as a
+ * torch formulation is about fourteen small launches.  Rows are B * n_agents for the agents and B for the planner (any
+ * B >= 1, not tied to the environment's E).  Per class (aie_mlp_class): x [rows, F] float32 with a leading dimension in
+ * floats (an arena tensor or any device memory, 4-byte aligned); weights row-major [in, out] float32, the leading dimension
+ * the out width (what x @ w takes): w1 [F, H], w2 [H, H], w3 [H, M], biases b1 [H], b2 [H], b3 [M]; wv [H] and bv [1] (device
+ * memory) the value column, both NULL for none; logits [rows, M] and values [rows] contiguous.
+ * THE ARITHMETIC (csrc/aie_layout.h states it once, aie_mlp_row; the CPU test compiles that helper): all float32,
+ *   chain(c; a, w) = acc after acc = c; for k ascending: acc = fmaf(a[k], w[k], acc)   -- one accumulator, one rounding per term
+ *   h1[j] = relu(chain(b1[j]; x, W1[:, j])), h2[j] = relu(chain(b2[j]; h1, W2[:, j])), relu(v) = v > 0 ? v : 0 (NaN -> 0),
+ *   logits[j] = chain(b3[j]; h2, W3[:, j]), value = chain(bv; h2, wv).
+ * The kernel's f32 MFMA is that chain; it may pad K with zero weights behind the real terms, which changes no value except
+ * the sign of an exact zero: the device equals the helper under float == wherever no NaN occurs.  Two runs give the same
+ * bits.  The weights are read from the caller's buffers at every launch (nothing is repacked or cached by the library): an
+ * in-place update of them is seen by the next launch, or the next replay of a captured one.  Exactly [rows, M] and [rows]
+ * are written.  Either class may be NULL; with both NULL the call launches nothing and returns AIE_OK.  Asynchronous on
+ * `stream`, no atomics, no allocation, no synchronisation, capturable in a hipGraph.
+ * AIE_E_UNSUPPORTED: H not a multiple of 16, or outside 16 .. 256.  AIE_E_INVALID: B < 1, F or M outside 1 .. 1024,
+ * x_ld < F, a NULL among x, the six weight and bias pointers and logits, values without wv or wv without values, wv
+ * without bv.  A refused call launches nothing. */
+typedef struct aie_mlp_class {
+  const float* x; int64_t x_ld;          /* [rows, F] observations (arena tensors included), leading dimension in floats */
+  const float *w1, *b1, *w2, *b2, *w3, *b3;   /* [F,H] [H] [H,H] [H] [H,M] [M], leading dimensions = out width */
+  const float *wv, *bv;                  /* [H], [1] in device memory; both NULL: no value column */
+  float *logits, *values;                /* [rows, M] contiguous; [rows] or NULL iff wv NULL */
+  int32_t F, H, M;
+} aie_mlp_class;
+int aie_policy_mlp_forward(aie_env* env, int64_t B, const aie_mlp_class* agents, const aie_mlp_class* planner, void* stream);
+
 /* Trajectory storage with the slot index on the device: one launch per step copies up to AIE_TRAJ_MAX_SEGMENTS per-replica
  * blocks (observations, masks, actions, log-probabilities, values -- any device memory, arena tensors included) into
  * replica e's slot d_slot[e] of the caller's ring buffers, then d_slot[e] becomes (d_slot[e] + 1) % n_slots.
