@@ -3032,6 +3032,12 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
   const bool REGEN = TAIL || (ph & 64), EMIT = TAIL || (ph & 128), CLOSE = TAIL || (ph & 256);
   const bool CLOSE_ONLY = CLOSE && !EMIT;  // (aie_step_range: then without HEAD, REGEN or components -- the state stays as it is)
   const int c_lo = ph ? next.comp_lo : 0, c_hi = ph ? next.comp_hi : P.c.n_components;
+  // A compile-time instance knows its component list, so its component loop is unrolled in full: each component then
+  // stands once in straight-line code.  Left as a loop around the switch, the compiler turns it into a state machine and
+  // hoists every lane mask and address that two components share out of it -- 22 scalar values that did not fit the 80
+  // scalar registers a wave has at 8 waves per SIMD and were parked in the lanes of a vector register, which in turn
+  // pushed three vector dwords to scratch.  The generic kernels (run-time bounds) keep the loop.
+  constexpr int COMP_UNROLL = (SPEC >= 0 && !LOG) ? AIE_MAX_COMPONENTS : 1;
   // The two waves run two separate ARMS from here to the end, each with its own copy of the four workgroup barriers
   // (the branch is wave-uniform, every wave passes the same number of them): a value that only one wave carries --
   // the agents' registers and the draw cache of the first, the generator's ten rows of the second -- is then live in
@@ -3082,6 +3088,7 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
     __builtin_amdgcn_s_setprio(3);  // the serial dynamics are the replica's critical path (at any batch size: round 6 A/B)
     if (TRACE && R.dev_trace && c.tid == 0) R.dev_trace[12 * blockIdx.x + 1] = wall_clock64();
     if (!(skip & AIE_DEV_SKIP_COMPONENTS)) {
+#pragma unroll COMP_UNROLL
       for (int k = c_lo; k < c_hi; ++k) {
         switch (P.c.components[k]) {
           case AIE_COMP_BUILD: if (!(skip & AIE_DEV_SKIP_BUILD)) build_component_step(c, ml, A); break;
