@@ -185,6 +185,12 @@ class AieMlpClass(C.Structure):  # aie_mlp_class
                [(k, C.c_int32) for k in ("F", "H", "M")]
 
 
+class AieMlpGradClass(C.Structure):  # aie_mlp_grad_class
+    _fields_ = [("net", AieMlpClass)] + \
+               [(k, C.c_void_p) for k in ("g_logits", "g_values", "gw1", "gb1", "gw2", "gb2", "gw3", "gb3", "gwv", "gbv")]
+
+
+MLP_BWD_SEG = 256     # AIE_MLP_BWD_SEG
 PPO_N_STATS = 8       # AIE_PPO_N_STATS
 PPO_MAX_WAVES = 8192  # AIE_PPO_MAX_WAVES
 
@@ -242,6 +248,10 @@ def bind(lib):
     lib.aie_ppo_loss.argtypes = [vp, C.c_int64, C.POINTER(AiePpoClass), C.POINTER(AiePpoClass), vp, vp, C.c_int64, vp]
     lib.aie_policy_mlp_forward.restype = C.c_int
     lib.aie_policy_mlp_forward.argtypes = [vp, C.c_int64, C.POINTER(AieMlpClass), C.POINTER(AieMlpClass), vp]
+    lib.aie_policy_mlp_backward_workspace_bytes.restype = C.c_int64
+    lib.aie_policy_mlp_backward_workspace_bytes.argtypes = [vp, C.c_int64, C.POINTER(AieMlpGradClass), C.POINTER(AieMlpGradClass)]
+    lib.aie_policy_mlp_backward.restype = C.c_int
+    lib.aie_policy_mlp_backward.argtypes = [vp, C.c_int64, C.POINTER(AieMlpGradClass), C.POINTER(AieMlpGradClass), vp, C.c_int64, vp]
     lib.aie_trajectory_store.restype = C.c_int
     lib.aie_trajectory_store.argtypes = [vp, C.POINTER(AieTrajSegment), C.c_int32, C.c_int32, vp, vp]
     lib.aie_sample_random_actions.restype = C.c_int
@@ -294,7 +304,7 @@ EXPORTED_SYMBOLS = [
     "aie_set_dense_log_active", "aie_step_kernel_instance", "aie_select_step_kernel", "aie_specialize", "aie_set_global_saez_buffer", "aie_sizeof_config",
     "aie_arena_info", "aie_step_range", "aie_sample_policy_actions_logp", "aie_policy_evaluate", "aie_policy_evaluate_backward",
     "aie_gae", "aie_trajectory_store", "aie_ppo_workspace_bytes", "aie_ppo_loss",
-    "aie_policy_mlp_forward",
+    "aie_policy_mlp_forward", "aie_policy_mlp_backward_workspace_bytes", "aie_policy_mlp_backward",
 ]
 STEP_HEAD, STEP_TAIL, STEP_OBSERVE, STEP_REBASE, STEP_RETAX = 1, 2, 4, 8, 16  # AIE_STEP_*
 STEP_REGEN, STEP_EMIT, STEP_CLOSE = 64, 128, 256  # the end of a step in three parts (scenario hooks run between them)

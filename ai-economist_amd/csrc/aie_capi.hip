@@ -12,6 +12,7 @@
 #include "aie_kernels_saez.hip"
 #include "aie_kernels_ppo.hip"
 #include "aie_kernels_mlp.hip"
+#include "aie_kernels_mlp_bwd.hip"
 #include "aie_kernels_covid.hip"  // last: switches FP contraction off for the rest of the TU
 #include "aie_jit.h"
 
@@ -1244,6 +1245,134 @@ int aie_policy_mlp_forward(aie_env* env, int64_t B, const aie_mlp_class* agents,
   }
   AIE_HIP_CHECK(env, hipSetDevice(env->device));
   hipLaunchKernelGGL(aie_policy_mlp_kernel, dim3((unsigned)blocks), dim3(256), lds, static_cast<hipStream_t>(stream), A);
+  AIE_HIP_CHECK(env, hipGetLastError());
+  return AIE_OK;
+}
+
+// aie_policy_mlp_backward's plan: the checks, the kernels' argument without the workspace pointers, and each class's share
+// of the workspace in floats.  err: where a refusal names itself (nullptr: nowhere).
+static int aie_mlp_bwd_plan(const aie_env* env, char* err, size_t err_size, int64_t B, const aie_mlp_grad_class* const (&cls)[2],
+                            aie_mlp_bwd_args* A, int64_t (&ws_floats)[2]) {
+  constexpr int TM = AIE_MLP_TILE_ROWS;
+  const char* fn = "aie_policy_mlp_backward";
+  memset(A, 0, sizeof(*A));
+  ws_floats[0] = ws_floats[1] = 0;
+  if (B < 1) {
+    if (err) snprintf(err, err_size, "%s: B = %lld (needs B >= 1)", fn, (long long)B);
+    return AIE_E_INVALID;
+  }
+  aie_mlp_bwd_group* grp[2] = {&A->agents, &A->planner};
+  for (int c = 0; c < 2; ++c) {
+    const aie_mlp_grad_class* q = cls[c];
+    if (!q) continue;
+    const aie_mlp_class* k = &q->net;
+    const char* who = c ? "planner's" : "agents'";
+    const bool v = k->wv != nullptr;
+    if (k->F < 1 || k->F > 1024 || k->M < 1 || k->M > 1024 || k->x_ld < k->F || !k->x || !k->w1 || !k->b1 || !k->w2 || !k->b2 ||
+        !k->w3 || !k->b3 || v != (k->bv != nullptr)) {
+      if (err) snprintf(err, err_size, "%s: the %s class needs F (%d) and M (%d) in 1 .. 1024, x_ld (%lld) >= F, x, w1, b1, w2, b2, w3 "
+                        "and b3, and wv and bv both or neither", fn, who, k->F, k->M, (long long)k->x_ld);
+      return AIE_E_INVALID;
+    }
+    if (!q->g_logits || !q->gw1 || !q->gb1 || !q->gw2 || !q->gb2 || !q->gw3 || !q->gb3 || v != (q->g_values != nullptr) ||
+        v != (q->gwv != nullptr) || v != (q->gbv != nullptr)) {
+      if (err) snprintf(err, err_size, "%s: the %s class needs g_logits, gw1, gb1, gw2, gb2, gw3 and gb3, and g_values, gwv and gbv "
+                        "exactly when it has wv", fn, who);
+      return AIE_E_INVALID;
+    }
+    if (k->H < 16 || k->H > 256 || (k->H & 15)) {
+      if (err) snprintf(err, err_size, "%s: the %s hidden width %d is not a multiple of 16 in 16 .. 256", fn, who, k->H);
+      return AIE_E_UNSUPPORTED;
+    }
+    aie_mlp_bwd_group& Q = *grp[c];
+    aie_mlp_group& G = Q.net;
+    G.x = k->x, G.x_ld = k->x_ld;
+    G.w1 = k->w1, G.b1 = k->b1, G.w2 = k->w2, G.b2 = k->b2, G.w3 = k->w3, G.b3 = k->b3, G.wv = k->wv, G.bv = k->bv;
+    G.F = k->F, G.H = k->H, G.M = k->M;
+    G.rows = c ? B : B * (int64_t)env->P.n;
+    const int kpad = (k->F + 3) & ~3, chunk = kpad < AIE_MLP_CHUNK ? kpad : AIE_MLP_CHUNK;
+    const int mpad = (k->M + 3) & ~3;
+    G.lds_a = (chunk > k->H ? chunk : k->H) + 2;
+    G.lds_h = k->H + 2;
+    Q.lds_c = (mpad < AIE_MLP_CHUNK ? mpad : AIE_MLP_CHUNK) + 2;
+    const int64_t nb = (G.rows + TM - 1) / TM, nseg = (G.rows + AIE_MLP_BWD_SEG - 1) / AIE_MLP_BWD_SEG;
+    if (nb > 0x3fffffffll) {
+      if (err) snprintf(err, err_size, "%s: B = %lld is more than one call takes", fn, (long long)B);
+      return AIE_E_INVALID;
+    }
+    G.blocks = (int32_t)nb;
+    Q.nseg = (int32_t)nseg;
+    Q.g_logits = q->g_logits, Q.g_values = q->g_values;
+    Q.gw1 = q->gw1, Q.gb1 = q->gb1, Q.gw2 = q->gw2, Q.gb2 = q->gb2, Q.gw3 = q->gw3, Q.gb3 = q->gb3, Q.gwv = q->gwv, Q.gbv = q->gbv;
+    Q.N3 = k->M + (v ? 1 : 0);
+    Q.off2 = (k->F + 1) * k->H;
+    Q.off3 = Q.off2 + (k->H + 1) * k->H;
+    Q.P = Q.off3 + (k->H + 1) * Q.N3;
+    const int Ks[3] = {k->F, k->H, k->H}, Ns[3] = {k->H, k->H, Q.N3};
+    for (int L = 0; L < 3; ++L) {
+      Q.cg[L] = (((Ns[L] + 15) >> 4) + 3) >> 2;
+      Q.items[L] = ((((Ks[L] + 1 + 15) >> 4) + 3) >> 2) * Q.cg[L];  // groups of four bands x column groups
+      Q.per_seg += Q.items[L];
+    }
+    Q.n_items = nseg * Q.per_seg;
+    const int64_t fl = 4 * G.rows * k->H + nseg * Q.P;
+    ws_floats[c] = (fl + 63) & ~(int64_t)63;
+  }
+  return AIE_OK;
+}
+int64_t aie_policy_mlp_backward_workspace_bytes(const aie_env* env, int64_t B, const aie_mlp_grad_class* agents,
+                                                const aie_mlp_grad_class* planner) {
+  if (!env) return AIE_E_INVALID;
+  const aie_mlp_grad_class* const cls[2] = {agents, planner};
+  aie_mlp_bwd_args A;
+  int64_t fl[2];
+  const int rc = aie_mlp_bwd_plan(env, nullptr, 0, B, cls, &A, fl);
+  return rc != AIE_OK ? rc : (fl[0] + fl[1]) * (int64_t)sizeof(float);
+}
+int aie_policy_mlp_backward(aie_env* env, int64_t B, const aie_mlp_grad_class* agents, const aie_mlp_grad_class* planner,
+                            void* d_workspace, int64_t workspace_bytes, void* stream) {
+  if (!env) return AIE_E_INVALID;
+  constexpr int TM = AIE_MLP_TILE_ROWS;
+  const aie_mlp_grad_class* const cls[2] = {agents, planner};
+  aie_mlp_bwd_args A;
+  int64_t fl[2];
+  const int rc = aie_mlp_bwd_plan(env, env->err, sizeof(env->err), B, cls, &A, fl);
+  if (rc != AIE_OK) return rc;
+  if (!agents && !planner) return AIE_OK;
+  const int64_t need = (fl[0] + fl[1]) * (int64_t)sizeof(float);
+  if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 15u) || workspace_bytes < need) {
+    snprintf(env->err, sizeof(env->err), "aie_policy_mlp_backward: the workspace (%p, %lld bytes) must be device memory, 16-byte "
+             "aligned, of at least %lld bytes (aie_policy_mlp_backward_workspace_bytes)", d_workspace, (long long)workspace_bytes,
+             (long long)need);
+    return AIE_E_INVALID;
+  }
+  aie_mlp_bwd_group* grp[2] = {&A.agents, &A.planner};
+  float* ws = static_cast<float*>(d_workspace);
+  size_t lds = 0;
+  int64_t blocks = 0, items = 0, rblocks = 0;
+  for (int c = 0; c < 2; ++c) {
+    if (!cls[c]) continue;
+    aie_mlp_bwd_group& Q = *grp[c];
+    const int64_t rh = Q.net.rows * Q.net.H;
+    Q.h1 = ws, Q.h2 = ws + rh, Q.dz2 = ws + 2 * rh, Q.dz1 = ws + 3 * rh, Q.partial = ws + 4 * rh;
+    ws += fl[c];
+    blocks += Q.net.blocks;
+    items += Q.n_items;
+    const int64_t rb = (Q.P + 255) / 256;
+    if (!c) A.reduce_blocks_a = (int32_t)rb;
+    rblocks += rb;
+    const size_t l = (size_t)TM * (size_t)(Q.net.lds_a + Q.net.lds_h + Q.lds_c) * sizeof(float);
+    lds = l > lds ? l : lds;
+  }
+  if (blocks > 0x7fffff00ll || items > 0x7fffff00ll) {
+    snprintf(env->err, sizeof(env->err), "aie_policy_mlp_backward: B = %lld is more than one call takes", (long long)B);
+    return AIE_E_INVALID;
+  }
+  AIE_HIP_CHECK(env, hipSetDevice(env->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(aie_policy_mlp_bwd_rows_kernel, dim3((unsigned)blocks), dim3(256), lds, s, A);
+  hipLaunchKernelGGL(aie_policy_mlp_bwd_atd_kernel, dim3((unsigned)items), dim3(256), 0, s, A);
+  hipLaunchKernelGGL(aie_policy_mlp_bwd_reduce_kernel, dim3((unsigned)rblocks), dim3(256), 0, s, A);
   AIE_HIP_CHECK(env, hipGetLastError());
   return AIE_OK;
 }

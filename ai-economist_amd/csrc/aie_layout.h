@@ -1961,6 +1961,98 @@ typedef struct aie_mlp_group {
 typedef struct aie_mlp_args {
   aie_mlp_group agents, planner;
 } aie_mlp_args;
+
+/* The policy network's backward pass (include/aie.h: aie_policy_mlp_backward), stated once -- the weights' gradients from
+ * the gradients with respect to logits and values; tests/test_policy_mlp_backward_cpu.py compiles these helpers against an
+ * independent transcription (tests/policy_mlp_bwd_ref.py).  All float32 unless said otherwise; chain0(a, w) = chain(+0; a, w).
+ * Per row r (g_logits [rows, M] contiguous, g_values [rows], NULL exactly when wv is):
+ *   h1, h2       recomputed exactly as aie_mlp_row computes them;
+ *   dz3[m] = g_logits[r][m], dv = g_values[r];
+ *   dh2[j] = chain0 over m = 0 .. M-1 ascending of (dz3[m], W3[j][m]), with a value column one last term fmaf(dv, wv[j], acc)
+ *            (the value column is column M, as in the forward);
+ *   dz2[j] = h2[j] > 0 ? dh2[j] : 0;
+ *   dh1[j] = chain0 over k = 0 .. H-1 ascending of (dz2[k], W2[j][k]);   dz1[j] = h1[j] > 0 ? dh1[j] : 0.
+ * Across rows: rows are cut into segments of AIE_MLP_BWD_SEG consecutive rows (the last may be short).  With the layers'
+ * activations a_1 = x, a_2 = h1, a_3 = h2,
+ *   partial_s(gW_L[k][j]) = chain0 over the rows r of segment s, ascending, of (a_L[r][k], dz_L[r][j]),
+ * gwv[k] pairs (h2[r][k], dv[r]), and the bias gradients are the same chain with the activation 1 (acc = acc + dz, rounded
+ * once per row).  A gradient entry is the sum of its segment partials in float64, in ascending segment order, rounded to
+ * float32 once (aie_ppo_loss's convention).  Nothing is produced for x.  Every entry is overwritten.
+ * AIE_MLP_BWD_SEG is this constant and nothing else -- not the device, not B, not the launch geometry -- so the bits do
+ * not depend on how many compute units ran the call.  As in the forward, a kernel may pad a chain with zero-times-zero
+ * terms behind the real ones: that changes nothing except the sign of an exact zero.  No float atomics anywhere. */
+#if AIE_MLP_BWD_SEG % AIE_MLP_TILE_ROWS   /* (include/aie.h defines it, 256: the formula of the workspace needs it there) */
+#error "AIE_MLP_BWD_SEG is a multiple of AIE_MLP_TILE_ROWS"
+#endif
+/* one row: h1, h2 (as aie_mlp_row's), dz2 and dz1, H floats each; g_values_r is read only with wv */
+AIE_HD static inline void aie_mlp_row_backward(const float* x, int F, int H, int M, const float* w1, const float* b1, const float* w2,
+                                               const float* b2, const float* w3, const float* wv, const float* g_logits_r,
+                                               float g_value_r, float* h1, float* h2, float* dz2, float* dz1) {
+  for (int j = 0; j < H; ++j) h1[j] = aie_mlp_relu(aie_mlp_chain(b1[j], x, w1 + j, H, F));
+  for (int j = 0; j < H; ++j) h2[j] = aie_mlp_relu(aie_mlp_chain(b2[j], h1, w2 + j, H, H));
+  for (int j = 0; j < H; ++j) {
+    float acc = aie_mlp_chain(0.0f, g_logits_r, w3 + (int64_t)j * M, 1, M);
+    if (wv) acc = fmaf(g_value_r, wv[j], acc);
+    dz2[j] = h2[j] > 0.0f ? acc : 0.0f;
+  }
+  for (int j = 0; j < H; ++j) {
+    const float acc = aie_mlp_chain(0.0f, dz2, w2 + (int64_t)j * H, 1, H);
+    dz1[j] = h1[j] > 0.0f ? acc : 0.0f;
+  }
+}
+/* one gradient entry: a (NULL: the constant 1, a bias) and d are columns of row-major arrays, entry r at a[r * a_ld] */
+AIE_HD static inline float aie_mlp_grad_entry(const float* a, int64_t a_ld, const float* d, int64_t d_ld, int64_t rows) {
+  double sum = 0.0;
+  for (int64_t r0 = 0; r0 < rows; r0 += AIE_MLP_BWD_SEG) {
+    const int64_t r1 = r0 + AIE_MLP_BWD_SEG < rows ? r0 + AIE_MLP_BWD_SEG : rows;
+    float acc = 0.0f;
+    for (int64_t r = r0; r < r1; ++r) acc = fmaf(a ? a[r * a_ld] : 1.0f, d[r * d_ld], acc);
+    sum += (double)acc;
+  }
+  return (float)sum;
+}
+/* The whole pass of one class on the host.  scratch: 4 * rows * H floats (h1, h2, dz2, dz1 as [rows, H] each). */
+static inline void aie_mlp_backward_host(const float* x, int64_t x_ld, int64_t rows, int F, int H, int M, const float* w1,
+                                         const float* b1, const float* w2, const float* b2, const float* w3, const float* wv,
+                                         const float* g_logits, const float* g_values, float* scratch, float* gw1, float* gb1,
+                                         float* gw2, float* gb2, float* gw3, float* gb3, float* gwv, float* gbv) {
+  float *h1 = scratch, *h2 = h1 + rows * H, *dz2 = h2 + rows * H, *dz1 = dz2 + rows * H;
+  for (int64_t r = 0; r < rows; ++r)
+    aie_mlp_row_backward(x + r * x_ld, F, H, M, w1, b1, w2, b2, w3, wv, g_logits + r * M, wv ? g_values[r] : 0.0f, h1 + r * H,
+                         h2 + r * H, dz2 + r * H, dz1 + r * H);
+  for (int j = 0; j < H; ++j) {
+    for (int k = 0; k < F; ++k) gw1[(int64_t)k * H + j] = aie_mlp_grad_entry(x + k, x_ld, dz1 + j, H, rows);
+    for (int k = 0; k < H; ++k) gw2[(int64_t)k * H + j] = aie_mlp_grad_entry(h1 + k, H, dz2 + j, H, rows);
+    gb1[j] = aie_mlp_grad_entry(0, 0, dz1 + j, H, rows);
+    gb2[j] = aie_mlp_grad_entry(0, 0, dz2 + j, H, rows);
+  }
+  for (int j = 0; j < M; ++j) {
+    for (int k = 0; k < H; ++k) gw3[(int64_t)k * M + j] = aie_mlp_grad_entry(h2 + k, H, g_logits + j, M, rows);
+    gb3[j] = aie_mlp_grad_entry(0, 0, g_logits + j, M, rows);
+  }
+  if (wv) {
+    for (int k = 0; k < H; ++k) gwv[k] = aie_mlp_grad_entry(h2 + k, H, g_values, 1, rows);
+    gbv[0] = aie_mlp_grad_entry(0, 0, g_values, 1, rows);
+  }
+}
+/* The kernels' argument (aie_policy_mlp_backward fills it).  net: the forward's group (logits / values unused; blocks the
+ * row tiles).  The workspace per class: h1, h2, dz2, dz1 as [rows, H] each, then the segments' partials [nseg][P], one
+ * float per gradient entry in three blocks [(K + 1), N] -- (F + 1, H), (H + 1, H), (H + 1, M + value) -- whose last row
+ * is the bias and, in the third, whose column M is the value head.  An ITEM is one workgroup's work in the second launch:
+ * four 16-row bands of a layer's block (one per wave) by up to four 16-column tiles, over one segment's rows. */
+typedef struct aie_mlp_bwd_group {
+  aie_mlp_group net;
+  const float *g_logits, *g_values;
+  float *h1, *h2, *dz2, *dz1, *partial;
+  float *gw1, *gb1, *gw2, *gb2, *gw3, *gb3, *gwv, *gbv;
+  int32_t lds_c, nseg, P, off2, off3, N3;   /* the staged dz3 chunk's row stride; segments; entries; the blocks' offsets; M + value */
+  int32_t cg[3], items[3], per_seg;         /* per layer: column groups, items per segment; their sum */
+  int64_t n_items;                          /* nseg * per_seg */
+} aie_mlp_bwd_group;
+typedef struct aie_mlp_bwd_args {
+  aie_mlp_bwd_group agents, planner;
+  int32_t reduce_blocks_a;                  /* the third launch: workgroups [0, reduce_blocks_a) are the agents' */
+} aie_mlp_bwd_args;
 /* aie_trajectory_store's kernel argument: the caller's segments (include/aie.h: aie_traj_segment, 32 bytes each) with the
  * copy width decided on the host: wide != 0 = 16-byte lane accesses (source, destination, stride and size allow it for
  * every replica and slot), else 4-byte ones. */

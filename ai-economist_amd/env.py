@@ -597,6 +597,35 @@ class DeviceBackend:
                                           C.c_void_p(ws.data_ptr()), C.c_int64(ws.numel() * 8), self._stream()))
         return outs[0], outs[1]
 
+    def _mlp_operands(self, fn, who, x, w, per):
+        """The checks policy_mlp_forward and policy_mlp_backward share for one class -> (x as [rows, F], x_ld, the dict of its
+        weight tensors w1 .. bv, F, H, M)."""
+        torch = _torch()
+        get = w.get if hasattr(w, "get") else lambda k, w=w: getattr(w, k, None)  # noqa: E731
+        if x.dim() == 3:  # [B, n, F] with one row stride throughout: a view, never a copy
+            if x.shape[0] > 1 and x.stride(0) != x.shape[1] * x.stride(1):
+                raise ValueError("%s: x_%s [B, n, F] needs one row stride throughout (strides %s)" % (fn, who, tuple(x.stride())))
+            x = x.as_strided((x.shape[0] * x.shape[1], x.shape[2]), (x.stride(1), x.stride(2)), x.storage_offset())
+        if x.dim() != 2 or x.dtype != torch.float32 or x.device != self.device or (x.shape[1] > 1 and x.stride(1) != 1) \
+                or x.shape[0] == 0 or x.shape[0] % per:
+            raise ValueError("%s: x_%s is a float32 device tensor [B x %d, F] with contiguous rows" % (fn, who, per))
+        rows, F = int(x.shape[0]), int(x.shape[1])
+        x_ld = int(x.stride(0)) if rows > 1 else F
+        t = {k: get(k) for k in ("w1", "b1", "w2", "b2", "w3", "b3", "wv", "bv")}
+        H = int(t["w1"].shape[-1]) if t["w1"] is not None and t["w1"].dim() == 2 else 0
+        M = int(t["w3"].shape[-1]) if t["w3"] is not None and t["w3"].dim() == 2 else 0
+        for k, shape in (("w1", (F, H)), ("b1", (H,)), ("w2", (H, H)), ("b2", (H,)), ("w3", (H, M)), ("b3", (M,)),
+                         ("wv", (H,)), ("bv", (1,))):
+            v = t[k]
+            if v is None and k in ("wv", "bv"):
+                continue
+            if (v is None or v.dtype != torch.float32 or v.device != self.device or not v.is_contiguous()
+                    or v.numel() != int(np.prod(shape)) or (v.dim() == 2 and k != "wv" and tuple(v.shape) != shape)):
+                raise ValueError("%s: weights_%s[%r] must be a contiguous float32 device tensor of shape %s" % (fn, who, k, shape))
+        if (t["wv"] is None) != (t["bv"] is None):
+            raise ValueError("%s: weights_%s needs wv and bv together" % (fn, who))
+        return x, x_ld, t, F, H, M
+
     def policy_mlp_forward(self, x_a, x_p, weights_a, weights_p, out=None):
         """aie_policy_mlp_forward: both classes' policy network -- x -> relu -> H -> relu -> H -> logits (+ value) -- in ONE
         launch on the current stream.  x_a [B * n, F_a] (or [B, n, F_a]) and x_p [B, F_p]: float32 device tensors whose rows
@@ -616,31 +645,8 @@ class DeviceBackend:
                 classes.append(None)
                 res.append((None, None))
                 continue
-            get = w.get if hasattr(w, "get") else lambda k, w=w: getattr(w, k, None)  # noqa: E731
-            if x.dim() == 3:  # [B, n, F] with one row stride throughout: a view, never a copy
-                if x.shape[0] > 1 and x.stride(0) != x.shape[1] * x.stride(1):
-                    raise ValueError("policy_mlp_forward: x_%s [B, n, F] needs one row stride throughout (strides %s)"
-                                     % (who, tuple(x.stride())))
-                x = x.as_strided((x.shape[0] * x.shape[1], x.shape[2]), (x.stride(1), x.stride(2)), x.storage_offset())
-            if x.dim() != 2 or x.dtype != torch.float32 or x.device != self.device or (x.shape[1] > 1 and x.stride(1) != 1) \
-                    or x.shape[0] == 0 or x.shape[0] % per:
-                raise ValueError("policy_mlp_forward: x_%s is a float32 device tensor [B x %d, F] with contiguous rows" % (who, per))
-            rows, F = int(x.shape[0]), int(x.shape[1])
-            x_ld = int(x.stride(0)) if rows > 1 else F
-            t = {k: get(k) for k in ("w1", "b1", "w2", "b2", "w3", "b3", "wv", "bv")}
-            H = int(t["w1"].shape[-1]) if t["w1"] is not None and t["w1"].dim() == 2 else 0
-            M = int(t["w3"].shape[-1]) if t["w3"] is not None and t["w3"].dim() == 2 else 0
-            for k, shape in (("w1", (F, H)), ("b1", (H,)), ("w2", (H, H)), ("b2", (H,)), ("w3", (H, M)), ("b3", (M,)),
-                             ("wv", (H,)), ("bv", (1,))):
-                v = t[k]
-                if v is None and k in ("wv", "bv"):
-                    continue
-                if (v is None or v.dtype != torch.float32 or v.device != self.device or not v.is_contiguous()
-                        or v.numel() != int(np.prod(shape)) or (v.dim() == 2 and k != "wv" and tuple(v.shape) != shape)):
-                    raise ValueError("policy_mlp_forward: weights_%s[%r] must be a contiguous float32 device tensor of shape %s"
-                                     % (who, k, shape))
-            if (t["wv"] is None) != (t["bv"] is None):
-                raise ValueError("policy_mlp_forward: weights_%s needs wv and bv together" % who)
+            x, x_ld, t, F, H, M = self._mlp_operands("policy_mlp_forward", who, x, w, per)
+            rows = int(x.shape[0])
             has_v = t["wv"] is not None
             for o, numel, what in ((o_l, rows * M, "logits"), (o_v, rows, "value")):
                 if o is not None and (o.dtype != torch.float32 or o.device != self.device or not o.is_contiguous() or o.numel() != numel):
@@ -662,6 +668,74 @@ class DeviceBackend:
         self._check(self.lib.aie_policy_mlp_forward(self.handle, C.c_int64(Bs.pop()), ref(classes[0]), ref(classes[1]),
                                                     self._stream()))
         return res[0][0], res[1][0], res[0][1], res[1][1]
+
+    def policy_mlp_backward(self, x_a, x_p, weights_a, weights_p, g_logits_a, g_logits_p, g_values_a=None, g_values_p=None,
+                            out=None):
+        """aie_policy_mlp_backward: the gradients of both classes' weights from the gradients with respect to logits and
+        values (ppo_loss's grad_logits and grad_values), THREE launches on the current stream.  x_* and weights_* as for
+        policy_mlp_forward (the same validation); g_logits_* [rows, M] and g_values_* [rows]: contiguous float32 device
+        tensors, g_values exactly for a class with wv.  Returns (grads_a, grads_p): a dict w1, b1, w2, b2, w3, b3 (and wv,
+        bv) of new float32 tensors in the weights' shapes per class, None for a class left out; out=(dict_a, dict_p) fills
+        the caller's contiguous float32 tensors instead.  Every entry is overwritten.  The arithmetic contract (segments of
+        _cabi.MLP_BWD_SEG rows, float64 sums of the segments, no atomics: two runs give the same bits) is include/aie.h's.
+        The workspace grows with the row count; it is cached per backend and replaced when a call needs more (calls of one
+        backend share it and must not run at the same time on two streams; a captured call keeps the pointer, so capture
+        the largest batch first or keep batch sizes fixed)."""
+        torch = _torch()
+        f = dict(dtype=torch.float32, device=self.device)
+        out = tuple(out) if out is not None else (None, None)
+        classes, res, Bs = [], [], set()
+        for who, x, w, per, gl, gv, o in (("a", x_a, weights_a, self.n, g_logits_a, g_values_a, out[0]),
+                                          ("p", x_p, weights_p, 1, g_logits_p, g_values_p, out[1])):
+            if x is None:
+                classes.append(None)
+                res.append(None)
+                continue
+            x, x_ld, t, F, H, M = self._mlp_operands("policy_mlp_backward", who, x, w, per)
+            rows = int(x.shape[0])
+            shapes = dict(w1=(F, H), b1=(H,), w2=(H, H), b2=(H,), w3=(H, M), b3=(M,), wv=(H,), bv=(1,))
+            has_v = t["wv"] is not None
+            if (gv is not None) != has_v:
+                raise ValueError("policy_mlp_backward: g_values_%s goes with wv: both or neither" % who)
+            for g, numel, what in ((gl, rows * M, "g_logits"), (gv, rows, "g_values")):
+                if (g is None and what == "g_logits") or (g is not None and (
+                        g.dtype != torch.float32 or g.device != self.device or not g.is_contiguous() or g.numel() != numel)):
+                    raise ValueError("policy_mlp_backward: %s_%s must be a contiguous float32 device tensor of %d elements"
+                                     % (what, who, numel))
+            names = [k for k in shapes if t[k] is not None]
+            if o is not None:
+                for k in names:
+                    v = o.get(k)
+                    if (v is None or v.dtype != torch.float32 or v.device != self.device or not v.is_contiguous()
+                            or v.numel() != t[k].numel()):
+                        raise ValueError("policy_mlp_backward: out's %s_%s must be a contiguous float32 device tensor of %d elements"
+                                         % (k, who, t[k].numel()))
+                grads = {k: o[k] for k in names}
+            else:
+                grads = {k: torch.empty_like(t[k]) for k in names}
+            ptr = lambda v: v.data_ptr() if v is not None else None  # noqa: E731
+            net = _cabi.AieMlpClass(x=x.data_ptr(), x_ld=x_ld, w1=ptr(t["w1"]), b1=ptr(t["b1"]), w2=ptr(t["w2"]), b2=ptr(t["b2"]),
+                                    w3=ptr(t["w3"]), b3=ptr(t["b3"]), wv=ptr(t["wv"]), bv=ptr(t["bv"]), logits=None, values=None,
+                                    F=F, H=H, M=M)
+            classes.append(_cabi.AieMlpGradClass(net=net, g_logits=ptr(gl), g_values=ptr(gv),
+                                                 **{"g" + k: ptr(grads.get(k)) for k in shapes}))
+            res.append(grads)
+            Bs.add(rows // per)
+        if not Bs:
+            raise ValueError("policy_mlp_backward: no actor class")
+        if len(Bs) != 1:
+            raise ValueError("policy_mlp_backward: the classes disagree on the batch size (%s)" % sorted(Bs))
+        B = C.c_int64(Bs.pop())
+        ref = lambda c: C.byref(c) if c is not None else None  # noqa: E731
+        need = int(self.lib.aie_policy_mlp_backward_workspace_bytes(self.handle, B, ref(classes[0]), ref(classes[1])))
+        ws = getattr(self, "_mlp_bwd_ws", None)
+        if need > 0 and (ws is None or ws.numel() * 4 < need):
+            ws = self._mlp_bwd_ws = torch.empty((need + 3) // 4, **f)
+        # (a refusal of the plan makes `need` its negative code: the call below then refuses too, and names itself)
+        self._check(self.lib.aie_policy_mlp_backward(self.handle, B, ref(classes[0]), ref(classes[1]),
+                                                     C.c_void_p(ws.data_ptr()) if ws is not None else None,
+                                                     C.c_int64(ws.numel() * 4 if ws is not None else 0), self._stream()))
+        return res[0], res[1]
 
     def _action_buffers(self, slot):
         torch = _torch()

@@ -336,11 +336,72 @@ def ppo_loss(be, logits_a, logits_p, values_a, values_p, batch, index=None, clip
     return _ppo_loss_function().apply(be, logits_a, logits_p, values_a, values_p, batch, index, coefs, coeffs_p, adv_moments)
 
 
-def __getattr__(name):  # rollout.MaskedCategorical, rollout.PPOLoss: the classes themselves, made when first asked for
+def _policy_mlp_function():
+    """The autograd Function of policy_mlp, built at first use."""
+    global _PolicyMLP
+    if _PolicyMLP is not None:
+        return _PolicyMLP
+    import torch
+
+    class PolicyMLP(torch.autograd.Function):
+        """Both classes' policy network, differentiable in its weights: forward = ONE Backend.policy_mlp_forward call,
+        backward = ONE Backend.policy_mlp_backward call (three launches).  apply(be, x_a, x_p, names_a, names_p, *weights)
+        -> (logits_a, logits_p, value_a, value_p); names_*: the keys of the class's weights among `weights`, in order."""
+
+        @staticmethod
+        def forward(ctx, be, x_a, x_p, names_a, names_p, *weights):
+            wa = dict(zip(names_a, weights[:len(names_a)]))
+            wp = dict(zip(names_p, weights[len(names_a):]))
+            out = be.policy_mlp_forward(x_a, x_p, wa if x_a is not None else None, wp if x_p is not None else None)
+            ctx.be, ctx.names = be, (names_a, names_p)
+            ctx.has_x = (x_a is not None, x_p is not None)
+            ctx.save_for_backward(*[t for t in (x_a, x_p) if t is not None], *weights)
+            return out
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable  # (one library call, not a graph of torch operations)
+        def backward(ctx, g_la, g_lp, g_va, g_vp):
+            saved = list(ctx.saved_tensors)
+            x_a = saved.pop(0) if ctx.has_x[0] else None
+            x_p = saved.pop(0) if ctx.has_x[1] else None
+            names_a, names_p = ctx.names
+            wa, wp = dict(zip(names_a, saved[:len(names_a)])), dict(zip(names_p, saved[len(names_a):]))
+            c = lambda g: None if g is None else g.contiguous()  # noqa: E731  (a missing one arrives as zeros)
+            ga, gp = ctx.be.policy_mlp_backward(x_a, x_p, wa, wp, c(g_la), c(g_lp), c(g_va) if "wv" in wa else None,
+                                                c(g_vp) if "wv" in wp else None)
+            grads = [ga[k] if ga is not None else None for k in names_a] + [gp[k] if gp is not None else None for k in names_p]
+            return (None,) * 5 + tuple(grads)
+
+    _PolicyMLP = PolicyMLP
+    return PolicyMLP
+
+
+_PolicyMLP = None
+
+
+def policy_mlp(be, x_a, x_p, weights_a, weights_p):
+    """(logits_a, logits_p, value_a, value_p) of Backend.policy_mlp_forward -- the same operands, the same bits -- as
+    tensors that are differentiable in the sixteen weight tensors (those with requires_grad): backward is ONE
+    Backend.policy_mlp_backward call in the forward's float32 chains, bit-reproducible (include/aie.h states the
+    arithmetic).  Nothing flows to the observations; an output that takes no part in the loss counts as a zero gradient.
+    With ppo_loss on the outputs, loss.backward() fills .grad of [in, out] weight tensors an in-place optimizer updates
+    where the next forward -- eager or replayed -- reads them: no mlp_weights.refresh()."""
+    names, flat = [], []
+    for x, w in ((x_a, weights_a), (x_p, weights_p)):
+        get = (lambda k: None) if x is None else w.get if hasattr(w, "get") else (lambda k, w=w: getattr(w, k, None))
+        present = tuple(k for k in mlp_weights.NAMES if get(k) is not None)
+        names.append(present)
+        flat.extend(get(k) for k in present)
+    return _policy_mlp_function().apply(be, x_a, x_p, names[0], names[1], *flat)
+
+
+def __getattr__(name):  # rollout.MaskedCategorical, rollout.PPOLoss, rollout.PolicyMLP: the classes, made when first asked for
     if name == "MaskedCategorical":
         return _masked_categorical()
     if name == "PPOLoss":
         return _ppo_loss_function()
+    if name == "PolicyMLP":
+        return _policy_mlp_function()
     raise AttributeError(name)
 
 
@@ -416,7 +477,8 @@ class MaskedMLPPolicy:
     layers and value columns in one launch, float32, every output one ascending fmaf chain from its bias) that reads the
     arena's observations and this object's weight tensors where they lie and writes the fixed buffers `logits_a` /
     `logits_p` and `value_a` / `value_p` in place; a call of the policy is then two launches, the network and the sampler.
-    float32 only.  The default "torch" path is unchanged."""
+    float32 only.  evaluate(x_a, x_p) is the same network as an autograd function (rollout.policy_mlp) on the same
+    weight tensors: what a PPO update differentiates.  The default "torch" path is unchanged."""
 
     def __init__(self, be, hidden=128, seed=0, dtype=None, sampler="library", sample_seed=1234, record_logp=False,
                  value_head=False, network="torch"):
@@ -534,6 +596,18 @@ class MaskedMLPPolicy:
         if self.value_head:
             self.value_p.view(-1, 1).copy_(torch.addmm(self.bpv, h, self.wpv))
         return la, lp
+
+    def evaluate(self, x_a, x_p):
+        """network="library": policy_mlp's (logits_a, logits_p, value_a, value_p) for the given observations (any batch
+        size) on this object's own weight tensors, differentiable in those that require a gradient: with ppo_loss on
+        them, backward() fills .grad of wa1 .. bpv, and an in-place optimizer step is what the next call, logits() or
+        replay sees.  New tensors: the fixed buffers of logits() are not touched."""
+        if self.network != "library":
+            raise NotImplementedError("MaskedMLPPolicy.evaluate: network='library'")
+        wa, wp = dict(self.weights_a), dict(self.weights_p)
+        if self.value_head:  # (views made now, so that a gradient reaches the [hidden, 1] columns)
+            wa["wv"], wp["wv"] = self.wav.view(-1), self.wpv.view(-1)
+        return policy_mlp(self.be, x_a, x_p, wa, wp)
 
     def __call__(self, tensors, actions_a, actions_p):
         torch = self.torch

@@ -739,6 +739,45 @@ typedef struct aie_mlp_class {
 } aie_mlp_class;
 int aie_policy_mlp_forward(aie_env* env, int64_t B, const aie_mlp_class* agents, const aie_mlp_class* planner, void* stream);
 
+/* The same network's backward pass for both actor classes, THREE launches: the gradients of the eight weight tensors from
+ * the gradients with respect to logits and values (aie_ppo_loss's grad_logits and grad_values, say).  Rows, B and the
+ * classes as for the forward.  Per class (aie_mlp_grad_class): net -- x, x_ld, the weights, F, H and M as for the forward
+ * (net.logits and net.values are ignored); g_logits [rows, M] contiguous and g_values [rows] (NULL exactly when net.wv is);
+ * the outputs gw1 .. gbv in the weights' shapes (gwv and gbv NULL exactly when net.wv is).  Nothing is produced for x.
+ * THE ARITHMETIC (csrc/aie_layout.h states it once -- aie_mlp_row_backward, aie_mlp_grad_entry -- and the CPU test compiles
+ * those helpers): all float32 unless said otherwise; chain0(a, w) = chain(+0; a, w), the forward's chain from zero.  Per row r:
+ *   h1, h2 are recomputed exactly as the forward computes them;   dz3[m] = g_logits[r][m], dv = g_values[r];
+ *   dh2[j] = chain0 over m ascending of (dz3[m], W3[j][m]), with a value column one last term fmaf(dv, wv[j], acc);
+ *   dz2[j] = h2[j] > 0 ? dh2[j] : 0;   dh1[j] = chain0 over k ascending of (dz2[k], W2[j][k]);   dz1[j] = h1[j] > 0 ? dh1[j] : 0.
+ * Across rows: segments of AIE_MLP_BWD_SEG consecutive rows (the last may be short); with a_1 = x, a_2 = h1, a_3 = h2,
+ *   partial_s(gW_L[k][j]) = chain0 over segment s's rows ascending of (a_L[r][k], dz_L[r][j]);   gwv[k] pairs (h2[r][k], dv[r]);
+ *   a bias gradient is the same chain with the activation 1 (acc = acc + dz, rounded once per row);
+ *   an entry = the sum of its segment partials in float64, ascending, rounded to float32 once (aie_ppo_loss's convention).
+ * The segment length is a compile-time constant: the bits do not depend on the device, on B or on how many compute units
+ * ran the call.  A kernel may pad a chain with zero-times-zero terms behind the real ones, which changes nothing except the
+ * sign of an exact zero: the device equals the helpers under float == wherever no NaN occurs.  No float atomics; two runs
+ * give the same bits.  Every gradient entry is overwritten, not accumulated into.
+ * d_workspace: device memory, 16-byte aligned, the call's own until it has run (two streams: one each; a captured call keeps
+ * the pointer).  It holds h1, h2, dz2 and dz1 and the segments' partial sums, so it GROWS LINEARLY WITH THE ROW COUNT: per
+ * class, with v = 1 with a value column and 0 without,
+ *   floats = 4 rows H + ceil(rows / AIE_MLP_BWD_SEG) P,   P = (F + 1) H + (H + 1) H + (H + 1)(M + v),
+ * rounded up to a multiple of 64 floats; the sum over the classes given, times 4 bytes, is what the workspace_bytes function
+ * returns (or the negative code of the call's own refusal; 0 with no class).
+ * Either class may be NULL; with both NULL the call launches nothing and returns AIE_OK.  Asynchronous on `stream`, no
+ * allocation, no synchronisation, capturable in a hipGraph.  The forward's refusals for B, F, H, M, x_ld and NULL pointers;
+ * AIE_E_INVALID also for a NULL g_logits or required gradient pointer, a g_values, gwv or gbv that is there without net.wv or
+ * missing with it, and a workspace that is NULL, misaligned or too small.  A refused call launches and writes nothing. */
+#define AIE_MLP_BWD_SEG 256
+typedef struct aie_mlp_grad_class {
+  aie_mlp_class net;                       /* x, x_ld, weights, F, H, M as for the forward; net.logits / net.values are ignored */
+  const float *g_logits, *g_values;        /* [rows, M]; [rows], NULL iff net.wv is NULL */
+  float *gw1, *gb1, *gw2, *gb2, *gw3, *gb3, *gwv, *gbv;   /* the weights' shapes; gwv / gbv NULL iff net.wv is NULL */
+} aie_mlp_grad_class;
+int64_t aie_policy_mlp_backward_workspace_bytes(const aie_env* env, int64_t B, const aie_mlp_grad_class* agents,
+                                                const aie_mlp_grad_class* planner);
+int aie_policy_mlp_backward(aie_env* env, int64_t B, const aie_mlp_grad_class* agents, const aie_mlp_grad_class* planner,
+                            void* d_workspace, int64_t workspace_bytes, void* stream);
+
 /* Trajectory storage with the slot index on the device: one launch per step copies up to AIE_TRAJ_MAX_SEGMENTS per-replica
  * blocks (observations, masks, actions, log-probabilities, values -- any device memory, arena tensors included) into
  * replica e's slot d_slot[e] of the caller's ring buffers, then d_slot[e] becomes (d_slot[e] + 1) % n_slots.
