@@ -14,7 +14,7 @@ LIB = os.path.join(CSRC, "libaie_hip.so")
 LIB_DEV = os.path.join(CSRC, "libaie_hip_dev.so")
 SOURCES = ["aie_capi.hip", "aie_kernels.hip", "aie_kernels_ose.hip", "aie_kernels_saez.hip", "aie_kernels_ppo.hip", "aie_kernels_mlp.hip",
            "aie_kernels_mlp_bwd.hip", "aie_kernels_covid.hip", "aie_layout.h", "aie_glibc_math.h", "aie_glibc_tables.h", "aie_spec_generated.h",
-           "aie_jit.h"]
+           "aie_jit.h", "aie_trainer_plan.h"]
 
 
 def hipcc_path():

@@ -1,7 +1,9 @@
 """ctypes mirror of include/aie.h (the C ABI of the batched env.step()).
 
 Only plain C types cross this boundary: pointers, sizes, ints, doubles.  torch is used
-by env.py purely as the owner of device memory / streams.
+by env.py (the environment's calls) and _trainer_ops.py (the trainer operators' calls and
+their argument structures: AieTrajSegment, AiePpoClass, AieMlpClass, AieMlpGradClass)
+purely as the owner of device memory / streams.
 """
 import ctypes as C
 

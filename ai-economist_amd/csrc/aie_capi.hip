@@ -15,6 +15,7 @@
 #include "aie_kernels_mlp_bwd.hip"
 #include "aie_kernels_covid.hip"  // last: switches FP contraction off for the rest of the TU
 #include "aie_jit.h"
+#include "aie_trainer_plan.h"  // host only: the trainer calls' plans
 
 struct aie_env {
   aie_params P{};
@@ -933,85 +934,21 @@ int aie_sample_policy_actions_logp(aie_env* env, const float* d_logits_a, const 
                                         d_logp_p, stream);
 }
 
-// The evaluation kernels' argument: the sampler's row shapes (aie_sampler_args_of), the caller's pointers, B batch elements.
-static int aie_policy_eval_args_of(aie_env* env, const char* who, int64_t B, const float* lg_a, const float* lg_p, const float* mk_a,
-                                   const float* mk_p, aie_policy_eval_args* out) {
-  if (aie_sampler_check(&env->P, env->err, sizeof(env->err)) != AIE_OK) return AIE_E_UNSUPPORTED;
-  if (B < 1 || (((lg_a && !mk_a) || (lg_p && !mk_p)) && B != env->P.E)) {
-    snprintf(env->err, sizeof(env->err), "%s: B = %lld; without the caller's masks (the arena's current ones) B must be the "
-             "environment's %d replicas", who, (long long)B, env->P.E);
-    return AIE_E_INVALID;
-  }
-  const aie_sampler_args S = aie_sampler_args_of(&env->P, env->d_params);
-  aie_policy_eval_args A;
-  memset(&A, 0, sizeof(A));
-  const aie_sampler_group* sg[2] = {&S.agents, &S.planner};
-  aie_policy_eval_group* eg[2] = {&A.agents, &A.planner};
-  const float* lg[2] = {lg_a, lg_p};
-  const float* mk[2] = {mk_a, mk_p};
-  for (int c = 0; c < 2; ++c) {
-    aie_policy_eval_group& G = *eg[c];
-    const aie_sampler_group& s = *sg[c];
-    G.lg = lg[c];
-    G.lg_bstride = s.lg_estride;
-    G.len = s.len;
-    G.lrs = s.lrs;
-    G.lsh = s.lsh;
-    G.rows = s.rows;
-    G.generic = (c == 0 && S.ragged) || s.len > 64;
-    if (mk[c]) {  // the caller's masks: the logits' layout
-      G.mk = mk[c];
-      G.mk_bstride = s.lg_estride;
-      G.mrs = s.lrs;
-      G.mks = 1;
-    } else {      // the arena's current masks
-      G.mk = reinterpret_cast<const float*>(env->arena + s.mk_off);
-      G.mk_bstride = s.mk_estride;
-      G.mrs = s.mrs;
-      G.mks = s.mks;
-    }
-    const int rpw = G.generic ? 1 : 64 >> s.lsh;
-    G.items = lg[c] ? (s.rows + rpw - 1) / rpw : 0;
-  }
-  A.params = env->d_params;
-  A.B = (uint32_t)B;
-  A.items = (uint32_t)(A.agents.items + A.planner.items);
-  A.act_a_width = S.act_a_width;
-  A.ragged = S.ragged;
-  if (A.items && B * (int64_t)A.items > 0x7fffff00ll) {
-    snprintf(env->err, sizeof(env->err), "%s: B = %lld is more than one launch takes (%u wavefronts per batch element)", who,
-             (long long)B, A.items);
-    return AIE_E_INVALID;
-  }
-  *out = A;
-  return AIE_OK;
-}
-
+// ---- the trainer calls: a host plan (aie_trainer_plan.h: checks, kernel argument, launch geometry), then the launches ----
+static int aie_launched(aie_env* env) { AIE_HIP_CHECK(env, hipGetLastError()); return AIE_OK; }  // every trainer call's last line
 int aie_policy_evaluate(aie_env* env, int64_t B, const float* d_logits_a, const float* d_logits_p, const float* d_masks_a,
                         const float* d_masks_p, const int32_t* d_actions_a, const int32_t* d_actions_p, float* d_logp_a,
                         float* d_logp_p, float* d_entropy_a, float* d_entropy_p, void* stream) {
   if (!env) return AIE_E_INVALID;
-  if ((d_logp_a && !(d_logits_a && d_actions_a)) || (d_logp_p && !(d_logits_p && d_actions_p)) || (d_entropy_a && !d_logits_a) ||
-      (d_entropy_p && !d_logits_p)) {
-    snprintf(env->err, sizeof(env->err), "aie_policy_evaluate: an output without its logits (logp: and its stored actions)");
-    return AIE_E_INVALID;
-  }
-  aie_policy_eval_args A;
-  // (an actor class none of whose outputs is asked for is left out of the launch)
-  const int rc = aie_policy_eval_args_of(env, "aie_policy_evaluate", B, (d_logp_a || d_entropy_a) ? d_logits_a : nullptr,
-                                         (d_logp_p || d_entropy_p) ? d_logits_p : nullptr, d_masks_a, d_masks_p, &A);
-  if (rc != AIE_OK) return rc;
-  if (!A.items) return AIE_OK;
-  A.agents.act = d_actions_a;
-  A.planner.act = d_actions_p;
-  A.agents.logp = d_logp_a;
-  A.planner.logp = d_logp_p;
-  A.agents.ent = d_entropy_a;
-  A.planner.ent = d_entropy_p;
+  aie_eval_plan p;
+  if (const int rc = aie_plan_policy_evaluate(&env->P, env->d_params, env->arena, B, d_logits_a, d_logits_p, d_masks_a, d_masks_p,
+                                              d_actions_a, d_actions_p, d_logp_a, d_logp_p, d_entropy_a, d_entropy_p, env->err,
+                                              sizeof(env->err), &p))
+    return rc;
+  if (!p.grid) return AIE_OK;
   AIE_HIP_CHECK(env, hipSetDevice(env->device));
-  hipLaunchKernelGGL(aie_policy_eval_kernel, dim3((unsigned)((B * A.items + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), A);
-  AIE_HIP_CHECK(env, hipGetLastError());
-  return AIE_OK;
+  hipLaunchKernelGGL(aie_policy_eval_kernel, dim3(p.grid), dim3(p.block), 0, static_cast<hipStream_t>(stream), p.A);
+  return aie_launched(env);
 }
 
 int aie_policy_evaluate_backward(aie_env* env, int64_t B, const float* d_logits_a, const float* d_logits_p, const float* d_masks_a,
@@ -1019,401 +956,100 @@ int aie_policy_evaluate_backward(aie_env* env, int64_t B, const float* d_logits_
                                  const float* d_glogp_a, const float* d_glogp_p, const float* d_gentropy_a,
                                  const float* d_gentropy_p, float* d_grad_logits_a, float* d_grad_logits_p, void* stream) {
   if (!env) return AIE_E_INVALID;
-  if ((d_grad_logits_a && !d_logits_a) || (d_grad_logits_p && !d_logits_p) || (d_glogp_a && !d_actions_a) ||
-      (d_glogp_p && !d_actions_p)) {
-    snprintf(env->err, sizeof(env->err), "aie_policy_evaluate_backward: a gradient buffer without its logits, or a logp gradient "
-             "without the stored actions");
-    return AIE_E_INVALID;
-  }
-  aie_policy_eval_args A;
-  const int rc = aie_policy_eval_args_of(env, "aie_policy_evaluate_backward", B, d_grad_logits_a ? d_logits_a : nullptr,
-                                         d_grad_logits_p ? d_logits_p : nullptr, d_masks_a, d_masks_p, &A);
-  if (rc != AIE_OK) return rc;
-  if (!A.items) return AIE_OK;
-  A.agents.act = d_actions_a;
-  A.planner.act = d_actions_p;
-  A.agents.g_logp = d_glogp_a;
-  A.planner.g_logp = d_glogp_p;
-  A.agents.g_ent = d_gentropy_a;
-  A.planner.g_ent = d_gentropy_p;
-  A.agents.grad = d_grad_logits_a;
-  A.planner.grad = d_grad_logits_p;
+  aie_eval_plan p;
+  if (const int rc = aie_plan_policy_evaluate_backward(&env->P, env->d_params, env->arena, B, d_logits_a, d_logits_p, d_masks_a,
+                                                       d_masks_p, d_actions_a, d_actions_p, d_glogp_a, d_glogp_p, d_gentropy_a,
+                                                       d_gentropy_p, d_grad_logits_a, d_grad_logits_p, env->err, sizeof(env->err), &p))
+    return rc;
+  if (!p.grid) return AIE_OK;
   AIE_HIP_CHECK(env, hipSetDevice(env->device));
-  hipLaunchKernelGGL(aie_policy_eval_bwd_kernel, dim3((unsigned)((B * A.items + 3) / 4)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), A);
-  AIE_HIP_CHECK(env, hipGetLastError());
-  return AIE_OK;
+  hipLaunchKernelGGL(aie_policy_eval_bwd_kernel, dim3(p.grid), dim3(p.block), 0, static_cast<hipStream_t>(stream), p.A);
+  return aie_launched(env);
 }
 
 int aie_gae(aie_env* env, int32_t T, const float* d_log, int32_t n_slots, int32_t first_slot, const float* d_values_a,
             const float* d_values_p, float gamma, float lambda, float* d_adv_a, float* d_adv_p, float* d_ret_a, float* d_ret_p,
             void* stream) {
   if (!env) return AIE_E_INVALID;
-  if (T < 1 || T > n_slots || first_slot < 0 || first_slot >= n_slots || !d_log) {
-    snprintf(env->err, sizeof(env->err), "aie_gae: T = %d steps from slot %d of a log of %d slots at %p (needs a log, 1 <= T <= "
-             "n_slots, 0 <= first_slot < n_slots)", T, first_slot, n_slots, (const void*)d_log);
-    return AIE_E_INVALID;
-  }
-  if (((d_adv_a || d_ret_a) && !d_values_a) || ((d_adv_p || d_ret_p) && !d_values_p)) {
-    snprintf(env->err, sizeof(env->err), "aie_gae: an output without its values");
-    return AIE_E_INVALID;
-  }
-  const int64_t row = (int64_t)env->P.E * (env->P.n + 2);
-  if (row > 0x7fffff00ll) {
-    snprintf(env->err, sizeof(env->err), "aie_gae: %lld floats per log row are more than one launch takes", (long long)row);
-    return AIE_E_INVALID;
-  }
-  aie_gae_args A;
-  memset(&A, 0, sizeof(A));
-  A.log = d_log;
-  // (an actor class none of whose outputs is asked for is left out of the launch)
-  A.va = (d_adv_a || d_ret_a) ? d_values_a : nullptr;
-  A.vp = (d_adv_p || d_ret_p) ? d_values_p : nullptr;
-  if (!A.va && !A.vp) return AIE_OK;
-  A.adv_a = d_adv_a;
-  A.adv_p = d_adv_p;
-  A.ret_a = d_ret_a;
-  A.ret_p = d_ret_p;
-  A.T = T;
-  A.slots = n_slots;
-  A.first = first_slot;
-  A.E = env->P.E;
-  A.n = env->P.n;
-  A.gamma = gamma;
-  A.gl = aie_gae_gl(gamma, lambda);
+  aie_gae_plan p;
+  if (const int rc = aie_plan_gae(&env->P, T, d_log, n_slots, first_slot, d_values_a, d_values_p, gamma, lambda, d_adv_a, d_adv_p,
+                                  d_ret_a, d_ret_p, env->err, sizeof(env->err), &p))
+    return rc;
+  if (!p.grid) return AIE_OK;
   AIE_HIP_CHECK(env, hipSetDevice(env->device));
-  hipLaunchKernelGGL(aie_gae_kernel, dim3((unsigned)((row + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream), A);
-  AIE_HIP_CHECK(env, hipGetLastError());
-  return AIE_OK;
+  hipLaunchKernelGGL(aie_gae_kernel, dim3(p.grid), dim3(p.block), 0, static_cast<hipStream_t>(stream), p.A);
+  return aie_launched(env);
 }
 
-// The wavefronts aie_ppo_loss launches for B batch elements of `items` work items each, and its workspace: a record each.
-static uint32_t aie_ppo_waves(int64_t work, int64_t bound) { return (uint32_t)(work < bound ? work : bound); }
-int64_t aie_ppo_workspace_bytes(const aie_env* env, int64_t B) {
-  if (!env || B < 1) return AIE_E_INVALID;
-  // (at most one work item per actor: n agents and the planner)
-  const int64_t per = (int64_t)env->P.n + 1;
-  const int64_t work = B > AIE_PPO_MAX_WAVES / per ? (int64_t)AIE_PPO_MAX_WAVES : B * per;
-  return (int64_t)aie_ppo_waves(work, AIE_PPO_MAX_WAVES) * AIE_PPO_RECORD * (int64_t)sizeof(double);
+// a call's own workspace: device memory, aligned, of at least the plan's `need` bytes (`query` names the function that sizes it)
+static int aie_check_workspace(aie_env* env, const char* fn, const char* query, void* d_workspace, int64_t workspace_bytes,
+                               int64_t need, unsigned align) {
+  if (d_workspace && !(reinterpret_cast<uintptr_t>(d_workspace) & (align - 1u)) && workspace_bytes >= need) return AIE_OK;
+  snprintf(env->err, sizeof(env->err), "%s: the workspace (%p, %lld bytes) must be device memory, %u-byte aligned, of at least "
+           "%lld bytes (%s)", fn, d_workspace, (long long)workspace_bytes, align, (long long)need, query);
+  return AIE_E_INVALID;
 }
+
+int64_t aie_ppo_workspace_bytes(const aie_env* env, int64_t B) { return env ? aie_plan_ppo_workspace_bytes(&env->P, B) : AIE_E_INVALID; }
 int aie_ppo_loss(aie_env* env, int64_t B, const aie_ppo_class* agents, const aie_ppo_class* planner, const int32_t* d_index,
                  void* d_workspace, int64_t workspace_bytes, void* stream) {
   if (!env) return AIE_E_INVALID;
-  const aie_ppo_class* cls[2] = {agents, planner};
-  for (int c = 0; c < 2; ++c) {
-    const aie_ppo_class* k = cls[c];
-    if (!k) continue;
-    if (!k->logits || !k->masks || !k->actions || !k->logp_old || !k->adv || !k->grad_logits || !k->stats ||
-        (k->values && (!k->values_old || !k->returns || !k->grad_values)) || (!k->values && k->grad_values) || !(k->clip > 0.0f)) {
-      snprintf(env->err, sizeof(env->err), "aie_ppo_loss: the %s class needs logits, masks, actions, logp_old, adv, grad_logits and "
-               "stats, with values also values_old, returns and grad_values (and no grad_values without), and clip > 0 (%g)",
-               c ? "planner's" : "agents'", (double)k->clip);
-      return AIE_E_INVALID;
-    }
-  }
-  // the rows' shape is the evaluator's (B < 1 and the samplers' refusals are its own)
-  aie_policy_eval_args E;
-  const int rc = aie_policy_eval_args_of(env, "aie_ppo_loss", B, agents ? agents->logits : nullptr, planner ? planner->logits : nullptr,
-                                         agents ? agents->masks : nullptr, planner ? planner->masks : nullptr, &E);
-  if (rc != AIE_OK) return rc;
-  if (!E.items) return AIE_OK;
-  aie_ppo_args A;
-  memset(&A, 0, sizeof(A));
-  const aie_policy_eval_group* eg[2] = {&E.agents, &E.planner};
-  aie_ppo_group* pg[2] = {&A.agents, &A.planner};
-  const int width[2] = {env->P.act_a_width, env->P.act_p_width};
-  for (int c = 0; c < 2; ++c) {
-    const aie_ppo_class* k = cls[c];
-    if (!k) continue;
-    const aie_policy_eval_group& e = *eg[c];
-    aie_ppo_group& G = *pg[c];
-    G.lg = k->logits;
-    G.val = k->values;
-    G.mk = k->masks;
-    G.act = k->actions;
-    G.lp_old = k->logp_old;
-    G.adv = k->adv;
-    G.val_old = k->values_old;
-    G.ret = k->returns;
-    G.mom = k->adv_moments;
-    G.grad = k->grad_logits;
-    G.grad_v = k->grad_values;
-    G.stats = k->stats;
-    G.lg_bstride = e.lg_bstride;
-    G.len = e.len;
-    G.lrs = e.lrs;
-    G.lsh = e.lsh;
-    G.rows = e.rows;
-    G.w = width[c] > 0 ? width[c] : 1;
-    G.actors = e.rows / G.w;
-    if (G.w > 64 || G.actors * G.w != e.rows) {
-      snprintf(env->err, sizeof(env->err), "aie_ppo_loss: %d action slots per actor (%d rows) are more than a wavefront holds", G.w, e.rows);
-      return AIE_E_UNSUPPORTED;
-    }
-    G.generic = e.generic || G.w > 1;
-    const int rpw = G.generic ? 1 : 64 >> e.lsh;
-    G.items = G.generic ? G.actors : (e.rows + rpw - 1) / rpw;
-    G.clip = k->clip;
-    G.vf_clip = k->vf_clip;
-    G.vf_coef = k->vf_coef;
-    G.ent_coef = k->ent_coef;
-    G.scale = aie_ppo_scale(B * (int64_t)G.actors);
-    G.g_H = -aie_ppo_product(G.scale, k->ent_coef);
-    G.kv = aie_ppo_product(G.scale, k->vf_coef);
-  }
-  A.params = env->d_params;
-  A.index = d_index;
-  A.ws = static_cast<double*>(d_workspace);
-  A.B = (uint32_t)B;
-  A.items = (uint32_t)(A.agents.items + A.planner.items);
-  A.act_a_width = E.act_a_width;
-  A.ragged = E.ragged;
-  const int64_t work = B * (int64_t)A.items;
-  if (work > 0x7fffff00ll) {
-    snprintf(env->err, sizeof(env->err), "aie_ppo_loss: B = %lld is more than one call takes (%u work items per batch element)",
-             (long long)B, A.items);
-    return AIE_E_INVALID;
-  }
+  aie_ppo_plan p;
+  if (const int rc = aie_plan_ppo_loss(&env->P, env->d_params, env->arena, B, agents, planner, d_index, d_workspace, env->err,
+                                       sizeof(env->err), &p))
+    return rc;
+  if (!p.grid) return AIE_OK;
+  if (const int rc = aie_check_workspace(env, "aie_ppo_loss", "aie_ppo_workspace_bytes", d_workspace, workspace_bytes, p.need, 8))
+    return rc;
   AIE_HIP_CHECK(env, hipSetDevice(env->device));
-  // (the whole bound, although 89 registers leave only 5120 wavefronts resident at once: sized to residency the kernel took
-  // 2.4 x as long on a fragment of 819 200 rows -- DESIGN_HISTORY.md, item 10 -- it lives on loads in flight, not on rounds)
-  A.waves = aie_ppo_waves(work, AIE_PPO_MAX_WAVES);
-  const int64_t need = (int64_t)A.waves * AIE_PPO_RECORD * (int64_t)sizeof(double);
-  if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 7u) || workspace_bytes < need) {
-    snprintf(env->err, sizeof(env->err), "aie_ppo_loss: the workspace (%p, %lld bytes) must be device memory, 8-byte aligned, of at "
-             "least %lld bytes (aie_ppo_workspace_bytes)", d_workspace, (long long)workspace_bytes, (long long)need);
-    return AIE_E_INVALID;
-  }
-  hipLaunchKernelGGL(aie_ppo_loss_kernel, dim3((A.waves + 3u) / 4u), dim3(256), 0, static_cast<hipStream_t>(stream), A);
-  hipLaunchKernelGGL(aie_ppo_reduce_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), A);
-  AIE_HIP_CHECK(env, hipGetLastError());
-  return AIE_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(aie_ppo_loss_kernel, dim3(p.grid), dim3(p.block), 0, s, p.A);
+  hipLaunchKernelGGL(aie_ppo_reduce_kernel, dim3(p.reduce_grid), dim3(p.reduce_block), 0, s, p.A);
+  return aie_launched(env);
 }
 
 int aie_policy_mlp_forward(aie_env* env, int64_t B, const aie_mlp_class* agents, const aie_mlp_class* planner, void* stream) {
   if (!env) return AIE_E_INVALID;
-  if (B < 1) {
-    snprintf(env->err, sizeof(env->err), "aie_policy_mlp_forward: B = %lld (needs B >= 1)", (long long)B);
-    return AIE_E_INVALID;
-  }
-  constexpr int TM = AIE_MLP_TILE_ROWS;
-  static_assert(TM == 32 || TM == 64, "the kernel's row tile is 2 or 4 MFMA tiles");
-  const aie_mlp_class* cls[2] = {agents, planner};
-  aie_mlp_args A;
-  memset(&A, 0, sizeof(A));
-  aie_mlp_group* grp[2] = {&A.agents, &A.planner};
-  size_t lds = 0;
-  int64_t blocks = 0;
-  for (int c = 0; c < 2; ++c) {
-    const aie_mlp_class* k = cls[c];
-    if (!k) continue;
-    const char* who = c ? "planner's" : "agents'";
-    if (k->F < 1 || k->F > 1024 || k->M < 1 || k->M > 1024 || k->x_ld < k->F || !k->x || !k->w1 || !k->b1 || !k->w2 || !k->b2 ||
-        !k->w3 || !k->b3 || !k->logits || (k->wv != nullptr) != (k->values != nullptr) || (k->wv != nullptr) != (k->bv != nullptr)) {
-      snprintf(env->err, sizeof(env->err), "aie_policy_mlp_forward: the %s class needs F (%d) and M (%d) in 1 .. 1024, x_ld (%lld) >= F, "
-               "x, w1, b1, w2, b2, w3, b3 and logits, and wv, bv and values all three or none", who, k->F, k->M, (long long)k->x_ld);
-      return AIE_E_INVALID;
-    }
-    if (k->H < 16 || k->H > 256 || (k->H & 15)) {
-      snprintf(env->err, sizeof(env->err), "aie_policy_mlp_forward: the %s hidden width %d is not a multiple of 16 in 16 .. 256", who, k->H);
-      return AIE_E_UNSUPPORTED;
-    }
-    aie_mlp_group& G = *grp[c];
-    G.x = k->x, G.x_ld = k->x_ld;
-    G.w1 = k->w1, G.b1 = k->b1, G.w2 = k->w2, G.b2 = k->b2, G.w3 = k->w3, G.b3 = k->b3, G.wv = k->wv, G.bv = k->bv;
-    G.logits = k->logits, G.values = k->values;
-    G.F = k->F, G.H = k->H, G.M = k->M;
-    G.rows = c ? B : B * (int64_t)env->P.n;
-    const int kpad = (k->F + 3) & ~3, chunk = kpad < AIE_MLP_CHUNK ? kpad : AIE_MLP_CHUNK;
-    G.lds_a = (chunk > k->H ? chunk : k->H) + 2;
-    G.lds_h = k->H + 2;
-    const int64_t nb = (G.rows + TM - 1) / TM;
-    if (nb > 0x3fffffffll) {
-      snprintf(env->err, sizeof(env->err), "aie_policy_mlp_forward: B = %lld is more than one launch takes", (long long)B);
-      return AIE_E_INVALID;
-    }
-    G.blocks = (int32_t)nb;
-    blocks += nb;
-    const size_t need = (size_t)TM * (size_t)(G.lds_a + G.lds_h) * sizeof(float);
-    lds = need > lds ? need : lds;
-  }
-  if (!blocks) return AIE_OK;
-  if (blocks > 0x7fffff00ll) {
-    snprintf(env->err, sizeof(env->err), "aie_policy_mlp_forward: B = %lld is more than one launch takes (%lld workgroups)",
-             (long long)B, (long long)blocks);
-    return AIE_E_INVALID;
-  }
+  aie_mlp_fwd_plan p;
+  if (const int rc = aie_plan_mlp_forward(&env->P, B, agents, planner, env->err, sizeof(env->err), &p)) return rc;
+  if (!p.grid) return AIE_OK;
   AIE_HIP_CHECK(env, hipSetDevice(env->device));
-  hipLaunchKernelGGL(aie_policy_mlp_kernel, dim3((unsigned)blocks), dim3(256), lds, static_cast<hipStream_t>(stream), A);
-  AIE_HIP_CHECK(env, hipGetLastError());
-  return AIE_OK;
+  hipLaunchKernelGGL(aie_policy_mlp_kernel, dim3(p.grid), dim3(p.block), p.lds, static_cast<hipStream_t>(stream), p.A);
+  return aie_launched(env);
 }
 
-// aie_policy_mlp_backward's plan: the checks, the kernels' argument without the workspace pointers, and each class's share
-// of the workspace in floats.  err: where a refusal names itself (nullptr: nowhere).
-static int aie_mlp_bwd_plan(const aie_env* env, char* err, size_t err_size, int64_t B, const aie_mlp_grad_class* const (&cls)[2],
-                            aie_mlp_bwd_args* A, int64_t (&ws_floats)[2]) {
-  constexpr int TM = AIE_MLP_TILE_ROWS;
-  const char* fn = "aie_policy_mlp_backward";
-  memset(A, 0, sizeof(*A));
-  ws_floats[0] = ws_floats[1] = 0;
-  if (B < 1) {
-    if (err) snprintf(err, err_size, "%s: B = %lld (needs B >= 1)", fn, (long long)B);
-    return AIE_E_INVALID;
-  }
-  aie_mlp_bwd_group* grp[2] = {&A->agents, &A->planner};
-  for (int c = 0; c < 2; ++c) {
-    const aie_mlp_grad_class* q = cls[c];
-    if (!q) continue;
-    const aie_mlp_class* k = &q->net;
-    const char* who = c ? "planner's" : "agents'";
-    const bool v = k->wv != nullptr;
-    if (k->F < 1 || k->F > 1024 || k->M < 1 || k->M > 1024 || k->x_ld < k->F || !k->x || !k->w1 || !k->b1 || !k->w2 || !k->b2 ||
-        !k->w3 || !k->b3 || v != (k->bv != nullptr)) {
-      if (err) snprintf(err, err_size, "%s: the %s class needs F (%d) and M (%d) in 1 .. 1024, x_ld (%lld) >= F, x, w1, b1, w2, b2, w3 "
-                        "and b3, and wv and bv both or neither", fn, who, k->F, k->M, (long long)k->x_ld);
-      return AIE_E_INVALID;
-    }
-    if (!q->g_logits || !q->gw1 || !q->gb1 || !q->gw2 || !q->gb2 || !q->gw3 || !q->gb3 || v != (q->g_values != nullptr) ||
-        v != (q->gwv != nullptr) || v != (q->gbv != nullptr)) {
-      if (err) snprintf(err, err_size, "%s: the %s class needs g_logits, gw1, gb1, gw2, gb2, gw3 and gb3, and g_values, gwv and gbv "
-                        "exactly when it has wv", fn, who);
-      return AIE_E_INVALID;
-    }
-    if (k->H < 16 || k->H > 256 || (k->H & 15)) {
-      if (err) snprintf(err, err_size, "%s: the %s hidden width %d is not a multiple of 16 in 16 .. 256", fn, who, k->H);
-      return AIE_E_UNSUPPORTED;
-    }
-    aie_mlp_bwd_group& Q = *grp[c];
-    aie_mlp_group& G = Q.net;
-    G.x = k->x, G.x_ld = k->x_ld;
-    G.w1 = k->w1, G.b1 = k->b1, G.w2 = k->w2, G.b2 = k->b2, G.w3 = k->w3, G.b3 = k->b3, G.wv = k->wv, G.bv = k->bv;
-    G.F = k->F, G.H = k->H, G.M = k->M;
-    G.rows = c ? B : B * (int64_t)env->P.n;
-    const int kpad = (k->F + 3) & ~3, chunk = kpad < AIE_MLP_CHUNK ? kpad : AIE_MLP_CHUNK;
-    const int mpad = (k->M + 3) & ~3;
-    G.lds_a = (chunk > k->H ? chunk : k->H) + 2;
-    G.lds_h = k->H + 2;
-    Q.lds_c = (mpad < AIE_MLP_CHUNK ? mpad : AIE_MLP_CHUNK) + 2;
-    const int64_t nb = (G.rows + TM - 1) / TM, nseg = (G.rows + AIE_MLP_BWD_SEG - 1) / AIE_MLP_BWD_SEG;
-    if (nb > 0x3fffffffll) {
-      if (err) snprintf(err, err_size, "%s: B = %lld is more than one call takes", fn, (long long)B);
-      return AIE_E_INVALID;
-    }
-    G.blocks = (int32_t)nb;
-    Q.nseg = (int32_t)nseg;
-    Q.g_logits = q->g_logits, Q.g_values = q->g_values;
-    Q.gw1 = q->gw1, Q.gb1 = q->gb1, Q.gw2 = q->gw2, Q.gb2 = q->gb2, Q.gw3 = q->gw3, Q.gb3 = q->gb3, Q.gwv = q->gwv, Q.gbv = q->gbv;
-    Q.N3 = k->M + (v ? 1 : 0);
-    Q.off2 = (k->F + 1) * k->H;
-    Q.off3 = Q.off2 + (k->H + 1) * k->H;
-    Q.P = Q.off3 + (k->H + 1) * Q.N3;
-    const int Ks[3] = {k->F, k->H, k->H}, Ns[3] = {k->H, k->H, Q.N3};
-    for (int L = 0; L < 3; ++L) {
-      Q.cg[L] = (((Ns[L] + 15) >> 4) + 3) >> 2;
-      Q.items[L] = ((((Ks[L] + 1 + 15) >> 4) + 3) >> 2) * Q.cg[L];  // groups of four bands x column groups
-      Q.per_seg += Q.items[L];
-    }
-    Q.n_items = nseg * Q.per_seg;
-    const int64_t fl = 4 * G.rows * k->H + nseg * Q.P;
-    ws_floats[c] = (fl + 63) & ~(int64_t)63;
-  }
-  return AIE_OK;
-}
 int64_t aie_policy_mlp_backward_workspace_bytes(const aie_env* env, int64_t B, const aie_mlp_grad_class* agents,
                                                 const aie_mlp_grad_class* planner) {
   if (!env) return AIE_E_INVALID;
-  const aie_mlp_grad_class* const cls[2] = {agents, planner};
-  aie_mlp_bwd_args A;
-  int64_t fl[2];
-  const int rc = aie_mlp_bwd_plan(env, nullptr, 0, B, cls, &A, fl);
-  return rc != AIE_OK ? rc : (fl[0] + fl[1]) * (int64_t)sizeof(float);
+  aie_mlp_bwd_plan p;
+  const int rc = aie_plan_mlp_backward(&env->P, B, agents, planner, nullptr, 0, &p);
+  return rc != AIE_OK ? rc : p.need;
 }
 int aie_policy_mlp_backward(aie_env* env, int64_t B, const aie_mlp_grad_class* agents, const aie_mlp_grad_class* planner,
                             void* d_workspace, int64_t workspace_bytes, void* stream) {
   if (!env) return AIE_E_INVALID;
-  constexpr int TM = AIE_MLP_TILE_ROWS;
-  const aie_mlp_grad_class* const cls[2] = {agents, planner};
-  aie_mlp_bwd_args A;
-  int64_t fl[2];
-  const int rc = aie_mlp_bwd_plan(env, env->err, sizeof(env->err), B, cls, &A, fl);
-  if (rc != AIE_OK) return rc;
+  aie_mlp_bwd_plan p;
+  if (const int rc = aie_plan_mlp_backward(&env->P, B, agents, planner, env->err, sizeof(env->err), &p)) return rc;
   if (!agents && !planner) return AIE_OK;
-  const int64_t need = (fl[0] + fl[1]) * (int64_t)sizeof(float);
-  if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 15u) || workspace_bytes < need) {
-    snprintf(env->err, sizeof(env->err), "aie_policy_mlp_backward: the workspace (%p, %lld bytes) must be device memory, 16-byte "
-             "aligned, of at least %lld bytes (aie_policy_mlp_backward_workspace_bytes)", d_workspace, (long long)workspace_bytes,
-             (long long)need);
-    return AIE_E_INVALID;
-  }
-  aie_mlp_bwd_group* grp[2] = {&A.agents, &A.planner};
-  float* ws = static_cast<float*>(d_workspace);
-  size_t lds = 0;
-  int64_t blocks = 0, items = 0, rblocks = 0;
-  for (int c = 0; c < 2; ++c) {
-    if (!cls[c]) continue;
-    aie_mlp_bwd_group& Q = *grp[c];
-    const int64_t rh = Q.net.rows * Q.net.H;
-    Q.h1 = ws, Q.h2 = ws + rh, Q.dz2 = ws + 2 * rh, Q.dz1 = ws + 3 * rh, Q.partial = ws + 4 * rh;
-    ws += fl[c];
-    blocks += Q.net.blocks;
-    items += Q.n_items;
-    const int64_t rb = (Q.P + 255) / 256;
-    if (!c) A.reduce_blocks_a = (int32_t)rb;
-    rblocks += rb;
-    const size_t l = (size_t)TM * (size_t)(Q.net.lds_a + Q.net.lds_h + Q.lds_c) * sizeof(float);
-    lds = l > lds ? l : lds;
-  }
-  if (blocks > 0x7fffff00ll || items > 0x7fffff00ll) {
-    snprintf(env->err, sizeof(env->err), "aie_policy_mlp_backward: B = %lld is more than one call takes", (long long)B);
-    return AIE_E_INVALID;
-  }
+  if (const int rc = aie_check_workspace(env, "aie_policy_mlp_backward", "aie_policy_mlp_backward_workspace_bytes", d_workspace,
+                                         workspace_bytes, p.need, 16))
+    return rc;
+  if (const int rc = aie_plan_mlp_backward_launch(&p, B, agents, planner, d_workspace, env->err, sizeof(env->err))) return rc;
   AIE_HIP_CHECK(env, hipSetDevice(env->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(aie_policy_mlp_bwd_rows_kernel, dim3((unsigned)blocks), dim3(256), lds, s, A);
-  hipLaunchKernelGGL(aie_policy_mlp_bwd_atd_kernel, dim3((unsigned)items), dim3(256), 0, s, A);
-  hipLaunchKernelGGL(aie_policy_mlp_bwd_reduce_kernel, dim3((unsigned)rblocks), dim3(256), 0, s, A);
-  AIE_HIP_CHECK(env, hipGetLastError());
-  return AIE_OK;
+  hipLaunchKernelGGL(aie_policy_mlp_bwd_rows_kernel, dim3(p.grid_rows), dim3(p.block), p.lds, s, p.A);
+  hipLaunchKernelGGL(aie_policy_mlp_bwd_atd_kernel, dim3(p.grid_atd), dim3(p.block), 0, s, p.A);
+  hipLaunchKernelGGL(aie_policy_mlp_bwd_reduce_kernel, dim3(p.grid_reduce), dim3(p.block), 0, s, p.A);
+  return aie_launched(env);
 }
 
 int aie_trajectory_store(aie_env* env, const aie_traj_segment* segs, int32_t n_segs, int32_t n_slots, int32_t* d_slot, void* stream) {
   if (!env) return AIE_E_INVALID;
-  static_assert(AIE_TRAJ_SEGMENTS == AIE_TRAJ_MAX_SEGMENTS, "aie_layout.h and aie.h disagree on the segment count");
-  if (!segs || n_segs < 1 || n_segs > AIE_TRAJ_MAX_SEGMENTS || n_slots < 1 || !d_slot) {
-    snprintf(env->err, sizeof(env->err), "aie_trajectory_store: %d segments (1 .. %d), %d slots (>= 1), segments and slot counters "
-             "not NULL", n_segs, AIE_TRAJ_MAX_SEGMENTS, n_slots);
-    return AIE_E_INVALID;
-  }
-  aie_traj_args A;
-  memset(&A, 0, sizeof(A));
-  for (int g = 0; g < n_segs; ++g) {
-    const aie_traj_segment& s = segs[g];
-    const uintptr_t sp = reinterpret_cast<uintptr_t>(s.src), dp = reinterpret_cast<uintptr_t>(s.dst);
-    const int64_t count = s.bytes / 4;
-    if (!s.src || !s.dst || s.bytes < 4 || (s.bytes & 3) || (s.src_stride & 3) || (sp & 3) || (dp & 3) || s.rows < 0 ||
-        s.rows > 32767 || (s.rows > 1 && count % s.rows)) {
-      snprintf(env->err, sizeof(env->err), "aie_trajectory_store: segment %d (%d bytes per replica, source stride %lld, rows %d): "
-               "pointers not NULL and 4-byte aligned, sizes and strides multiples of 4, rows dividing the element count", g,
-               s.bytes, (long long)s.src_stride, s.rows);
-      return AIE_E_INVALID;
-    }
-    aie_traj_seg_k& k = A.seg[g];
-    k.src = static_cast<const uint8_t*>(s.src);
-    k.dst = static_cast<uint8_t*>(s.dst);
-    k.src_stride = s.src_stride;
-    k.bytes = s.bytes;
-    k.rows = (int16_t)s.rows;
-    k.wide = (int16_t)(s.rows <= 1 && !((sp | dp | (uintptr_t)s.src_stride | (uintptr_t)s.bytes) & 15));
-  }
-  A.slot = d_slot;
-  A.n_segs = n_segs;
-  A.n_slots = n_slots;
-  A.E = env->P.E;
+  aie_traj_plan p;
+  if (const int rc = aie_plan_trajectory_store(&env->P, segs, n_segs, n_slots, d_slot, env->err, sizeof(env->err), &p)) return rc;
   AIE_HIP_CHECK(env, hipSetDevice(env->device));
-  hipLaunchKernelGGL(aie_trajectory_store_kernel, dim3((unsigned)env->P.E), dim3(256), 0, static_cast<hipStream_t>(stream), A);
-  AIE_HIP_CHECK(env, hipGetLastError());
-  return AIE_OK;
+  hipLaunchKernelGGL(aie_trajectory_store_kernel, dim3(p.grid), dim3(p.block), 0, static_cast<hipStream_t>(stream), p.A);
+  return aie_launched(env);
 }
 
 // Which step kernel runs this environment: >= 0 = compile-time instance (index into aie_spec_generated.h), -1 = generic.

@@ -1,12 +1,14 @@
 """Device backend: owns the arena (a torch uint8 CUDA/HIP tensor), the `aie_env` handle
 and zero-copy torch views of every exported tensor.  torch is plumbing here (memory,
 streams, distributed); all compute happens in the HIP kernels behind the C ABI.
+The environment's own calls are here; the trainer operators are the mixin _trainer_ops.TrainerOps.
 """
 import ctypes as C
 
 import numpy as np
 
 from . import _cabi, _native
+from ._trainer_ops import TrainerOps
 
 _TORCH_DTYPES = None
 
@@ -25,7 +27,7 @@ class AieError(RuntimeError):
     pass
 
 
-class DeviceBackend:
+class DeviceBackend(TrainerOps):
     def __init__(self, cfg, layout_planes, device=None):
         torch = _torch()
         if not torch.cuda.is_available():
@@ -357,385 +359,6 @@ class DeviceBackend:
         out[0].view(ma.shape).copy_(ma)
         out[1].view(mp.shape).copy_(mp)
         return out[0], out[1]
-
-    def _policy_eval_operands(self, logits_a, logits_p, masks_a, masks_p, actions_a, actions_p):
-        """Contiguous device operands of aie_policy_evaluate / _backward and the batch size B they agree on."""
-        torch = _torch()
-        per_a = self.tensors["obs_a_action_mask"].numel() // self.E
-        per_p = self.tensors["obs_p_action_mask"].numel() // self.E
-        aa, ap = self._action_buffers(0)
-        act_a, act_p = aa.numel() // self.E, ap.numel() // self.E
-
-        def dev(t, dtype):
-            if t is None:
-                return None
-            if not isinstance(t, torch.Tensor):
-                t = torch.as_tensor(np.asarray(t))
-            return t.to(device=self.device, dtype=dtype).contiguous()
-
-        ops = dict(la=dev(logits_a, torch.float32), lp=dev(logits_p, torch.float32), ma=dev(masks_a, torch.float32),
-                   mp=dev(masks_p, torch.float32), aa=dev(actions_a, torch.int32), ap=dev(actions_p, torch.int32))
-        per = dict(la=per_a, lp=per_p, ma=per_a, mp=per_p, aa=act_a, ap=act_p)
-        Bs = set()
-        for k, t in ops.items():
-            if t is not None:
-                if t.numel() == 0 or t.numel() % per[k]:
-                    raise ValueError("policy evaluation: operand %r has %d elements, not a multiple of the %d per batch element"
-                                     % (k, t.numel(), per[k]))
-                Bs.add(t.numel() // per[k])
-        if len(Bs) != 1:
-            raise ValueError("policy evaluation: the operands disagree on the batch size (%s)" % sorted(Bs))
-        return ops, Bs.pop(), (act_a, act_p, per_a, per_p)
-
-    def policy_evaluate(self, logits_a, logits_p, masks_a, masks_p, actions_a, actions_p, entropy=True):
-        """aie_policy_evaluate: (logp_a, logp_p, entropy_a, entropy_p) of stored actions under stored masks for the given
-        logits, B batch elements (any B: the operands' leading extent(s); with masks None -- the arena's current masks
-        -- B = E).  Layouts as sample_policy_actions / action_masks; either actor class may be None (its outputs are
-        None).  One launch on the current stream."""
-        torch = _torch()
-        ops, B, (act_a, act_p, _, _) = self._policy_eval_operands(logits_a, logits_p, masks_a, masks_p, actions_a, actions_p)
-        f = dict(dtype=torch.float32, device=self.device)
-        sa, sp = ((B,) + tuple(t.shape[1:]) for t in self._action_buffers(0))
-        out = [torch.empty(sa, **f) if ops["la"] is not None and ops["aa"] is not None else None,
-               torch.empty(sp, **f) if ops["lp"] is not None and ops["ap"] is not None else None,
-               torch.empty(sa, **f) if ops["la"] is not None and entropy else None,
-               torch.empty(sp, **f) if ops["lp"] is not None and entropy else None]
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        self._check(self.lib.aie_policy_evaluate(
-            self.handle, C.c_int64(B), ptr(ops["la"]), ptr(ops["lp"]), ptr(ops["ma"]), ptr(ops["mp"]), ptr(ops["aa"]), ptr(ops["ap"]),
-            ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), self._stream()))
-        return tuple(out)
-
-    def policy_evaluate_backward(self, logits_a, logits_p, masks_a, masks_p, actions_a, actions_p,
-                                 g_logp_a=None, g_logp_p=None, g_entropy_a=None, g_entropy_p=None):
-        """aie_policy_evaluate_backward: (grad_logits_a, grad_logits_p), the logits' shapes, of
-        sum(g_logp * logp + g_entropy * entropy); a None gradient counts as zeros.  One launch on the current stream."""
-        torch = _torch()
-        ops, B, (act_a, act_p, _, _) = self._policy_eval_operands(logits_a, logits_p, masks_a, masks_p, actions_a, actions_p)
-        gs = []
-        for g, per, what in ((g_logp_a, act_a, "g_logp_a"), (g_logp_p, act_p, "g_logp_p"), (g_entropy_a, act_a, "g_entropy_a"),
-                             (g_entropy_p, act_p, "g_entropy_p")):
-            if g is not None:
-                g = g.to(device=self.device, dtype=torch.float32).contiguous()
-                if g.numel() != B * per:
-                    raise ValueError("%s has %d elements, the batch needs %d" % (what, g.numel(), B * per))
-            gs.append(g)
-        grad_a = torch.empty_like(ops["la"]) if ops["la"] is not None else None
-        grad_p = torch.empty_like(ops["lp"]) if ops["lp"] is not None else None
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        self._check(self.lib.aie_policy_evaluate_backward(
-            self.handle, C.c_int64(B), ptr(ops["la"]), ptr(ops["lp"]), ptr(ops["ma"]), ptr(ops["mp"]), ptr(ops["aa"]), ptr(ops["ap"]),
-            ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gs[3]), ptr(grad_a), ptr(grad_p), self._stream()))
-        return grad_a, grad_p
-
-    def trajectory_segment(self, src, dst, transpose_rows=0):
-        """One aie_traj_segment: `src`, a device tensor whose dimension 0 is the replica ([E, ...], each replica's block
-        contiguous; the replica stride may be anything -- an arena tensor's, a record field's), stored into `dst`
-        ([n_slots, E, ...] contiguous, same dtype, same bytes per replica).  transpose_rows > 1: the replica's block is
-        [transpose_rows][cols] 4-byte elements and is stored as [cols][transpose_rows]."""
-        if src.shape[0] != self.E or dst.dim() < 2 or dst.shape[1] != self.E or src.dtype != dst.dtype:
-            raise ValueError("trajectory segment: src [E, ...] and dst [n_slots, E, ...] of one dtype")
-        if not dst.is_contiguous() or not src[0].is_contiguous():
-            raise ValueError("trajectory segment: dst and each replica's block of src must be contiguous")
-        nbytes = src[0].numel() * src.element_size()
-        if nbytes != dst[0, 0].numel() * dst.element_size():
-            raise ValueError("trajectory segment: %d bytes per replica in src, %d in dst"
-                             % (nbytes, dst[0, 0].numel() * dst.element_size()))
-        stride = (src.stride(0) if self.E > 1 else src[0].numel()) * src.element_size()
-        return _cabi.AieTrajSegment(src.data_ptr(), dst.data_ptr(), stride, nbytes, int(transpose_rows)), (src, dst)
-
-    def trajectory_store(self, segments, n_slots, slot_counters):
-        """aie_trajectory_store: every segment's block of replica e goes to ring slot slot_counters[e] of its destination,
-        then the counter advances modulo n_slots -- one launch on the current stream, capturable (the slot index lives on
-        the device).  segments: what trajectory_segment returns (or bare _cabi.AieTrajSegment), at most
-        _cabi.TRAJ_MAX_SEGMENTS; slot_counters: int32 [E] device tensor, zeroed by the caller."""
-        torch = _torch()
-        segs = [s[0] if isinstance(s, tuple) else s for s in segments]
-        if (slot_counters.dtype != torch.int32 or slot_counters.numel() != self.E or not slot_counters.is_contiguous()
-                or slot_counters.device != self.device):
-            raise ValueError("slot_counters: a contiguous int32 device tensor of %d elements" % self.E)
-        arr = (_cabi.AieTrajSegment * max(1, len(segs)))(*segs)
-        self._check(self.lib.aie_trajectory_store(self.handle, arr, len(segs), int(n_slots),
-                                                  C.c_void_p(slot_counters.data_ptr()), self._stream()))
-
-    def gae(self, T, log, values_a, values_p, gamma, lam, first_slot=0, advantages=True, returns=True, out=None):
-        """aie_gae: (adv_a, adv_p, ret_a, ret_p) of T steps from a reward log (float32 [n_slots, E, n + 2], time t in slot
-        (first_slot + t) % n_slots) and the values (float32 [T + 1, E, n] / [T + 1, E], row T the bootstrap; either may be
-        None).  One launch on the current stream.  out=(adv_a, adv_p, ret_a, ret_p) to fill the caller's own."""
-        torch = _torch()
-        T = int(T)
-        f = dict(dtype=torch.float32, device=self.device)
-        if log.dtype != torch.float32 or not log.is_contiguous() or log.device != self.device or log.dim() != 3 \
-                or tuple(log.shape[1:]) != (self.E, self.n + 2):
-            raise ValueError("gae: the log is a contiguous float32 device tensor [n_slots, %d, %d]" % (self.E, self.n + 2))
-        for v, per, what in ((values_a, self.E * self.n, "values_a"), (values_p, self.E, "values_p")):
-            if v is not None and (v.dtype != torch.float32 or not v.is_contiguous() or v.device != self.device
-                                  or v.numel() != (T + 1) * per):
-                raise ValueError("gae: %s is a contiguous float32 device tensor of (T + 1) x %d elements" % (what, per))
-        if out is None:
-            sa, sp = (T, self.E, self.n), (T, self.E)
-            out = [torch.empty(sa, **f) if values_a is not None and advantages else None,
-                   torch.empty(sp, **f) if values_p is not None and advantages else None,
-                   torch.empty(sa, **f) if values_a is not None and returns else None,
-                   torch.empty(sp, **f) if values_p is not None and returns else None]
-        else:
-            for o, per, what in zip(out, (self.E * self.n, self.E) * 2, ("adv_a", "adv_p", "ret_a", "ret_p")):
-                if o is not None and (o.dtype != torch.float32 or not o.is_contiguous() or o.device != self.device
-                                      or o.numel() != T * per):
-                    raise ValueError("gae: %s is a contiguous float32 device tensor of T x %d elements" % (what, per))
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        self._check(self.lib.aie_gae(self.handle, T, ptr(log), int(log.shape[0]), int(first_slot), ptr(values_a), ptr(values_p),
-                                     C.c_float(gamma), C.c_float(lam), ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]),
-                                     self._stream()))
-        return tuple(out)
-
-    def ppo_loss(self, logits_a, logits_p, values_a, values_p, batch, index=None, clip=0.3, vf_clip=50.0, vf_coef=0.05,
-                 ent_coef=0.025, coeffs_p=None, adv_moments=None, out=None):
-        """aie_ppo_loss: the PPO loss of both actor classes with its gradients, two launches on the current stream.
-        logits_a [B, n, MA] / logits_p [B, MP] and values_a [B, n] / values_p [B] are the networks' outputs for B batch
-        elements (either class None: left out; values None: no value term).  `batch` holds the STORED operands as
-        contiguous device tensors of R rows -- masks_a / masks_p (float32, the logits' layout), actions_* (int32),
-        logp_old_*, adv_*, values_old_*, returns_* (float32; Trajectory.ppo_batch() makes the dict) -- read at row index[b]
-        (index: int32 [B] on the device) or, with index None, at row b (R == B): a minibatch is an index, nothing is
-        copied and nothing is converted (a tensor of another dtype, device or layout is an error).
-        clip, vf_clip, vf_coef, ent_coef: the agents' coefficients, and the planner's unless coeffs_p (a dict of any of
-        them) says otherwise.  adv_moments: None or (moments_a, moments_p), each None or a float32 device tensor
-        {mean, rstd}: the advantage enters as (adv - mean) * rstd.
-        Returns ((stats_a, grad_logits_a, grad_values_a), (stats_p, grad_logits_p, grad_values_p)); a class that is left
-        out is None, grad_values is None without values.  stats: float32 [_cabi.PPO_N_STATS] (include/aie.h); the
-        gradients are those of stats[0].  Only the two gradients, the statistics and (once per backend, 1 MiB: calls of
-        one backend share it and must not run at the same time on two streams) the workspace are allocated -- out=((stats_a, grad_logits_a, grad_values_a), (stats_p, ...)) to fill the caller's own instead."""
-        torch = _torch()
-        per_a = self.tensors["obs_a_action_mask"].numel() // self.E
-        per_p = self.tensors["obs_p_action_mask"].numel() // self.E
-        aa, ap = self._action_buffers(0)
-        act_a, act_p = aa.numel() // self.E, ap.numel() // self.E
-        f = dict(dtype=torch.float32, device=self.device)
-
-        def net(t, per, what):  # a network output: made contiguous float32 here if it is not
-            if t is None:
-                return None
-            t = t.detach().to(**f).contiguous()
-            if t.numel() == 0 or t.numel() % per:
-                raise ValueError("ppo_loss: %s has %d elements, not a multiple of the %d per batch element" % (what, t.numel(), per))
-            return t
-
-        def stored(name, dtype, per):  # a stored operand: used where it lies
-            t = batch.get(name)
-            if t is None:
-                raise ValueError("ppo_loss: the batch has no %r" % name)
-            if (not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != self.device or not t.is_contiguous()
-                    or t.numel() == 0 or t.numel() % per):
-                raise ValueError("ppo_loss: %s must be a contiguous %s device tensor of R x %d elements" % (name, dtype, per))
-            return t
-
-        la, lp = net(logits_a, per_a, "logits_a"), net(logits_p, per_p, "logits_p")
-        if la is None and lp is None:
-            raise ValueError("ppo_loss: no actor class")
-        va = net(values_a, self.n, "values_a") if la is not None else None
-        vp = net(values_p, 1, "values_p") if lp is not None else None
-        Bs = {t.numel() // per for t, per in ((la, per_a), (lp, per_p), (va, self.n), (vp, 1)) if t is not None}
-        if len(Bs) != 1:
-            raise ValueError("ppo_loss: logits and values disagree on the batch size (%s)" % sorted(Bs))
-        B = Bs.pop()
-        if index is not None and (index.dtype != torch.int32 or index.device != self.device or not index.is_contiguous()
-                                  or index.numel() != B):
-            raise ValueError("ppo_loss: index must be a contiguous int32 device tensor of B = %d elements" % B)
-        mom = adv_moments if adv_moments is not None else (None, None)
-        coef_a = dict(clip=clip, vf_clip=vf_clip, vf_coef=vf_coef, ent_coef=ent_coef)
-        coef_p = dict(coef_a, **(coeffs_p or {}))
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        classes, outs, keep, Rs = [], [], [], set()
-        for who, lg, val, per, act, actors, co, mo in (("a", la, va, per_a, act_a, self.n, coef_a, mom[0]),
-                                                       ("p", lp, vp, per_p, act_p, 1, coef_p, mom[1])):
-            if lg is None:
-                classes.append(None)
-                outs.append(None)
-                continue
-            ops = dict(masks=stored("masks_" + who, torch.float32, per), actions=stored("actions_" + who, torch.int32, act),
-                       logp_old=stored("logp_old_" + who, torch.float32, act), adv=stored("adv_" + who, torch.float32, actors))
-            pers = dict(masks=per, actions=act, logp_old=act, adv=actors, values_old=actors, returns=actors)
-            if val is not None:
-                ops["values_old"] = stored("values_old_" + who, torch.float32, actors)
-                ops["returns"] = stored("returns_" + who, torch.float32, actors)
-            Rs |= {t.numel() // pers[k] for k, t in ops.items()}
-            if mo is not None and (mo.dtype != torch.float32 or mo.device != self.device or not mo.is_contiguous() or mo.numel() != 2):
-                raise ValueError("ppo_loss: adv_moments are float32 device tensors {mean, rstd}")
-            if out is not None:
-                stats, grad, grad_v = out[who == "p"]
-                for t, like, what in ((stats, None, "stats"), (grad, lg, "grad_logits"), (grad_v, val, "grad_values")):
-                    numel = _cabi.PPO_N_STATS if like is None else like.numel()
-                    if (t is None) != (what == "grad_values" and val is None) or (
-                            t is not None and (t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous()
-                                               or t.numel() != numel)):
-                        raise ValueError("ppo_loss: out's %s_%s must be a contiguous float32 device tensor of %d elements (None "
-                                         "for grad_values without values)" % (what, who, numel))
-            else:
-                stats = torch.empty(_cabi.PPO_N_STATS, **f)
-                grad = torch.empty_like(lg)
-                grad_v = torch.empty_like(val) if val is not None else None
-            c = _cabi.AiePpoClass(logits=ptr(lg), values=ptr(val), masks=ptr(ops["masks"]), actions=ptr(ops["actions"]),
-                                  logp_old=ptr(ops["logp_old"]), adv=ptr(ops["adv"]), values_old=ptr(ops.get("values_old")),
-                                  returns=ptr(ops.get("returns")), adv_moments=ptr(mo), grad_logits=ptr(grad),
-                                  grad_values=ptr(grad_v), stats=ptr(stats), clip=co["clip"], vf_clip=co["vf_clip"],
-                                  vf_coef=co["vf_coef"], ent_coef=co["ent_coef"])
-            classes.append(c)
-            outs.append((stats, grad, grad_v))
-            keep.append(ops)
-        if len(Rs) != 1 or (index is None and Rs != {B}):
-            raise ValueError("ppo_loss: the stored operands have %s rows; all must agree, and without an index equal B = %d"
-                             % (sorted(Rs), B))
-        # the workspace: the largest any B needs (1 MiB), allocated once per backend and never replaced -- a captured call
-        # keeps its pointer.  Calls of one backend share it: they must not overlap (two streams: two backends' worth of
-        # workspace through the C ABI)
-        ws = getattr(self, "_ppo_ws", None)
-        if ws is None:
-            ws = self._ppo_ws = torch.empty(_cabi.PPO_MAX_WAVES * 16, dtype=torch.float64, device=self.device)
-        ref = lambda c: C.byref(c) if c is not None else None  # noqa: E731
-        self._check(self.lib.aie_ppo_loss(self.handle, C.c_int64(B), ref(classes[0]), ref(classes[1]),
-                                          C.c_void_p(index.data_ptr()) if index is not None else None,
-                                          C.c_void_p(ws.data_ptr()), C.c_int64(ws.numel() * 8), self._stream()))
-        return outs[0], outs[1]
-
-    def _mlp_operands(self, fn, who, x, w, per):
-        """The checks policy_mlp_forward and policy_mlp_backward share for one class -> (x as [rows, F], x_ld, the dict of its
-        weight tensors w1 .. bv, F, H, M)."""
-        torch = _torch()
-        get = w.get if hasattr(w, "get") else lambda k, w=w: getattr(w, k, None)  # noqa: E731
-        if x.dim() == 3:  # [B, n, F] with one row stride throughout: a view, never a copy
-            if x.shape[0] > 1 and x.stride(0) != x.shape[1] * x.stride(1):
-                raise ValueError("%s: x_%s [B, n, F] needs one row stride throughout (strides %s)" % (fn, who, tuple(x.stride())))
-            x = x.as_strided((x.shape[0] * x.shape[1], x.shape[2]), (x.stride(1), x.stride(2)), x.storage_offset())
-        if x.dim() != 2 or x.dtype != torch.float32 or x.device != self.device or (x.shape[1] > 1 and x.stride(1) != 1) \
-                or x.shape[0] == 0 or x.shape[0] % per:
-            raise ValueError("%s: x_%s is a float32 device tensor [B x %d, F] with contiguous rows" % (fn, who, per))
-        rows, F = int(x.shape[0]), int(x.shape[1])
-        x_ld = int(x.stride(0)) if rows > 1 else F
-        t = {k: get(k) for k in ("w1", "b1", "w2", "b2", "w3", "b3", "wv", "bv")}
-        H = int(t["w1"].shape[-1]) if t["w1"] is not None and t["w1"].dim() == 2 else 0
-        M = int(t["w3"].shape[-1]) if t["w3"] is not None and t["w3"].dim() == 2 else 0
-        for k, shape in (("w1", (F, H)), ("b1", (H,)), ("w2", (H, H)), ("b2", (H,)), ("w3", (H, M)), ("b3", (M,)),
-                         ("wv", (H,)), ("bv", (1,))):
-            v = t[k]
-            if v is None and k in ("wv", "bv"):
-                continue
-            if (v is None or v.dtype != torch.float32 or v.device != self.device or not v.is_contiguous()
-                    or v.numel() != int(np.prod(shape)) or (v.dim() == 2 and k != "wv" and tuple(v.shape) != shape)):
-                raise ValueError("%s: weights_%s[%r] must be a contiguous float32 device tensor of shape %s" % (fn, who, k, shape))
-        if (t["wv"] is None) != (t["bv"] is None):
-            raise ValueError("%s: weights_%s needs wv and bv together" % (fn, who))
-        return x, x_ld, t, F, H, M
-
-    def policy_mlp_forward(self, x_a, x_p, weights_a, weights_p, out=None):
-        """aie_policy_mlp_forward: both classes' policy network -- x -> relu -> H -> relu -> H -> logits (+ value) -- in ONE
-        launch on the current stream.  x_a [B * n, F_a] (or [B, n, F_a]) and x_p [B, F_p]: float32 device tensors whose rows
-        are contiguous (any row stride: an arena tensor, a sliced view); a class whose x is None is left out.  weights_*:
-        a mapping (or rollout.mlp_weights) with float32 device tensors w1 [F, H], b1 [H], w2 [H, H], b2 [H], w3 [H, M],
-        b3 [M], contiguous, and optionally wv [H] (or [H, 1]) with bv [1]: the value column.  The library reads them where
-        they lie at every launch: update them in place and the next launch, or graph replay, sees the new values.
-        Returns (logits_a [rows, M_a], logits_p [B, M_p], value_a [rows], value_p [B]) -- None for a class left out and for a
-        value without wv; out=(logits_a, logits_p, value_a, value_p) fills the caller's contiguous float32 tensors instead
-        (nothing is allocated).  The arithmetic contract (one ascending fmaf chain per output) is include/aie.h's."""
-        torch = _torch()
-        f = dict(dtype=torch.float32, device=self.device)
-        out = tuple(out) if out is not None else (None,) * 4
-        classes, res, Bs = [], [], set()
-        for who, x, w, per, o_l, o_v in (("a", x_a, weights_a, self.n, out[0], out[2]), ("p", x_p, weights_p, 1, out[1], out[3])):
-            if x is None:
-                classes.append(None)
-                res.append((None, None))
-                continue
-            x, x_ld, t, F, H, M = self._mlp_operands("policy_mlp_forward", who, x, w, per)
-            rows = int(x.shape[0])
-            has_v = t["wv"] is not None
-            for o, numel, what in ((o_l, rows * M, "logits"), (o_v, rows, "value")):
-                if o is not None and (o.dtype != torch.float32 or o.device != self.device or not o.is_contiguous() or o.numel() != numel):
-                    raise ValueError("policy_mlp_forward: out's %s_%s must be a contiguous float32 device tensor of %d elements"
-                                     % (what, who, numel))
-            logits = o_l if o_l is not None else torch.empty((rows, M), **f)
-            value = (o_v if o_v is not None else torch.empty((rows,), **f)) if has_v else None
-            ptr = lambda v: v.data_ptr() if v is not None else None  # noqa: E731
-            classes.append(_cabi.AieMlpClass(x=x.data_ptr(), x_ld=x_ld, w1=ptr(t["w1"]), b1=ptr(t["b1"]), w2=ptr(t["w2"]),
-                                             b2=ptr(t["b2"]), w3=ptr(t["w3"]), b3=ptr(t["b3"]), wv=ptr(t["wv"]), bv=ptr(t["bv"]),
-                                             logits=logits.data_ptr(), values=ptr(value), F=F, H=H, M=M))
-            res.append((logits, value))
-            Bs.add(rows // per)
-        if not Bs:
-            raise ValueError("policy_mlp_forward: no actor class")
-        if len(Bs) != 1:
-            raise ValueError("policy_mlp_forward: the classes disagree on the batch size (%s)" % sorted(Bs))
-        ref = lambda c: C.byref(c) if c is not None else None  # noqa: E731
-        self._check(self.lib.aie_policy_mlp_forward(self.handle, C.c_int64(Bs.pop()), ref(classes[0]), ref(classes[1]),
-                                                    self._stream()))
-        return res[0][0], res[1][0], res[0][1], res[1][1]
-
-    def policy_mlp_backward(self, x_a, x_p, weights_a, weights_p, g_logits_a, g_logits_p, g_values_a=None, g_values_p=None,
-                            out=None):
-        """aie_policy_mlp_backward: the gradients of both classes' weights from the gradients with respect to logits and
-        values (ppo_loss's grad_logits and grad_values), THREE launches on the current stream.  x_* and weights_* as for
-        policy_mlp_forward (the same validation); g_logits_* [rows, M] and g_values_* [rows]: contiguous float32 device
-        tensors, g_values exactly for a class with wv.  Returns (grads_a, grads_p): a dict w1, b1, w2, b2, w3, b3 (and wv,
-        bv) of new float32 tensors in the weights' shapes per class, None for a class left out; out=(dict_a, dict_p) fills
-        the caller's contiguous float32 tensors instead.  Every entry is overwritten.  The arithmetic contract (segments of
-        _cabi.MLP_BWD_SEG rows, float64 sums of the segments, no atomics: two runs give the same bits) is include/aie.h's.
-        The workspace grows with the row count; it is cached per backend and replaced when a call needs more (calls of one
-        backend share it and must not run at the same time on two streams; a captured call keeps the pointer, so capture
-        the largest batch first or keep batch sizes fixed)."""
-        torch = _torch()
-        f = dict(dtype=torch.float32, device=self.device)
-        out = tuple(out) if out is not None else (None, None)
-        classes, res, Bs = [], [], set()
-        for who, x, w, per, gl, gv, o in (("a", x_a, weights_a, self.n, g_logits_a, g_values_a, out[0]),
-                                          ("p", x_p, weights_p, 1, g_logits_p, g_values_p, out[1])):
-            if x is None:
-                classes.append(None)
-                res.append(None)
-                continue
-            x, x_ld, t, F, H, M = self._mlp_operands("policy_mlp_backward", who, x, w, per)
-            rows = int(x.shape[0])
-            shapes = dict(w1=(F, H), b1=(H,), w2=(H, H), b2=(H,), w3=(H, M), b3=(M,), wv=(H,), bv=(1,))
-            has_v = t["wv"] is not None
-            if (gv is not None) != has_v:
-                raise ValueError("policy_mlp_backward: g_values_%s goes with wv: both or neither" % who)
-            for g, numel, what in ((gl, rows * M, "g_logits"), (gv, rows, "g_values")):
-                if (g is None and what == "g_logits") or (g is not None and (
-                        g.dtype != torch.float32 or g.device != self.device or not g.is_contiguous() or g.numel() != numel)):
-                    raise ValueError("policy_mlp_backward: %s_%s must be a contiguous float32 device tensor of %d elements"
-                                     % (what, who, numel))
-            names = [k for k in shapes if t[k] is not None]
-            if o is not None:
-                for k in names:
-                    v = o.get(k)
-                    if (v is None or v.dtype != torch.float32 or v.device != self.device or not v.is_contiguous()
-                            or v.numel() != t[k].numel()):
-                        raise ValueError("policy_mlp_backward: out's %s_%s must be a contiguous float32 device tensor of %d elements"
-                                         % (k, who, t[k].numel()))
-                grads = {k: o[k] for k in names}
-            else:
-                grads = {k: torch.empty_like(t[k]) for k in names}
-            ptr = lambda v: v.data_ptr() if v is not None else None  # noqa: E731
-            net = _cabi.AieMlpClass(x=x.data_ptr(), x_ld=x_ld, w1=ptr(t["w1"]), b1=ptr(t["b1"]), w2=ptr(t["w2"]), b2=ptr(t["b2"]),
-                                    w3=ptr(t["w3"]), b3=ptr(t["b3"]), wv=ptr(t["wv"]), bv=ptr(t["bv"]), logits=None, values=None,
-                                    F=F, H=H, M=M)
-            classes.append(_cabi.AieMlpGradClass(net=net, g_logits=ptr(gl), g_values=ptr(gv),
-                                                 **{"g" + k: ptr(grads.get(k)) for k in shapes}))
-            res.append(grads)
-            Bs.add(rows // per)
-        if not Bs:
-            raise ValueError("policy_mlp_backward: no actor class")
-        if len(Bs) != 1:
-            raise ValueError("policy_mlp_backward: the classes disagree on the batch size (%s)" % sorted(Bs))
-        B = C.c_int64(Bs.pop())
-        ref = lambda c: C.byref(c) if c is not None else None  # noqa: E731
-        need = int(self.lib.aie_policy_mlp_backward_workspace_bytes(self.handle, B, ref(classes[0]), ref(classes[1])))
-        ws = getattr(self, "_mlp_bwd_ws", None)
-        if need > 0 and (ws is None or ws.numel() * 4 < need):
-            ws = self._mlp_bwd_ws = torch.empty((need + 3) // 4, **f)
-        # (a refusal of the plan makes `need` its negative code: the call below then refuses too, and names itself)
-        self._check(self.lib.aie_policy_mlp_backward(self.handle, B, ref(classes[0]), ref(classes[1]),
-                                                     C.c_void_p(ws.data_ptr()) if ws is not None else None,
-                                                     C.c_int64(ws.numel() * 4 if ws is not None else 0), self._stream()))
-        return res[0], res[1]
 
     def _action_buffers(self, slot):
         torch = _torch()
