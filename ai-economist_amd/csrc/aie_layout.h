@@ -1084,7 +1084,10 @@ static inline int aie_build_params(const aie_config* c, aie_params* p, aie_tenso
   p->has_tax = aie__has(c, AIE_COMP_TAX);
   p->has_labor = aie__has(c, AIE_COMP_SIMPLE_LABOR);
   if (p->has_labor) {
-    if (c->labor_num_hours < 1 || c->labor_num_hours > 1000) AIE__FAIL("SimpleLabor.num_labor_hours out of range");
+    /* an agent's mask row is [NO-OP, hours...]: the one-step-economy kernels store a row with one 16-byte quad per lane
+     * of a wavefront (ose_store_rows), which holds 256 floats */
+    if (c->labor_num_hours < 1 || c->labor_num_hours > 255)
+      AIE__FAIL("SimpleLabor.num_labor_hours out of range (%d: 1 .. 255, an agent's mask row is at most 256 entries)", c->labor_num_hours);
     if (!(c->labor_pmsm > 0.0)) AIE__FAIL("SimpleLabor.payment_max_skill_multiplier must be > 0");
   }
   if (!gtb) {

@@ -260,7 +260,7 @@ typedef struct aie_config {
 
   /* SimpleLabor (F/components/simple_labor.py:41-74) */
   int32_t labor_mask_first_step;
-  int32_t labor_num_hours;           /* 100                                             */
+  int32_t labor_num_hours;           /* 100; 1 .. 255 (an agent's mask row, [NO-OP, hours...], is at most 256 entries) */
   double labor_pmsm;                 /* payment_max_skill_multiplier                    */
   double labor_skills[AIE_MAX_AGENTS_WIDE]; /* per-agent skill (sorted Pareto means, :66-74) */
 
