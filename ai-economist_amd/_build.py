@@ -12,9 +12,6 @@ CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(CSRC, "libaie_hip.so")
 LIB_DEV = os.path.join(CSRC, "libaie_hip_dev.so")
-SOURCES = ["aie_capi.hip", "aie_kernels.hip", "aie_kernels_ose.hip", "aie_kernels_saez.hip", "aie_kernels_ppo.hip", "aie_kernels_mlp.hip",
-           "aie_kernels_mlp_bwd.hip", "aie_kernels_covid.hip", "aie_layout.h", "aie_glibc_math.h", "aie_glibc_tables.h", "aie_spec_generated.h",
-           "aie_jit.h", "aie_trainer_plan.h"]
 
 
 def hipcc_path():
@@ -32,12 +29,19 @@ def have_hipcc():
         return False
 
 
+def source_files():
+    """What the library counts as built from: every *.hip and *.h under csrc/ plus include/aie.h.  No hand-kept list:
+    a file too many costs a rebuild, a file too few a stale library (tests/test_kernel_sources.py checks the latter)."""
+    names = sorted(n for n in os.listdir(CSRC) if n.endswith((".hip", ".h")))
+    return [os.path.join(CSRC, n) for n in names] + [os.path.join(ROOT, "include", "aie.h")]
+
+
 def _source_hash():
     import hashlib
 
     h = hashlib.sha256()
-    h.update(b"recipe 3: -fvisibility=hidden + version script\n")
-    for d in [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(ROOT, "include", "aie.h")]:
+    h.update(b"recipe 4: -fvisibility=hidden + version script; sources = csrc/*.hip, csrc/*.h, include/aie.h\n")
+    for d in source_files():
         with open(d, "rb") as f:
             h.update(f.read())
     return h.hexdigest()

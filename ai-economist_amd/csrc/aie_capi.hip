@@ -7,13 +7,16 @@
 #include <cstring>
 #include <vector>
 
+// every kernel file includes what it needs; the order here is only the order the kernels are emitted in
 #include "aie_kernels.hip"
+#include "aie_kernels_sampler.hip"
+#include "aie_kernels_rollout.hip"
 #include "aie_kernels_ose.hip"
 #include "aie_kernels_saez.hip"
 #include "aie_kernels_ppo.hip"
 #include "aie_kernels_mlp.hip"
 #include "aie_kernels_mlp_bwd.hip"
-#include "aie_kernels_covid.hip"  // last: switches FP contraction off for the rest of the TU
+#include "aie_kernels_covid.hip"
 #include "aie_jit.h"
 #include "aie_trainer_plan.h"  // host only: the trainer calls' plans
 

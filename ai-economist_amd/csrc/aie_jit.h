@@ -91,6 +91,9 @@ static inline bool private_dir(const std::string& p) {
 }
 static const char* const kRecipe = "recipe 2: -O3 -std=c++17 -Wno-comment";  // compile options: part of the cache key
 
+// The files of this directory a specialisation is compiled from (with include/aie.h): part of the cache key.  Kept by
+// hand so that the key does not grow to the trainer-side kernel files; tests/test_kernel_sources.py preprocesses both
+// source strings below and fails when this list and what they include differ.
 static const char* const kSources[] = {"aie_kernels.hip", "aie_kernels_ose.hip", "aie_layout.h", "aie_glibc_math.h",
                                        "aie_glibc_tables.h"};
 

@@ -19,6 +19,9 @@
 // materialises delta[l]*w[s,f]*filt[f,l] and np.sum()s 3000 terms; here each lane streams its
 // own 600-day window of stringency levels once and keeps F float64 accumulators (FMA),
 // weighting them by w[s,f] at the end -- a float64 reordering, ~1e-16 relative.
+#pragma once
+#include "aie_kernels.hip"
+
 #pragma clang fp contract(off)
 
 // ablations (tools/covid_ablate.py, -DAIE_DEV build): the AIE_CV_SKIP_* bits of aie_dev_set_skip_mask (aie_layout.h)

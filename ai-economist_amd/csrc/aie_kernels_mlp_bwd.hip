@@ -20,6 +20,8 @@
 //    Row K of the block is the bias: a constant 1.  Column M of the head's block is the value head: dz = g_values.
 // C. aie_policy_mlp_bwd_reduce_kernel: one thread per gradient entry adds its segment partials in float64, ascending.
 // No atomics, no allocation, no scratch; rows, columns and k outside the arrays read clamped addresses and contribute zeros.
+#pragma once
+#include "aie_kernels_mlp.hip"  // the forward's machinery: MlpCol, mlp_tiles, aie_mlp_f4
 
 // A hidden layer of the forward (fwd: acc from the bias, relu) or a transposed product of the backward (acc from 0, the
 // value term, the ReLU mask) on the tile.  Source: `act` [TM][S] in LDS, staged here from xg (global rows of K floats) or

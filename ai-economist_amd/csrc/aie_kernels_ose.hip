@@ -8,6 +8,7 @@
 //
 // Reference: F/scenarios/one_step_economy/one_step_economy.py,
 // F/components/simple_labor.py, F/components/redistribution.py.
+#pragma once
 #include "aie_kernels.hip"
 
 // Threads per replica (a multiple of the wavefront size; every wave keeps its own copy of the generator rows

@@ -18,6 +18,9 @@
 // them) added in that order, by plain vector stores of lane 0.  No atomics: the order of every sum is fixed by B.
 // Launch 2, aie_ppo_reduce_kernel: one workgroup adds the records (thread (q, j): records q, q + 64, ... of sum j, sixteen
 // loads in flight, then q = 0 .. 63 in order) and writes both classes' statistics (aie_ppo_finish_stats).
+#pragma once
+#include "aie_kernels_rollout.hip"  // the evaluator's row values: sampler_segment_max, sampler_scan, policy_segment_total
+
 #pragma clang fp contract(off)
 
 struct PpoTerms {  // what one work item adds to its class's sums, per lane (0 in a lane that leads no actor)

@@ -4,7 +4,7 @@
  * flat-observation bookkeeping that the reference derives at construction time.
  *
  * Plain C99 (also included from HIP C++).  Included by the HIP library
- * (aie_capi.hip / aie_kernels.hip) and by the CPU restatement oracle/aie_oracle.c so
+ * (aie_capi.hip / aie_kernels*.hip) and by the CPU restatement oracle/aie_oracle.c so
  * that both step byte-identical records.
  *
  * Reference logic restated here:

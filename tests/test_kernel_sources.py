@@ -1,0 +1,80 @@
+"""CPU tests: what the kernel sources are made of.  Every csrc/aie_kernels*.hip is a unit that compiles on its own (it
+includes what it uses: no file relies on its place in aie_capi.hip's include block), the cache key of a run-time
+specialisation (aie_jit.h: kSources) names exactly the project files its two units are compiled from, and the library's
+staleness hash (_build.source_files) reads every project file aie_capi.hip is compiled from.  The compiler's own
+preprocessor says what a unit includes (the `# n "file"` line markers); nothing is launched."""
+import ast
+import glob
+import os
+import re
+import subprocess
+
+import pytest
+
+from helpers import ROOT
+
+CSRC = os.path.join(ROOT, "ai-economist_amd", "csrc")
+INCLUDE = os.path.join(ROOT, "include")
+KERNEL_FILES = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "aie_kernels*.hip")))
+# aie_jit_image.h as aie_jit.h writes it per configuration; the preprocessor does not care for the image's size
+STUB_IMAGE = ("#pragma once\n#define AIE_N_SPECS 1\ntemplate <int K> struct aie_spec_image;\n"
+              "alignas(16) static constexpr unsigned char aie_jit_bytes[1] = {0};\n"
+              "template <> struct aie_spec_image<0> { static constexpr const unsigned char* bytes = aie_jit_bytes; "
+              "static constexpr int waves = 8; };\n")
+
+
+def _hipcc():
+    from ai_economist_amd import _build
+
+    if not _build.have_hipcc():
+        pytest.skip("hipcc not found: the kernel sources cannot be compiled")
+    return [_build.hipcc_path(), "--offload-arch=gfx950", "--cuda-device-only", "-std=c++17", "-Wno-comment",
+            "-Wno-pragma-once-outside-header", "-I" + CSRC, "-I" + INCLUDE]
+
+
+def _project_files(unit, extra=()):
+    """The files under the repository that the device side of `unit` is compiled from, the unit itself included."""
+    text = subprocess.run(_hipcc() + ["-E"] + list(extra) + [unit, "-o", "-"], check=True, capture_output=True, text=True).stdout
+    files = {os.path.realpath(f) for f in re.findall(r'(?m)^# \d+ "([^"<][^"]*)"', text)}
+    return {f for f in files if f.startswith(os.path.realpath(ROOT) + os.sep)}
+
+
+@pytest.mark.parametrize("name", KERNEL_FILES)
+def test_each_kernel_file_compiles_on_its_own(name):
+    r = subprocess.run(_hipcc() + ["-fsyntax-only", os.path.join(CSRC, name)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+
+
+def _jit_units():
+    """(kSources, the two source strings) as csrc/aie_jit.h states them."""
+    with open(os.path.join(CSRC, "aie_jit.h")) as f:
+        text = f.read()
+    listed = re.search(r"kSources\[\]\s*=\s*\{(.*?)\};", text, re.S).group(1)
+    units = re.search(r'std::string src = ose \? ("(?:[^"\\]|\\.)*")\s*:\s*("(?:[^"\\]|\\.)*");', text)
+    return re.findall(r'"([^"]+)"', listed), [ast.literal_eval(units.group(k)) for k in (1, 2)]
+
+
+def test_specialisation_cache_key_covers_what_it_compiles(tmp_path):
+    listed, units = _jit_units()
+    assert len(units) == 2 and all("#define AIE_JIT 1" in u for u in units), units
+    (tmp_path / "aie_jit_image.h").write_text(STUB_IMAGE)
+    compiled = set()
+    for k, unit in enumerate(units):
+        src = tmp_path / ("aie_jit_%d.hip" % k)
+        src.write_text(unit)
+        compiled |= _project_files(str(src), ["-I" + str(tmp_path)])
+    compiled = {f for f in compiled if not f.startswith(os.path.realpath(str(tmp_path)) + os.sep)}
+    keyed = {os.path.realpath(os.path.join(CSRC, s)) for s in listed} | {os.path.realpath(os.path.join(INCLUDE, "aie.h"))}
+    assert len(listed) == len(set(listed))
+    assert compiled == keyed, (sorted(compiled - keyed), sorted(keyed - compiled))
+    # the step / reset kernel files only: an edit to a trainer-side kernel file leaves every cached code object valid
+    assert sorted(s for s in listed if s.endswith(".hip")) == ["aie_kernels.hip", "aie_kernels_ose.hip"], listed
+
+
+def test_library_staleness_hash_reads_what_the_library_is_compiled_from():
+    from ai_economist_amd import _build
+
+    compiled = _project_files(os.path.join(CSRC, "aie_capi.hip"))
+    hashed = {os.path.realpath(f) for f in _build.source_files()}
+    assert KERNEL_FILES and {os.path.realpath(os.path.join(CSRC, n)) for n in KERNEL_FILES} <= compiled  # (no dead kernel file)
+    assert compiled <= hashed, sorted(compiled - hashed)

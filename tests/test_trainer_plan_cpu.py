@@ -324,8 +324,9 @@ def test_mlp_backward_workspace_and_launches(S, B):
 
 def test_mlp_refusals(S):
     P = S.params["c2"]
-    fwd = lambda B, a, q: ("shim_mlp_forward", MlpFwdPlan, P, B, a and C.addressof(a), q and C.addressof(q))  # noqa: E731
-    bwd = lambda B, a, q, ws=WS: ("shim_mlp_backward", MlpBwdPlan, P, B, a and C.addressof(a), q and C.addressof(q), ws)  # noqa: E731
+    # (byref, not addressof: the tuple then keeps a class built in the call's argument list alive until the plan has read it)
+    fwd = lambda B, a, q: ("shim_mlp_forward", MlpFwdPlan, P, B, a and C.byref(a), q and C.byref(q))  # noqa: E731
+    bwd = lambda B, a, q, ws=WS: ("shim_mlp_backward", MlpBwdPlan, P, B, a and C.byref(a), q and C.byref(q), ws)  # noqa: E731
     F, B = "aie_policy_mlp_forward: ", "aie_policy_mlp_backward: "
     good, gg = mlp_class(S, 20, 32, 5), grad_class(S, 20, 32, 5)
     # both classes NULL: nothing to launch, after the check of B
@@ -444,7 +445,7 @@ def test_ppo_waves_workspace_and_paths(S, cfg):
 
 def test_ppo_refusals(S):
     P = S.params["c2"]
-    call = lambda B, a, q, P=P: ("shim_ppo", PpoPlan, P, DP, ARENA, B, a and C.addressof(a), q and C.addressof(q), None, WS)  # noqa: E731
+    call = lambda B, a, q, P=P: ("shim_ppo", PpoPlan, P, DP, ARENA, B, a and C.byref(a), q and C.byref(q), None, WS)  # noqa: E731
     N = "aie_ppo_loss: "
     for c in (0, 1):
         for kw in (dict(logits=None), dict(masks=None), dict(actions=None), dict(logp_old=None), dict(adv=None), dict(grad_logits=None),

@@ -1,5 +1,5 @@
-"""Static instruction statistics per kernel: compiles the device side of csrc/aie_capi.hip to assembly
-(hipcc --cuda-device-only -S) and counts instructions by class.   python tools/kernel_asm_stats.py [min_instructions]"""
+"""Static instruction statistics per kernel: compiles the device side of csrc/aie_capi.hip (the library's one translation
+unit: it includes every csrc/aie_kernels*.hip) to assembly (hipcc --cuda-device-only -S) and counts instructions by class.   python tools/kernel_asm_stats.py [min_instructions]"""
 import os
 import re
 import subprocess

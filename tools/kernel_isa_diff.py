@@ -2,9 +2,11 @@
 csrc/aie_capi.hip (hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude --cuda-device-only -S ... -o X.s; the file
 tools/kernel_asm_stats.py leaves in the temporary directory is one) after dropping comments, directives and label numbers.
 Kernels are paired by their demangled names up to the template arguments the newer build added at the end
-(`foo<6, 5>` ~ `foo<6, 5, false>`, `foo` ~ `foo<false>`).
+(`foo<6, 5>` ~ `foo<6, 5, false>`, `foo` ~ `foo<false>`).  The translation unit's id (`__hip_cuid_*`, a hash of the
+compile's input) is no function and is left out.
 
-   python tools/kernel_isa_diff.py before.s after.s [substring of the kernels' names, default sample_policy]"""
+   python tools/kernel_isa_diff.py before.s after.s [substring of the kernels' names, default sample_policy;
+                                                     "" compares every kernel and device function]"""
 import difflib
 import re
 import subprocess
@@ -16,7 +18,7 @@ def bodies(path, want):
     for line in open(path):
         m = re.match(r"^([A-Za-z_]\w*):", line)
         if m and not line.startswith(".L"):
-            cur = m.group(1) if want in m.group(1) else None
+            cur = m.group(1) if want in m.group(1) and not m.group(1).startswith("__hip_cuid_") else None
             if cur:
                 out[cur] = []
             continue

@@ -1,4 +1,4 @@
-"""Compiles csrc/aie_capi.hip with -Rpass-analysis=kernel-resource-usage and prints one line per kernel:
+"""Compiles csrc/aie_capi.hip (the library's one translation unit: it includes every csrc/aie_kernels*.hip) with -Rpass-analysis=kernel-resource-usage and prints one line per kernel:
 VGPRs, AGPRs, SGPRs, scratch bytes per lane, occupancy (waves per SIMD), LDS.   python tools/kernel_resources.py"""
 import os
 import re
