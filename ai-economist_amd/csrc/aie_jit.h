@@ -91,11 +91,14 @@ static inline bool private_dir(const std::string& p) {
 }
 static const char* const kRecipe = "recipe 2: -O3 -std=c++17 -Wno-comment";  // compile options: part of the cache key
 
-// The files of this directory a specialisation is compiled from (with include/aie.h): part of the cache key.  Kept by
-// hand so that the key does not grow to the trainer-side kernel files; tests/test_kernel_sources.py preprocesses both
-// source strings below and fails when this list and what they include differ.
-static const char* const kSources[] = {"aie_kernels.hip", "aie_kernels_ose.hip", "aie_layout.h", "aie_glibc_math.h",
-                                       "aie_glibc_tables.h"};
+// The files of this directory a specialisation is compiled from (with include/aie.h): part of the cache key, one key
+// per unit -- what both units include, then what each adds, so that an edit to one scenario family's files leaves the
+// other's cached code objects valid.  Kept by hand so that a key does not grow to files its unit never sees;
+// tests/test_kernel_sources.py preprocesses both source strings below and fails when a unit's lists and what it
+// includes differ.
+static const char* const kSources[] = {"aie_device.h", "aie_layout.h", "aie_glibc_math.h", "aie_glibc_tables.h"};
+static const char* const kSourcesOse[] = {"aie_kernels_ose.hip"};
+static const char* const kSourcesGtb[] = {"aie_kernels.hip"};
 
 // Compiles (or fetches from the cache) the code object for `image` (sizeof(aie_params) normalised bytes); `waves` =
 // waves per SIMD the kernel is compiled for.  On failure returns false with a message in `err`.
@@ -122,10 +125,15 @@ static inline bool code_object(const void* image, size_t image_bytes, int waves,
   h = fnv1a(h, &waves, sizeof(waves));
   h = fnv1a(h, &ose, sizeof(ose));
   h = fnv1a(h, arch, strlen(arch));
-  for (const char* s : kSources) {
-    if (!read_file(csrc + "/" + s, text)) { err = "kernel source " + csrc + "/" + s + " not found"; return false; }
-    h = fnv1a(h, text.data(), text.size());
-  }
+  auto hash_sources = [&](const char* const* names, size_t count) {
+    for (size_t k = 0; k < count; ++k) {
+      if (!read_file(csrc + "/" + names[k], text)) { err = "kernel source " + csrc + "/" + names[k] + " not found"; return false; }
+      h = fnv1a(h, text.data(), text.size());
+    }
+    return true;
+  };
+  if (!hash_sources(kSources, std::size(kSources))) return false;
+  if (!(ose ? hash_sources(kSourcesOse, std::size(kSourcesOse)) : hash_sources(kSourcesGtb, std::size(kSourcesGtb)))) return false;
   if (!read_file(inc + "/aie.h", text)) { err = "include/aie.h not found beside the kernel sources"; return false; }
   h = fnv1a(h, text.data(), text.size());
   std::string cache;

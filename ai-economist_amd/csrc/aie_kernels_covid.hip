@@ -20,7 +20,7 @@
 // own 600-day window of stringency levels once and keeps F float64 accumulators (FMA),
 // weighting them by w[s,f] at the end -- a float64 reordering, ~1e-16 relative.
 #pragma once
-#include "aie_kernels.hip"
+#include "aie_device.h"
 
 #pragma clang fp contract(off)
 

@@ -19,7 +19,7 @@
 // parts; the launch relies on gfx950's 160 KB per workgroup, the only target this library is built for.
 // No atomics, no allocation, no synchronisation with the host.
 #pragma once
-#include "aie_kernels.hip"
+#include "aie_device.h"
 
 typedef float aie_mlp_f4 __attribute__((ext_vector_type(4)));
 typedef const float __attribute__((address_space(1))) * aie_mlp_gptr;  // global memory, said so: a walked pointer otherwise loads as flat

@@ -14,7 +14,7 @@
 // determinant, u = 2^-53: a few u on spread-out marginal rates, ~1e-9 at sd 1e-3, ~1e-6 at sd 1e-5; everything else
 // stays at a few u.  tests/saez_exact.py derives the band every output has to lie in ("Saez").
 #pragma once
-#include "aie_kernels.hip"
+#include "aie_device.h"
 
 namespace aie {
 

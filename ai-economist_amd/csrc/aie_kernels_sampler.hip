@@ -3,7 +3,7 @@
 // helpers).  Never part of a run-time specialisation: aie_jit.h compiles aie_kernels.hip / aie_kernels_ose.hip only, so
 // an edit here leaves the cached step / reset code objects valid.
 #pragma once
-#include "aie_kernels.hip"
+#include "aie_device.h"
 
 // Synthetic uniform random policy of the benchmark: a counter RNG
 // keyed (seed, global replica id, t, agent); one thread per (replica, agent slot).

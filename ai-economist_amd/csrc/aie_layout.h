@@ -461,7 +461,7 @@ static inline int aie__has(const aie_config* c, int comp) {
 static inline int aie__shared_src_list(const aie_config* c) {
   return c->scenario == AIE_SCN_GTB && c->shared_layout && c->layout_gen == AIE_LAYOUT_FIXED;
 }
-/* ... which the kernels use with the counter stream only (aie_kernels.hip: shared_src_list); everybody else keeps a list
+/* ... which the kernels use with the counter stream only (aie_device.h: shared_src_list); everybody else keeps a list
  * per replica in the record (o_src_n / o_src_list) */
 static inline int aie__record_src_list(const aie_config* c) {
   return c->scenario == AIE_SCN_GTB && !(aie__shared_src_list(c) && c->rng_mode == AIE_RNG_FAST);

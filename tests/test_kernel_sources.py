@@ -1,8 +1,9 @@
-"""CPU tests: what the kernel sources are made of.  Every csrc/aie_kernels*.hip is a unit that compiles on its own (it
-includes what it uses: no file relies on its place in aie_capi.hip's include block), the cache key of a run-time
-specialisation (aie_jit.h: kSources) names exactly the project files its two units are compiled from, and the library's
-staleness hash (_build.source_files) reads every project file aie_capi.hip is compiled from.  The compiler's own
-preprocessor says what a unit includes (the `# n "file"` line markers); nothing is launched."""
+"""CPU tests: what the kernel sources are made of.  Every csrc/aie_kernels*.hip and the device library header is a
+unit that compiles on its own (it includes what it uses: no file relies on its place in aie_capi.hip's include block),
+no kernel file outside the gather-trade-build family is compiled from gather-trade-build code, the cache key of each
+run-time unit (aie_jit.h: kSources + kSourcesOse / kSourcesGtb) names exactly the project files that unit is compiled
+from, and the library's staleness hash (_build.source_files) reads every project file aie_capi.hip is compiled from.
+The compiler's own preprocessor says what a unit includes (the `# n "file"` line markers); nothing is launched."""
 import ast
 import glob
 import os
@@ -16,6 +17,10 @@ from helpers import ROOT
 CSRC = os.path.join(ROOT, "ai-economist_amd", "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 KERNEL_FILES = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "aie_kernels*.hip")))
+DEVICE_HEADERS = ["aie_device.h"]
+# the gather-trade-build family ("How the kernel sources are organised"); every other kernel file sees the
+# device library only
+GTB_FILES = ["aie_kernels.hip"]
 # aie_jit_image.h as aie_jit.h writes it per configuration; the preprocessor does not care for the image's size
 STUB_IMAGE = ("#pragma once\n#define AIE_N_SPECS 1\ntemplate <int K> struct aie_spec_image;\n"
               "alignas(16) static constexpr unsigned char aie_jit_bytes[1] = {0};\n"
@@ -34,41 +39,54 @@ def _hipcc():
 
 def _project_files(unit, extra=()):
     """The files under the repository that the device side of `unit` is compiled from, the unit itself included."""
-    text = subprocess.run(_hipcc() + ["-E"] + list(extra) + [unit, "-o", "-"], check=True, capture_output=True, text=True).stdout
+    text = subprocess.run(_hipcc() + ["-E"] + list(extra) + ["-x", "hip", unit, "-o", "-"], check=True, capture_output=True, text=True).stdout
     files = {os.path.realpath(f) for f in re.findall(r'(?m)^# \d+ "([^"<][^"]*)"', text)}
     return {f for f in files if f.startswith(os.path.realpath(ROOT) + os.sep)}
 
 
-@pytest.mark.parametrize("name", KERNEL_FILES)
+@pytest.mark.parametrize("name", KERNEL_FILES + DEVICE_HEADERS)
 def test_each_kernel_file_compiles_on_its_own(name):
-    r = subprocess.run(_hipcc() + ["-fsyntax-only", os.path.join(CSRC, name)], capture_output=True, text=True)
+    r = subprocess.run(_hipcc() + ["-fsyntax-only", "-x", "hip", os.path.join(CSRC, name)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
 
 
+@pytest.mark.parametrize("name", [n for n in KERNEL_FILES if n not in GTB_FILES])
+def test_only_the_gather_trade_build_family_sees_gather_trade_build_code(name):
+    assert all(os.path.exists(os.path.join(CSRC, n)) for n in GTB_FILES), GTB_FILES
+    seen = {os.path.basename(f) for f in _project_files(os.path.join(CSRC, name))}
+    assert "aie_device.h" in seen and not seen & set(GTB_FILES), sorted(seen)
+
+
 def _jit_units():
-    """(kSources, the two source strings) as csrc/aie_jit.h states them."""
+    """{"ose" / "gtb": (the unit's key list, its source string)} as csrc/aie_jit.h states them: the shared list plus the
+    unit's own."""
     with open(os.path.join(CSRC, "aie_jit.h")) as f:
         text = f.read()
-    listed = re.search(r"kSources\[\]\s*=\s*\{(.*?)\};", text, re.S).group(1)
+
+    def listed(name):
+        return re.findall(r'"([^"]+)"', re.search(name + r"\[\]\s*=\s*\{(.*?)\};", text, re.S).group(1))
+
     units = re.search(r'std::string src = ose \? ("(?:[^"\\]|\\.)*")\s*:\s*("(?:[^"\\]|\\.)*");', text)
-    return re.findall(r'"([^"]+)"', listed), [ast.literal_eval(units.group(k)) for k in (1, 2)]
+    return {"ose": (listed("kSources") + listed("kSourcesOse"), ast.literal_eval(units.group(1))),
+            "gtb": (listed("kSources") + listed("kSourcesGtb"), ast.literal_eval(units.group(2)))}
 
 
 def test_specialisation_cache_key_covers_what_it_compiles(tmp_path):
-    listed, units = _jit_units()
-    assert len(units) == 2 and all("#define AIE_JIT 1" in u for u in units), units
+    units = _jit_units()
     (tmp_path / "aie_jit_image.h").write_text(STUB_IMAGE)
-    compiled = set()
-    for k, unit in enumerate(units):
-        src = tmp_path / ("aie_jit_%d.hip" % k)
+    for which, (listed, unit) in units.items():  # each unit's key is its own
+        assert "#define AIE_JIT 1" in unit and ("#define AIE_JIT_OSE 1" in unit) == (which == "ose"), unit
+        src = tmp_path / ("aie_jit_%s.hip" % which)
         src.write_text(unit)
-        compiled |= _project_files(str(src), ["-I" + str(tmp_path)])
-    compiled = {f for f in compiled if not f.startswith(os.path.realpath(str(tmp_path)) + os.sep)}
-    keyed = {os.path.realpath(os.path.join(CSRC, s)) for s in listed} | {os.path.realpath(os.path.join(INCLUDE, "aie.h"))}
-    assert len(listed) == len(set(listed))
-    assert compiled == keyed, (sorted(compiled - keyed), sorted(keyed - compiled))
-    # the step / reset kernel files only: an edit to a trainer-side kernel file leaves every cached code object valid
-    assert sorted(s for s in listed if s.endswith(".hip")) == ["aie_kernels.hip", "aie_kernels_ose.hip"], listed
+        compiled = _project_files(str(src), ["-I" + str(tmp_path)])
+        compiled = {f for f in compiled if not f.startswith(os.path.realpath(str(tmp_path)) + os.sep)}
+        keyed = {os.path.realpath(os.path.join(CSRC, s)) for s in listed} | {os.path.realpath(os.path.join(INCLUDE, "aie.h"))}
+        assert len(listed) == len(set(listed)), listed
+        assert compiled == keyed, (which, sorted(compiled - keyed), sorted(keyed - compiled))
+    # the unit's own step / reset kernel files only: an edit to a trainer-side kernel file, or to the other scenario
+    # family's, leaves a unit's cached code objects valid
+    assert sorted(s for s in units["ose"][0] if s.endswith(".hip")) == ["aie_kernels_ose.hip"], units["ose"][0]
+    assert sorted(s for s in units["gtb"][0] if s.endswith(".hip")) == ["aie_kernels.hip"], units["gtb"][0]
 
 
 def test_library_staleness_hash_reads_what_the_library_is_compiled_from():

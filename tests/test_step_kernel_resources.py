@@ -70,14 +70,14 @@ def test_headline_step_kernel_has_no_scratch_and_no_spills(tmp_path):
 
 
 def test_headline_configuration_keeps_16_workgroups_per_cu(tmp_path):
-    """aie::lds_bytes of configs[1]'s constant image, evaluated by the host code of csrc/aie_kernels.hip itself: a
+    """aie::lds_bytes of configs[1]'s constant image, evaluated by the host code of csrc/aie_device.h itself: a
     host-only compile of three lines.  Nothing is launched, so the (absent) device image stays an unresolved symbol."""
     from ai_economist_amd import _build
 
     if not _build.have_hipcc():
-        pytest.skip("hipcc not found: the host side of aie_kernels.hip cannot be compiled")
+        pytest.skip("hipcc not found: the host side of aie_device.h cannot be compiled")
     src, exe = tmp_path / "lds_bytes.hip", str(tmp_path / "lds_bytes")
-    src.write_text('#include "aie_kernels.hip"\n#include <cstdio>\n'
+    src.write_text('#include "aie_device.h"\n#include <cstdio>\n'
                    'int main() { printf("%zu\\n", aie::lds_bytes(*reinterpret_cast<const aie_params*>(aie_spec_image<0>::bytes))); }\n')
     subprocess.run([_build.hipcc_path(), "--cuda-host-only", "-O0", "-std=c++17", "-Wno-comment", "-I" + os.path.join(ROOT, "include"),
                     "-I" + _build.CSRC, "-Wl,--unresolved-symbols=ignore-all", str(src), "-o", exe], check=True)
