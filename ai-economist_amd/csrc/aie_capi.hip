@@ -301,7 +301,7 @@ static aie_route<aie_reset_fn> aie_select_reset(const aie_env* env) {
   const aie_params& P = env->P;
   if (P.c.scenario == AIE_SCN_COVID) return {AIE_KERNEL(aie_covid_reset_kernel), false, AIE_NT, 0};
   if (P.c.scenario == AIE_SCN_ONE_STEP_ECONOMY) return {{nullptr, "aie_ose_reset_kernel"}, false, OSE_NT, env->lds};
-  // LG_NW wavefronts per replica when the reset draws a new source layout (aie_kernels.hip: layout_generate), else one
+  // LG_NW wavefronts per replica when the reset draws a new source layout (aie_gtb_layoutgen.h: layout_generate), else one
   const bool layout = P.c.layout_gen != AIE_LAYOUT_FIXED;
   aie_route<aie_reset_fn> r = {AIE_KERNEL(aie_reset_kernel), false, AIE_NT, env->lds + aie::layout_gen_lds_bytes(P)};
   if (layout) r.k = AIE_KERNEL(aie_reset_kernel_layout), r.block = LG_NW * AIE_NT;

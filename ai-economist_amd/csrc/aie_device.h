@@ -1,7 +1,7 @@
 // aie_device.h -- the device library every kernel file is written against: Ctx and the LDS carve-up, the wave helpers
 // and buffer stores, the record's way in and out, the generators (Philox, MT19937 in registers, the draw window, rng_*),
 // the NumPy-order sums, the tax schedule, NextActions and the reward log's slot.  No kernel and nothing of one scenario
-// belongs here: what only the gather-trade-build family uses is in aie_kernels.hip.  Part of
+// belongs here: what only the gather-trade-build family uses is in aie_gtb_*.h and aie_kernels.hip.  Part of
 // both run-time units (aie_jit.h): its hash is in every cached code object's key.
 #pragma once
 #include <hip/hip_runtime.h>

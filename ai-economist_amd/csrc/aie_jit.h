@@ -98,7 +98,8 @@ static const char* const kRecipe = "recipe 2: -O3 -std=c++17 -Wno-comment";  // 
 // includes differ.
 static const char* const kSources[] = {"aie_device.h", "aie_layout.h", "aie_glibc_math.h", "aie_glibc_tables.h"};
 static const char* const kSourcesOse[] = {"aie_kernels_ose.hip"};
-static const char* const kSourcesGtb[] = {"aie_kernels.hip"};
+static const char* const kSourcesGtb[] = {"aie_kernels.hip", "aie_gtb_state.h", "aie_gtb_components.h", "aie_gtb_observe.h",
+                                          "aie_gtb_layoutgen.h"};
 
 // Compiles (or fetches from the cache) the code object for `image` (sizeof(aie_params) normalised bytes); `waves` =
 // waves per SIMD the kernel is compiled for.  On failure returns false with a message in `err`.

@@ -123,7 +123,7 @@ class DeviceBackend(TrainerOps):
                                             wood_src.ctypes.data, water.ctypes.data))
         self._rand_a = None
         self._rand_p = None
-        # element counts the kernels index (aie_kernels.hip: decode_actions reads aa[(e*n + i) * act_a_width + s] and
+        # element counts the kernels index (aie_gtb_state.h: decode_actions reads aa[(e*n + i) * act_a_width + s] and
         # ap[e * act_p_width + b]): checked on every call, a wrongly shaped buffer would be read out of bounds
         wa = 1 if not cfg.multi_action_mode_agents else max(1, self._n_sub_a())
         self.act_a_numel = self.E * self.n * wa

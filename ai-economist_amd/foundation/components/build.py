@@ -1,5 +1,5 @@
 """`Build` (reference: F/components/build.py:15-110; dynamics -> build_component_step
-in csrc/aie_kernels.hip)."""
+in csrc/aie_gtb_components.h)."""
 from ... import _cabi
 from .base import BaseComponent, component_registry
 

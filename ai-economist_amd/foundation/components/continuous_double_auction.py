@@ -1,5 +1,5 @@
 """`ContinuousDoubleAuction` (reference: F/components/continuous_double_auction.py:16-98,
-411-431; dynamics -> cda_component_step / cda_match_orders in csrc/aie_kernels.hip)."""
+411-431; dynamics -> cda_component_step / cda_match_orders in csrc/aie_gtb_components.h)."""
 from ... import _cabi
 from .base import BaseComponent, component_registry
 

@@ -1,7 +1,7 @@
 """`WealthRedistribution` (reference: F/components/redistribution.py:21-75; dynamics ->
-wealth_component_step in csrc/aie_kernels.hip / aie_kernels_ose.hip) and
+wealth_component_step in csrc/aie_gtb_components.h / aie_kernels_ose.hip) and
 `PeriodicBracketTax` (reference: F/components/redistribution.py:78-346, 920-939;
-dynamics -> tax_component_step / tax_enact in csrc/aie_kernels.hip, the schedule in csrc/aie_device.h).
+dynamics -> tax_component_step / tax_enact in csrc/aie_gtb_components.h, the schedule in csrc/aie_device.h).
 
 Tax models: "model_wrapper" (planner picks discretised rates),
 "us-federal-single-filer-2018-scaled", "fixed-bracket-rates" and "saez"

@@ -6,7 +6,7 @@ layout per episode (no Water), and agents placed in a random order.
 The layout generation (dynamic_layout.py:313-392: uniform draws, a shrinking threshold,
 then growth by convolving with random 7x7 kernels; MultiZone's per-reset zone shuffle,
 Quadrant's empty water lines) runs INSIDE the reset kernel, from each replica's own
-legacy-NumPy stream (csrc/aie_kernels.hip: layout_generate; restated for the checker in
+legacy-NumPy stream (csrc/aie_gtb_layoutgen.h: layout_generate; restated for the checker in
 oracle/aie_oracle.c and pinned there against the live reference): a reset has no host
 round trip.  This module supplies the static source-probability maps and the kwargs.
 `generate_layout*` below is the same procedure on the host (NumPy / SciPy), kept for worlds

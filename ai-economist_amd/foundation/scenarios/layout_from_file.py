@@ -2,7 +2,7 @@
 F/scenarios/simple_wood_and_stone/layout_from_file.py:17-267): fixed Wood / Stone /
 Water layout, stochastic regeneration, egocentric crop observations, isoelastic
 utility rewards.  Dynamics -> scenario_step_regen / write_observations /
-compute_rewards in csrc/aie_kernels.hip.
+compute_rewards in csrc/aie_gtb_observe.h.
 """
 import os
 

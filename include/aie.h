@@ -567,7 +567,7 @@ int aie_select_step_kernel(aie_env* env, int which);
  * for the BASELINE configurations: the code-shaping part of the parameter block (component tuple, agent count, world
  * size, capacities, flags; NOT scalars such as starting coin, eta, episode length, labor costs, tax period / cutoffs,
  * which every specialised kernel reads at run time) becomes a compile-time constant of the kernels (hiprtc compiles
- * csrc/aie_kernels.hip with it as a constant image, a few seconds once; the code object is cached under
+ * csrc/aie_kernels.hip and the aie_gtb_*.h it includes with it as a constant image, a few seconds once; the code object is cached under
  * $AIE_JIT_CACHE / ~/.cache/ai_economist_amd -- private directories only -- keyed by the image, the sources, the
  * architecture, the compiler version and options).  aie_create already starts this in the background and a later
  * aie_reset (an episode boundary, outside stream capture; never aie_step) adopts the result; this call WAITS for it.  Afterwards AIE_KERNEL_AUTO runs

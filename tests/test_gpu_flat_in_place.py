@@ -1,4 +1,4 @@
-"""The flat observation vectors updated in place (csrc/aie_kernels.hip: update_flat_observations): a whole step whose
+"""The flat observation vectors updated in place (csrc/aie_gtb_observe.h: update_flat_observations): a whole step whose
 tensors still show the previous step writes only what the step changed -- time, world scalars, marginal rate and tax
 calendar always, a histogram column when the auction touched it, the tax block's slow entries through the full writer on
 the two steps of a period that change them.  Everything here compares the observation tensors, rewards and done with the

@@ -180,7 +180,7 @@ def test_c4_full_batch_matches_oracle(recurrence):
 
 def test_c1_uniform_layouts_drawn_on_device_full_batch():
     """BASELINE configs[0]'s scenario (uniform 15x15, Build + Gather) at 4096 replicas: every replica draws its own
-    source layout INSIDE the reset kernel (no host round trip: aie_kernels.hip layout_generate), bit-identical to
+    source layout INSIDE the reset kernel (no host round trip: aie_gtb_layoutgen.h layout_generate), bit-identical to
     the restatement's layouts (which the CPU tests pin to the live reference); two episodes with auto-reset."""
     import time
 

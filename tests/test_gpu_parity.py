@@ -537,7 +537,7 @@ def test_large_uniform_worlds(side, on_device):
 
 def test_dense_source_layouts_take_the_row_by_row_regeneration():
     """More than 128 source doubles per replica (here: uniform layouts drawn with 22 % coverage per resource on
-    20 x 20) leave the sparse gather regeneration for the row-by-row fallback (aie_kernels.hip:
+    20 x 20) leave the sparse gather regeneration for the row-by-row fallback (aie_gtb_components.h:
     scenario_step_regen_rows): same stream, same respawns as the oracle."""
     import torch
     from helpers import oracle_host_pre_reset

@@ -1,6 +1,8 @@
 """CPU tests: what the kernel sources are made of.  Every csrc/aie_kernels*.hip and the device library header is a
 unit that compiles on its own (it includes what it uses: no file relies on its place in aie_capi.hip's include block),
-no kernel file outside the gather-trade-build family is compiled from gather-trade-build code, the cache key of each
+no kernel file outside the gather-trade-build family is compiled from gather-trade-build code, the family's four headers
+of device functions include one another in one direction only (state <- components, state <- observe, the layout
+generator beside them, and none of them the kernel file), the cache key of each
 run-time unit (aie_jit.h: kSources + kSourcesOse / kSourcesGtb) names exactly the project files that unit is compiled
 from, and the library's staleness hash (_build.source_files) reads every project file aie_capi.hip is compiled from.
 The compiler's own preprocessor says what a unit includes (the `# n "file"` line markers); nothing is launched."""
@@ -17,10 +19,11 @@ from helpers import ROOT
 CSRC = os.path.join(ROOT, "ai-economist_amd", "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 KERNEL_FILES = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "aie_kernels*.hip")))
-DEVICE_HEADERS = ["aie_device.h"]
-# the gather-trade-build family ("How the kernel sources are organised"); every other kernel file sees the
-# device library only
-GTB_FILES = ["aie_kernels.hip"]
+# the gather-trade-build family ("How the kernel sources are organised"): its kernel file and the four headers
+# of device functions it is cut into; every other kernel file sees the device library only
+GTB_HEADERS = ["aie_gtb_state.h", "aie_gtb_components.h", "aie_gtb_observe.h", "aie_gtb_layoutgen.h"]
+GTB_FILES = ["aie_kernels.hip"] + GTB_HEADERS
+DEVICE_HEADERS = ["aie_device.h"] + GTB_HEADERS
 # aie_jit_image.h as aie_jit.h writes it per configuration; the preprocessor does not care for the image's size
 STUB_IMAGE = ("#pragma once\n#define AIE_N_SPECS 1\ntemplate <int K> struct aie_spec_image;\n"
               "alignas(16) static constexpr unsigned char aie_jit_bytes[1] = {0};\n"
@@ -57,15 +60,31 @@ def test_only_the_gather_trade_build_family_sees_gather_trade_build_code(name):
     assert "aie_device.h" in seen and not seen & set(GTB_FILES), sorted(seen)
 
 
+@pytest.mark.parametrize("name, unseen", [
+    ("aie_gtb_state.h", ["aie_gtb_components.h", "aie_gtb_observe.h", "aie_gtb_layoutgen.h"]),
+    ("aie_gtb_components.h", ["aie_gtb_observe.h", "aie_gtb_layoutgen.h"]),
+    ("aie_gtb_observe.h", ["aie_gtb_components.h", "aie_gtb_layoutgen.h"]),
+    ("aie_gtb_layoutgen.h", ["aie_gtb_components.h", "aie_gtb_observe.h"]),
+])
+def test_gather_trade_build_headers_depend_one_way(name, unseen):
+    """state <- components, state <- observe, layoutgen beside them; all four <- aie_kernels.hip and never back."""
+    seen = {os.path.basename(f) for f in _project_files(os.path.join(CSRC, name))}
+    assert name in seen and "aie_device.h" in seen, sorted(seen)
+    assert not seen & set(unseen + ["aie_kernels.hip"]), sorted(seen)
+
+
+def _jit_listed(name):
+    """One of csrc/aie_jit.h's lists of file names (kSources, kSourcesOse, kSourcesGtb)."""
+    with open(os.path.join(CSRC, "aie_jit.h")) as f:
+        return re.findall(r'"([^"]+)"', re.search(name + r"\[\]\s*=\s*\{(.*?)\};", f.read(), re.S).group(1))
+
+
 def _jit_units():
     """{"ose" / "gtb": (the unit's key list, its source string)} as csrc/aie_jit.h states them: the shared list plus the
     unit's own."""
     with open(os.path.join(CSRC, "aie_jit.h")) as f:
         text = f.read()
-
-    def listed(name):
-        return re.findall(r'"([^"]+)"', re.search(name + r"\[\]\s*=\s*\{(.*?)\};", text, re.S).group(1))
-
+    listed = _jit_listed
     units = re.search(r'std::string src = ose \? ("(?:[^"\\]|\\.)*")\s*:\s*("(?:[^"\\]|\\.)*");', text)
     return {"ose": (listed("kSources") + listed("kSourcesOse"), ast.literal_eval(units.group(1))),
             "gtb": (listed("kSources") + listed("kSourcesGtb"), ast.literal_eval(units.group(2)))}
@@ -87,6 +106,9 @@ def test_specialisation_cache_key_covers_what_it_compiles(tmp_path):
     # family's, leaves a unit's cached code objects valid
     assert sorted(s for s in units["ose"][0] if s.endswith(".hip")) == ["aie_kernels_ose.hip"], units["ose"][0]
     assert sorted(s for s in units["gtb"][0] if s.endswith(".hip")) == ["aie_kernels.hip"], units["gtb"][0]
+    # cutting the gather-trade-build unit into files leaves the other unit's key, and so its cached code objects, alone
+    assert units["ose"][0] == _jit_listed("kSources") + ["aie_kernels_ose.hip"], units["ose"][0]
+    assert sorted(units["gtb"][0]) == sorted(_jit_listed("kSources") + GTB_FILES), units["gtb"][0]
 
 
 def test_library_staleness_hash_reads_what_the_library_is_compiled_from():
