@@ -81,7 +81,7 @@ SPECS = [
 def _tool():
     exe = os.path.join(tempfile.gettempdir(), "aie_specgen_%d" % os.getuid())
     src = os.path.join(CSRC, "aie_specgen.c")
-    deps = [src, os.path.join(CSRC, "aie_layout.h"), os.path.join(ROOT, "include", "aie.h")]
+    deps = [src, os.path.join(CSRC, "aie_layout.h"), os.path.join(CSRC, "aie_layout_build.h"), os.path.join(ROOT, "include", "aie.h")]
     if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
         tmp = "%s.%d" % (exe, os.getpid())  # never execute a half-written tool (several ranks may build at once)
         subprocess.run(["gcc", "-O1", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, src, "-o", tmp, "-lm"], check=True)

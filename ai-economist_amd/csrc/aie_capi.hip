@@ -18,6 +18,7 @@
 #include "aie_kernels_mlp_bwd.hip"
 #include "aie_kernels_covid.hip"
 #include "aie_jit.h"
+#include "aie_layout_build.h"  // host only: aie_build_params and the tensor table
 #include "aie_trainer_plan.h"  // host only: the trainer calls' plans
 
 struct aie_env {

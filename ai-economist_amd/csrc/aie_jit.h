@@ -96,6 +96,9 @@ static const char* const kRecipe = "recipe 2: -O3 -std=c++17 -Wno-comment";  // 
 // other's cached code objects valid.  Kept by hand so that a key does not grow to files its unit never sees;
 // tests/test_kernel_sources.py preprocesses both source strings below and fails when a unit's lists and what it
 // includes differ.
+// aie_layout.h is what a kernel reads of the layout.  The builders of the parameter block (aie_layout_build.h) and the
+// trainer side's arithmetic (aie_trainer_math.h) are deliberately NOT keyed: no unit includes either, and what the
+// builders decide reaches a specialised kernel only through the normalised image, which is hashed into the key itself.
 static const char* const kSources[] = {"aie_device.h", "aie_layout.h", "aie_glibc_math.h", "aie_glibc_tables.h"};
 static const char* const kSourcesOse[] = {"aie_kernels_ose.hip"};
 static const char* const kSourcesGtb[] = {"aie_kernels.hip", "aie_gtb_state.h", "aie_gtb_components.h", "aie_gtb_observe.h",

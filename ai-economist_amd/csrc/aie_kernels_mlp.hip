@@ -1,5 +1,5 @@
 // ---- the policy network's forward pass of both actor classes in one launch (include/aie.h: aie_policy_mlp_forward) ------
-// x[F] -> relu -> H -> relu -> H -> M logits (+ 1 value) per row; the arithmetic is aie_layout.h's (aie_mlp_row): every
+// x[F] -> relu -> H -> relu -> H -> M logits (+ 1 value) per row; the arithmetic is aie_trainer_math.h's (aie_mlp_row): every
 // output is ONE ascending-k fmaf chain that starts from the bias.  v_mfma_f32_16x16x4_f32 is exactly that chain (one
 // rounding per product, nothing wider in between), so the accumulator is initialised with the bias and a tile's K is
 // walked in order by one accumulator; MFMA latency is hidden by the independent output tiles a wave owns, never by a
@@ -20,6 +20,7 @@
 // No atomics, no allocation, no synchronisation with the host.
 #pragma once
 #include "aie_device.h"
+#include "aie_trainer_math.h"
 
 typedef float aie_mlp_f4 __attribute__((ext_vector_type(4)));
 typedef const float __attribute__((address_space(1))) * aie_mlp_gptr;  // global memory, said so: a walked pointer otherwise loads as flat

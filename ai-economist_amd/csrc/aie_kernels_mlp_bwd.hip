@@ -1,5 +1,5 @@
 // ---- the policy network's backward pass: the weights' gradients of both actor classes, three launches ---------------------
-// (include/aie.h: aie_policy_mlp_backward; the arithmetic is aie_layout.h's: aie_mlp_row_backward and aie_mlp_grad_entry)
+// (include/aie.h: aie_policy_mlp_backward; the arithmetic is aie_trainer_math.h's: aie_mlp_row_backward and aie_mlp_grad_entry)
 //
 // A. aie_policy_mlp_bwd_rows_kernel: the forward's row tiles (AIE_MLP_TILE_ROWS rows of one class per workgroup, the block
 //    range split between the classes).  h1 and h2 are recomputed with the forward's machinery (mlp_tiles: the same MFMA

@@ -1,6 +1,6 @@
 // ---- the PPO loss of both actor classes with its gradients (include/aie.h: aie_ppo_loss) --------------------------------
 // Forward and backward of the clipped surrogate, the clipped value loss and the entropy bonus in two launches.  The
-// arithmetic is aie_layout.h's (aie_ppo_actor_terms, aie_ppo_value_terms over the evaluator's row values: M, T, S, L, H and
+// arithmetic is aie_trainer_math.h's (aie_ppo_actor_terms, aie_ppo_value_terms over the evaluator's row values: M, T, S, L, H and
 // aie_policy_entry_grad), so the gradients are the CPU twin's bit for bit.
 //
 // Launch 1, aie_ppo_loss_kernel.  A work item is the evaluator's: for single-slot actors with rows of at most 64 entries

@@ -8,7 +8,7 @@
 // aie_policy_evaluate, aie_policy_evaluate_backward) ---------------------------------------------------------------------
 // The learning-time half of the sampler: for B stored replica-steps (any B) the log-probability of the stored sub-action
 // and the entropy of every action slot, from new logits under the stored masks, in the sampler's own arithmetic
-// (aie_layout.h: M, y, w, T in the scan's order, aie_sampler_logf, S, H, the backward's operation order), so that what is
+// (aie_trainer_math.h: M, y, w, T in the scan's order, aie_sampler_logf, S, H, the backward's operation order), so that what is
 // evaluated is the distribution that was drawn from -- bit for bit the CPU twin's values.  The layout is the fast
 // sampler's: a lane per entry, as many whole rows to a wave as fit in aligned segments of 16 / 32 / 64 lanes (the shape is
 // a wave-uniform switch to compile-time instances), the row maximum and both sums (T and S) by the sampler's DPP steps, the
@@ -175,7 +175,7 @@ extern "C" __global__ void __launch_bounds__(256) aie_policy_eval_kernel(const a
 extern "C" __global__ void __launch_bounds__(256) aie_policy_eval_bwd_kernel(const aie_policy_eval_args A) { policy_eval_body<true>(A); }
 
 // ---- generalised advantage estimation from the reward log (include/aie.h: aie_gae) ---------------------------------------
-// The recurrence (aie_layout.h: aie_gae_step) is serial in t down a column (replica, actor) and is NOT re-associated across
+// The recurrence (aie_trainer_math.h: aie_gae_step) is serial in t down a column (replica, actor) and is NOT re-associated across
 // time: these are the bits of the plain float32 loop.  What is parallel is the loads.  A lane per float of a log row
 // (lane c = e (n + 2) + j), so a wave's reward loads are 256 contiguous bytes of the row whatever n is; the done flag is a
 // second load of the same lines (the lane's replica's last column); the values come from one load per step through a

@@ -4,6 +4,7 @@
 // an edit here leaves the cached step / reset code objects valid.
 #pragma once
 #include "aie_device.h"
+#include "aie_trainer_math.h"
 
 // Synthetic uniform random policy of the benchmark: a counter RNG
 // keyed (seed, global replica id, t, agent); one thread per (replica, agent slot).
@@ -93,7 +94,7 @@ extern "C" __global__ void aie_sample_masked_actions_kernel(const aie_params P, 
 // weights exp(logit_k - max), their prefix sums run in a fixed order, one uniform u per slot from a counter hash keyed
 // (seed, global replica, the replica's draw index t, slot) picks the first entry whose sum passes u times the total (NaN
 // logits count as masked; nothing allowed: NO-OP).  float32 throughout, every operation a plain IEEE add / multiply / fma
-// in a fixed order (aie_layout.h: aie_sampler_expf and the scan's definition), so the CPU restatement picks the same
+// in a fixed order (aie_trainer_math.h: aie_sampler_expf and the scan's definition), so the CPU restatement picks the same
 // entries.  The kernel is bound by the vector instructions it issues (round 6 counters: 530 per wave and 16 waves per
 // SIMD were 14 of its 19.7 us), so everything that is the same for a row runs on the scalar unit (the row's addresses,
 // its hash, the pick from the ballot) and the cross-lane steps are single DPP instructions: a WORK ITEM is one action
@@ -132,7 +133,7 @@ __device__ __forceinline__ float sampler_segment_max(float m, int seg) {
   }
   return m;
 }
-// Inclusive prefix sums of one 64-entry chunk in the sampler's fixed order (aie_layout.h).
+// Inclusive prefix sums of one 64-entry chunk in the sampler's fixed order (aie_trainer_math.h).
 __device__ __forceinline__ float sampler_scan(float v, int seg) {
   asm("s_nop 4\n\t"
       "v_add_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\ts_nop 1\n\t"
@@ -468,7 +469,7 @@ __device__ __forceinline__ void sampler_fast_run(const SamplerFast<LSH>& G, int 
   const uint64_t hits = __ballot(hit);
   const bool first = hit && (((uint32_t)hits & G.below_lo) | ((uint32_t)(hits >> 32) & G.below_hi)) == 0u;
   if (first) *reinterpret_cast<int32_t*>(reinterpret_cast<char*>(G.dst) + 4u * (uint32_t)(r0 + G.sub)) = G.kk;
-  // log pi of the pick, by the lane that stores the pick: y - aie_sampler_logf(T) (aie_layout.h; a hit means T > 0)
+  // log pi of the pick, by the lane that stores the pick: y - aie_sampler_logf(T) (aie_trainer_math.h; a hit means T > 0)
   float lpv = 0.0f;
   if constexpr (LOGP) {
     lpv = (x - M) - aie_sampler_logf(Tl > 0.0f ? Tl : 1.0f);

@@ -4,7 +4,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include "aie_layout.h"
+#include "aie_layout_build.h"
 
 int main(void) {
   aie_config c;

@@ -8,10 +8,10 @@
 #define AIE_TRAINER_PLAN_H_
 
 #include "aie.h"
-#include "aie_layout.h"
+#include "aie_trainer_math.h"
 
 #if AIE_TRAJ_SEGMENTS != AIE_TRAJ_MAX_SEGMENTS
-#error "aie_layout.h and aie.h disagree on the segment count"
+#error "aie_trainer_math.h and aie.h disagree on the segment count"
 #endif
 #if AIE_MLP_TILE_ROWS != 32 && AIE_MLP_TILE_ROWS != 64
 #error "the MLP kernels' row tile is 2 or 4 MFMA tiles"

@@ -372,7 +372,7 @@ int aie_destroy(aie_env* env);
 const char* aie_last_error(const aie_env* env /* NULL: last create error */);
 
 /* Number of exported tensors and their descriptors (index or name lookup).  Names (aie_num_tensors /
- * aie_tensor_at enumerate what a configuration has; csrc/aie_layout.h is where they are defined):
+ * aie_tensor_at enumerate what a configuration has; csrc/aie_layout_build.h is where they are defined):
  *   observations  obs_a_world-map, obs_a_world-idx_map, obs_a_flat, obs_a_action_mask, obs_a_time, obs_p_* (flat,
  *                 action_mask, time, world-map, world-idx_map, agents = the planner's per-agent p{i} fragments)
  *   outputs       rewards_a [E, n], rewards_p [E], done [E]
@@ -589,7 +589,7 @@ int aie_specialize(aie_env* env);
  * Sub-action = a draw from softmax(logits) restricted to the mask by inverse CDF: weights exp(logit_k - max) of the allowed
  * entries, their prefix sums in a fixed order, the first entry whose sum passes u x total, u in (0, 1) from a counter hash
  * keyed (seed, global env id, the replica's draw index, slot); NaN logits count as masked, NO-OP if nothing is allowed.
- * Everything is float32 and a fixed sequence of IEEE add / multiply / fused multiply-add operations (csrc/aie_layout.h:
+ * Everything is float32 and a fixed sequence of IEEE add / multiply / fused multiply-add operations (csrc/aie_trainer_math.h:
  * aie_sampler_expf, aie_sampler_uniform, aie_sampler_entry_rng, the scan's order), so the CPU restatement (oracle/:
  * aie_oracle_sample_policy_actions) picks the same entries; a probability is resolved to 2^-24 of its row's total and u
  * has 23 bits.  Rows of up to 64 entries with single-action agents (every BASELINE configuration, COVID) run on
@@ -602,7 +602,7 @@ int aie_sample_policy_actions(aie_env* env, const float* d_logits_a, const float
 /* aie_sample_policy_actions that also returns log pi(a|s) of every pick: the same picks and the same advance of
  * `sample_t`, bit for bit (the same kernels with one more store per action slot), one launch, replayable from a hipGraph.
  *   d_logp_a  float32 [E, n, width_a]   d_logp_p  float32 [E, width_p]   (the action buffers' shapes)
- * logp = y_a - log T (aie_sampler_logf) with the sampler's own y = logit - max, weights and total T (csrc/aie_layout.h: a
+ * logp = y_a - log T (aie_sampler_logf) with the sampler's own y = logit - max, weights and total T (csrc/aie_trainer_math.h: a
  * fixed sequence of float32 operations, no libm; the CPU twin aie_policy_row_logp gives the same bits); 0 for a slot
  * where nothing is allowed (the pick there is NO-OP).  Either actor class (logits, actions, logp) may be NULL. */
 int aie_sample_policy_actions_logp(aie_env* env, const float* d_logits_a, const float* d_logits_p, uint64_t seed,
@@ -619,7 +619,7 @@ int aie_sample_policy_actions_logp(aie_env* env, const float* d_logits_a, const 
  *       arena's collated rows); NULL = the arena's current masks, B == E only;
  *   d_actions_a int32 [B, n, width_a] / d_actions_p int32 [B, width_p]: the stored sub-actions;
  *   d_logp_* / d_entropy_*: float32, the actions' shapes: log pi of the stored sub-action and the entropy H of its slot.
- * Per slot (csrc/aie_layout.h states every operation): allowed = mask > 0.5 and logit not NaN; logp_k = y_k - log T;
+ * Per slot (csrc/aie_trainer_math.h states every operation): allowed = mask > 0.5 and logit not NaN; logp_k = y_k - log T;
  * H = log T - S / T, S = sum of w_k y_k in the scan's order.  A slot where nothing is allowed: logp 0, H 0.  A stored
  * action its mask does not allow (or outside the row): logp -INFINITY.  An allowed entry 80 or more below the maximum has
  * weight 0 and a finite logp.  Either actor class may be NULL, and so may any output.  One launch, asynchronous on
@@ -630,7 +630,7 @@ int aie_policy_evaluate(aie_env* env, int64_t B, const float* d_logits_a, const 
 
 /* Its backward: d_grad_logits_* (the logits' shapes) = the gradient of sum(d_glogp * logp + d_gentropy * H) with respect
  * to the logits,  g_k = g_logp ([k = a] - p_k) - g_H p_k (logp_k + H)  for allowed entries (p_k = w_k / T; the operation
- * order is in csrc/aie_layout.h) and exactly 0 for the others; every entry of the buffers is written.  M, T and S are
+ * order is in csrc/aie_trainer_math.h) and exactly 0 for the others; every entry of the buffers is written.  M, T and S are
  * recomputed (nothing is kept from the forward).  A slot where nothing is allowed has a zero gradient row; the g_logp of
  * a stored action its mask does not allow contributes nothing.  d_glogp_* / d_gentropy_* may be NULL (= zeros), either
  * actor class may be NULL.  One launch, asynchronous on `stream`. */
@@ -649,7 +649,7 @@ int aie_policy_evaluate_backward(aie_env* env, int64_t B, const float* d_logits_
  *   d_values_a float32 [T + 1][E][n], d_values_p float32 [T + 1][E]: row T is the bootstrap value of the observation behind
  *              the last step;
  *   d_adv_* / d_ret_*: the values' shapes with T rows.
- * float32, every product and sum rounded on its own (no fma), a fixed order (csrc/aie_layout.h states it once; the CPU test
+ * float32, every product and sum rounded on its own (no fma), a fixed order (csrc/aie_trainer_math.h states it once; the CPU test
  * compiles the same helper): with gl = gamma * lambda rounded once and done_t = log[t][e][n + 1] > 0.5,
  *   delta_t = done_t ? r_t - V_t : (r_t + gamma V_{t+1}) - V_t,   A_t = done_t ? delta_t : delta_t + gl A_{t+1}  (A_T = 0),
  *   ret_t = A_t + V_t
@@ -684,7 +684,7 @@ int aie_gae(aie_env* env, int32_t T, const float* d_log, int32_t n_slots, int32_
  *   ratio left [1 - clip, 1 + clip], [6] the number of skipped actors, [7] the largest |logp - logp_old| of the others.
  * The means are over all N = B x actors of the class.  An actor whose joint logp or stored old logp is not finite, or whose
  * log-ratio exceeds 80 in magnitude, is SKIPPED: it adds 0 to [1], [4], [5] and has no policy gradient, but keeps its
- * entropy and value terms.  csrc/aie_layout.h states every operation (float32, each rounded on its own, in the sampler's
+ * entropy and value terms.  csrc/aie_trainer_math.h states every operation (float32, each rounded on its own, in the sampler's
  * arithmetic: a step evaluated under the logits it was sampled from has ratio exactly 1); the sums are float64 over the
  * float32 terms in an order that is fixed for a given B, so two runs give the same bits; no atomics.
  * d_workspace: device memory, 8-byte aligned, the call's own until it has run: calls that may run at the same time (two
@@ -717,7 +717,7 @@ int aie_ppo_loss(aie_env* env, int64_t B, const aie_ppo_class* agents, const aie
  * floats (an arena tensor or any device memory, 4-byte aligned); weights row-major [in, out] float32, the leading dimension
  * the out width (what x @ w takes): w1 [F, H], w2 [H, H], w3 [H, M], biases b1 [H], b2 [H], b3 [M]; wv [H] and bv [1] (device
  * memory) the value column, both NULL for none; logits [rows, M] and values [rows] contiguous.
- * THE ARITHMETIC (csrc/aie_layout.h states it once, aie_mlp_row; the CPU test compiles that helper): all float32,
+ * THE ARITHMETIC (csrc/aie_trainer_math.h states it once, aie_mlp_row; the CPU test compiles that helper): all float32,
  *   chain(c; a, w) = acc after acc = c; for k ascending: acc = fmaf(a[k], w[k], acc)   -- one accumulator, one rounding per term
  *   h1[j] = relu(chain(b1[j]; x, W1[:, j])), h2[j] = relu(chain(b2[j]; h1, W2[:, j])), relu(v) = v > 0 ? v : 0 (NaN -> 0),
  *   logits[j] = chain(b3[j]; h2, W3[:, j]), value = chain(bv; h2, wv).
@@ -744,7 +744,7 @@ int aie_policy_mlp_forward(aie_env* env, int64_t B, const aie_mlp_class* agents,
  * classes as for the forward.  Per class (aie_mlp_grad_class): net -- x, x_ld, the weights, F, H and M as for the forward
  * (net.logits and net.values are ignored); g_logits [rows, M] contiguous and g_values [rows] (NULL exactly when net.wv is);
  * the outputs gw1 .. gbv in the weights' shapes (gwv and gbv NULL exactly when net.wv is).  Nothing is produced for x.
- * THE ARITHMETIC (csrc/aie_layout.h states it once -- aie_mlp_row_backward, aie_mlp_grad_entry -- and the CPU test compiles
+ * THE ARITHMETIC (csrc/aie_trainer_math.h states it once -- aie_mlp_row_backward, aie_mlp_grad_entry -- and the CPU test compiles
  * those helpers): all float32 unless said otherwise; chain0(a, w) = chain(+0; a, w), the forward's chain from zero.  Per row r:
  *   h1, h2 are recomputed exactly as the forward computes them;   dz3[m] = g_logits[r][m], dv = g_values[r];
  *   dh2[j] = chain0 over m ascending of (dz3[m], W3[j][m]), with a value column one last term fmaf(dv, wv[j], acc);

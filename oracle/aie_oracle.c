@@ -22,7 +22,8 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "../ai-economist_amd/csrc/aie_layout.h"
+#include "../ai-economist_amd/csrc/aie_layout_build.h"  /* with aie_layout.h: the device's records and tensors */
+#include "../ai-economist_amd/csrc/aie_trainer_math.h"  /* the sampler's arithmetic */
 
 typedef struct {
   const aie_params* p;
@@ -1848,12 +1849,12 @@ void aie_oracle_seed64(const aie_params* p, uint8_t* arena, uint64_t base_seed) 
 }
 void aie_oracle_seed(const aie_params* p, uint8_t* arena, uint32_t base_seed) { aie_oracle_seed64(p, arena, (uint64_t)base_seed); }
 /* aie_sample_policy_actions (include/aie.h) restated: inverse-CDF sampling over the allowed entries of every action slot,
- * float64 weights exp(logit - max) with the sampler's fixed-operation exp and prefix-sum order (aie_layout.h), one uniform
+ * float64 weights exp(logit - max) with the sampler's fixed-operation exp and prefix-sum order (aie_trainer_math.h), one uniform
  * per slot from the counter RNG keyed (seed, global replica, draw index, slot); NaN logits count as masked, NO-OP if nothing
  * is allowed; advances `sample_t`.  Not part of the reference (its trainers sample in their own framework,
  * training_script.py:88-133): this pins the PRODUCT's sampler.  Gather-trade-build and one-step-economy layouts (COVID's
  * collated masks: a Python transcription in tests/test_gpu_parity.py). */
-/* One row of the inverse-CDF sampler (aie_layout.h: the sampler's definition): chunks of 64 entries, the fixed-order scan
+/* One row of the inverse-CDF sampler (aie_trainer_math.h: the sampler's definition): chunks of 64 entries, the fixed-order scan
  * inside a chunk, a running carry from chunk to chunk. */
 int32_t aie_oracle_sample_row(const float* lg, const float* mask, int mask_stride, int len, uint32_t rnd) {
   int any = 0;
@@ -1949,7 +1950,7 @@ void aie_oracle_sample_policy_actions(const aie_params* p, uint8_t* arena, const
     *tf = (int32_t)t + 1;
   }
 }
-/* the sampler's building blocks (aie_layout.h), exported so that a CPU test can hold them to their Python transcription
+/* the sampler's building blocks (aie_trainer_math.h), exported so that a CPU test can hold them to their Python transcription
  * and to libm */
 /* the layout stream of a replica's k-th reset in the counter-stream mode (aie_layout.h): out = (key, counter high word, tag lo, tag hi) */
 void aie_oracle_layout_stream(const uint32_t* st, uint32_t* out) {

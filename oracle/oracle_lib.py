@@ -30,9 +30,9 @@ def lib():
     if _LIB is None:
         path = os.path.join(HERE, "_build", "libaie_oracle.so")
         src = os.path.join(HERE, "aie_oracle.c")
-        hdr = os.path.join(ROOT, "ai-economist_amd", "csrc", "aie_layout.h")
-        if (not os.path.exists(path) or os.path.getmtime(path) < os.path.getmtime(src)
-                or os.path.getmtime(path) < os.path.getmtime(hdr)):
+        deps = [src] + [os.path.join(ROOT, "ai-economist_amd", "csrc", h)
+                        for h in ("aie_layout.h", "aie_layout_build.h", "aie_trainer_math.h")]
+        if not os.path.exists(path) or any(os.path.getmtime(path) < os.path.getmtime(d) for d in deps):
             path = build()
         L = C.CDLL(path)
         vp = C.c_void_p

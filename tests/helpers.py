@@ -452,7 +452,7 @@ FAMILY_CASES = {
 }
 
 
-# ---- the policy sampler (csrc/aie_layout.h: aie_sampler_exp, aie_sampler_entry_rng, the scan's order), transcribed in
+# ---- the policy sampler (csrc/aie_trainer_math.h: aie_sampler_exp, aie_sampler_entry_rng, the scan's order), transcribed in
 # plain Python: IEEE double multiplies and adds in the header's order, nothing else ----
 def _f32_nearest(fr):
     """The float32 nearest to the exact rational `fr`, ties to even (one rounding, as a hardware fma rounds)."""

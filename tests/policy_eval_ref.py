@@ -1,4 +1,4 @@
-"""Python transcription of the policy evaluation (csrc/aie_layout.h: aie_sampler_logf, aie_policy_row_stats / _logp /
+"""Python transcription of the policy evaluation (csrc/aie_trainer_math.h: aie_sampler_logf, aie_policy_row_stats / _logp /
 _backward): log-probability, entropy and logit gradient of one action slot under its mask, float32 operation for
 operation.  Two forms of the same arithmetic:
 

@@ -1,5 +1,5 @@
 """The policy network's forward pass (include/aie.h: aie_policy_mlp_forward), transcribed in numpy from the contract in
-csrc/aie_layout.h's comment -- independent of the header's code:
+csrc/aie_trainer_math.h's comment -- independent of the header's code:
 
     chain(c; a, w) = acc, with acc = c and then acc = fmaf(a[k], w[k], acc) for k = 0, 1, ... ascending, all float32
     relu(v) = v > 0 ? v : 0

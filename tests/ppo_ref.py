@@ -1,4 +1,4 @@
-"""Python transcription of the PPO loss (csrc/aie_layout.h: the comment above aie_ppo_actor_terms), written from that
+"""Python transcription of the PPO loss (csrc/aie_trainer_math.h: the comment above aie_ppo_actor_terms), written from that
 comment: float32 operation for operation, vectorised over actors (numpy rounds every float32 operation on its own).
 
   * slot terms (logp_s, H_s, the slots' gradient rows) come from policy_eval_ref.rows_forward / rows_backward, which

@@ -2,7 +2,10 @@
 unit that compiles on its own (it includes what it uses: no file relies on its place in aie_capi.hip's include block),
 no kernel file outside the gather-trade-build family is compiled from gather-trade-build code, the family's four headers
 of device functions include one another in one direction only (state <- components, state <- observe, the layout
-generator beside them, and none of them the kernel file), the cache key of each
+generator beside them, and none of them the kernel file), the layout header is cut in three -- what a kernel reads
+(aie_layout.h), the host's builders of the parameter block (aie_layout_build.h: no kernel file is compiled from it) and the
+trainer side's arithmetic (aie_trainer_math.h: no step-side file and neither run-time unit is compiled from it) -- each
+of which compiles on its own as C99 and as HIP, the cache key of each
 run-time unit (aie_jit.h: kSources + kSourcesOse / kSourcesGtb) names exactly the project files that unit is compiled
 from, and the library's staleness hash (_build.source_files) reads every project file aie_capi.hip is compiled from.
 The compiler's own preprocessor says what a unit includes (the `# n "file"` line markers); nothing is launched."""
@@ -24,6 +27,10 @@ KERNEL_FILES = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, 
 GTB_HEADERS = ["aie_gtb_state.h", "aie_gtb_components.h", "aie_gtb_observe.h", "aie_gtb_layoutgen.h"]
 GTB_FILES = ["aie_kernels.hip"] + GTB_HEADERS
 DEVICE_HEADERS = ["aie_device.h"] + GTB_HEADERS
+# the layout header and the two cut out of it: only aie_layout.h is in a specialisation's key (aie_jit.h: kSources)
+LAYOUT_HEADERS = ["aie_layout.h", "aie_layout_build.h", "aie_trainer_math.h"]
+NOT_KEYED = ["aie_layout_build.h", "aie_trainer_math.h"]
+STEP_SIDE = ["aie_kernels.hip", "aie_kernels_ose.hip", "aie_kernels_covid.hip", "aie_kernels_saez.hip"] + DEVICE_HEADERS
 # aie_jit_image.h as aie_jit.h writes it per configuration; the preprocessor does not care for the image's size
 STUB_IMAGE = ("#pragma once\n#define AIE_N_SPECS 1\ntemplate <int K> struct aie_spec_image;\n"
               "alignas(16) static constexpr unsigned char aie_jit_bytes[1] = {0};\n"
@@ -73,6 +80,50 @@ def test_gather_trade_build_headers_depend_one_way(name, unseen):
     assert not seen & set(unseen + ["aie_kernels.hip"]), sorted(seen)
 
 
+@pytest.mark.parametrize("name", STEP_SIDE)
+def test_step_side_sees_neither_the_builders_nor_the_trainer_arithmetic(name):
+    assert os.path.exists(os.path.join(CSRC, name)) and all(os.path.exists(os.path.join(CSRC, n)) for n in NOT_KEYED)
+    seen = {os.path.basename(f) for f in _project_files(os.path.join(CSRC, name))}
+    assert "aie_layout.h" in seen and not seen & set(NOT_KEYED), sorted(seen)
+
+
+@pytest.mark.parametrize("name", KERNEL_FILES)
+def test_no_kernel_file_sees_the_host_builders(name):
+    """... and the trainer side's kernel files are the ones compiled from its arithmetic."""
+    seen = {os.path.basename(f) for f in _project_files(os.path.join(CSRC, name))}
+    assert "aie_layout.h" in seen and "aie_layout_build.h" not in seen, sorted(seen)
+    assert ("aie_trainer_math.h" in seen) == (name not in STEP_SIDE), sorted(seen)
+
+
+@pytest.mark.parametrize("lang", ["c99", "hip"])
+@pytest.mark.parametrize("name", LAYOUT_HEADERS)
+def test_each_layout_header_compiles_on_its_own(name, lang):
+    """As C99 with the host C compiler, and as HIP (host and device passes: aie_layout_build.h is host code)."""
+    if lang == "c99":
+        # (aie_layout.h really alone: without what follows it for host C of before the cut, see the next test)
+        cmd = ["gcc", "-std=c99", "-fsyntax-only", "-DAIE_LAYOUT_H_ONLY", "-I" + CSRC, "-I" + INCLUDE, "-x", "c"]
+    else:
+        cmd = [a for a in _hipcc() if a != "--cuda-device-only"] + ["-fsyntax-only", "-x", "hip"]
+    r = subprocess.run(cmd + [os.path.join(CSRC, name)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+
+
+def test_host_c_code_of_before_the_cut_still_compiles(tmp_path):
+    """The suite and the restatement of the commit before the cut are run against this library unchanged; their C
+    includes aie_layout.h alone (the plan shim: aie_trainer_plan.h alone) and calls the builders and the trainer
+    helpers, so for host C that reaches aie_layout.h without having named the builders the other two follow (its last
+    lines).  Behind aie_layout_build.h nothing follows: the spec generator compiles no trainer arithmetic."""
+    uses = "void* uses[] = {(void*)aie_build_params, (void*)aie_mlp_row, (void*)aie_gae_step};\n"
+    gcc = ["gcc", "-std=c99", "-fsyntax-only", "-I" + CSRC, "-I" + INCLUDE]
+    for head, ok in (('#include "aie_layout.h"\n', True),
+                     ('#include "aie_trainer_plan.h"\n', True),
+                     ('#include "aie_layout_build.h"\n#include "aie_layout.h"\n', False)):
+        src = tmp_path / "uses.c"
+        src.write_text(head + uses)
+        r = subprocess.run(gcc + [str(src)], capture_output=True, text=True)
+        assert (r.returncode == 0) == ok, (head, r.stderr[-2000:])
+
+
 def _jit_listed(name):
     """One of csrc/aie_jit.h's lists of file names (kSources, kSourcesOse, kSourcesGtb)."""
     with open(os.path.join(CSRC, "aie_jit.h")) as f:
@@ -102,6 +153,8 @@ def test_specialisation_cache_key_covers_what_it_compiles(tmp_path):
         keyed = {os.path.realpath(os.path.join(CSRC, s)) for s in listed} | {os.path.realpath(os.path.join(INCLUDE, "aie.h"))}
         assert len(listed) == len(set(listed)), listed
         assert compiled == keyed, (which, sorted(compiled - keyed), sorted(keyed - compiled))
+        # the builders and the trainer arithmetic are not keyed because no unit is compiled from them
+        assert "aie_layout.h" in listed and not {os.path.basename(f) for f in compiled} & set(NOT_KEYED), sorted(compiled)
     # the unit's own step / reset kernel files only: an edit to a trainer-side kernel file, or to the other scenario
     # family's, leaves a unit's cached code objects valid
     assert sorted(s for s in units["ose"][0] if s.endswith(".hip")) == ["aie_kernels_ose.hip"], units["ose"][0]

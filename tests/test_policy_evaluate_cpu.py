@@ -1,4 +1,4 @@
-"""Policy evaluation, CPU side (csrc/aie_layout.h: aie_sampler_logf, aie_policy_row_stats / _logp / _backward -- the twin
+"""Policy evaluation, CPU side (csrc/aie_trainer_math.h: aie_sampler_logf, aie_policy_row_stats / _logp / _backward -- the twin
 of aie_sample_policy_actions_logp, aie_policy_evaluate and aie_policy_evaluate_backward):
 
   * bits: the header, compiled here with the host C compiler, against the Python transcription (tests/policy_eval_ref.py),
@@ -35,7 +35,7 @@ CSRC = os.path.join(ROOT, "ai-economist_amd", "csrc")
 f32 = np.float32
 
 SHIM = r"""
-#include "aie_layout.h"
+#include "aie_trainer_math.h"
 void shim_logf(const float* T, long n, float* out) { for (long i = 0; i < n; ++i) out[i] = aie_sampler_logf(T[i]); }
 void shim_rows(const float* x, const float* mask, long R, int len, const int* a, const float* gl, const float* gh,
                float* logp, float* H, float* g, float* mts) {

@@ -1,4 +1,4 @@
-"""The policy network's backward pass, CPU side (csrc/aie_layout.h: aie_mlp_row_backward, aie_mlp_grad_entry -- the twins
+"""The policy network's backward pass, CPU side (csrc/aie_trainer_math.h: aie_mlp_row_backward, aie_mlp_grad_entry -- the twins
 of aie_policy_mlp_backward's kernels):
 
   * values: the header's helpers, compiled here with the host C compiler, == the numpy transcription
@@ -28,7 +28,7 @@ f32, f64 = np.float32, np.float64
 
 SHIM = r"""
 #include <stdlib.h>
-#include "aie_layout.h"
+#include "aie_trainer_math.h"
 int shim_seg(void) { return AIE_MLP_BWD_SEG; }
 void shim_mlp_backward(const float* x, long x_ld, long rows, int F, int H, int M, const float* w1, const float* b1, const float* w2,
                        const float* b2, const float* w3, const float* wv, const float* g_logits, const float* g_values, float* gw1,

@@ -1,4 +1,4 @@
-"""The policy network's forward pass, CPU side (csrc/aie_layout.h: aie_mlp_row -- the twin of aie_policy_mlp_forward):
+"""The policy network's forward pass, CPU side (csrc/aie_trainer_math.h: aie_mlp_row -- the twin of aie_policy_mlp_forward):
 
   * the fma emulation of tests/policy_mlp_ref.py against the C library's fmaf on 10^5 random triples, halfway cases
     (c = -a b rounded, plus or minus one ulp) among them;
@@ -25,7 +25,7 @@ f32 = np.float32
 
 SHIM = r"""
 #include <stdlib.h>
-#include "aie_layout.h"
+#include "aie_trainer_math.h"
 void shim_fmaf(const float* a, const float* b, const float* c, long n, float* out) {
   for (long i = 0; i < n; ++i) out[i] = fmaf(a[i], b[i], c[i]);
 }

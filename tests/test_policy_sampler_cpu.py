@@ -1,4 +1,4 @@
-"""aie_sample_policy_actions, CPU side: the sampler's building blocks (csrc/aie_layout.h: aie_sampler_expf,
+"""aie_sample_policy_actions, CPU side: the sampler's building blocks (csrc/aie_trainer_math.h: aie_sampler_expf,
 aie_sampler_entry_rng, the fixed prefix-sum order) against their Python transcription (tests/helpers.py) and libm, and --
 through oracle/'s restatement, which the -m gpu tests hold the kernel to entry for entry -- that the sampler draws from
 softmax(logits) restricted to the action mask (what a trainer expects of it: base_env.py:141-145,

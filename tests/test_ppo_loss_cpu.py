@@ -1,4 +1,4 @@
-"""The PPO loss, CPU side (csrc/aie_layout.h: aie_ppo_actor_terms, aie_ppo_value_terms, aie_ppo_advantage,
+"""The PPO loss, CPU side (csrc/aie_trainer_math.h: aie_ppo_actor_terms, aie_ppo_value_terms, aie_ppo_advantage,
 aie_ppo_finish_stats over aie_policy_row_stats / _logp / _backward -- the twin of aie_ppo_loss):
 
   * bits: the header's helpers, compiled here with the host C compiler and strung together per actor as the header's
@@ -39,7 +39,7 @@ f32 = np.float32
 
 # The class loss from the header's helpers, actor by actor (sums in actor order: the device's order is its own).
 SHIM = r"""
-#include "aie_layout.h"
+#include "aie_trainer_math.h"
 void shim_ppo(const float* x, const float* mask, long N, int W, int w, const int* row_off, const int* row_len, const int* act,
               const float* lp_old, const float* adv, const float* moments, const float* v, const float* v_old, const float* ret,
               float clip, float vf_clip, float vf_coef, float ent_coef, float* terms, float* grad, float* grad_v, float* stats) {

@@ -3,7 +3,7 @@ entry points check, hand to their kernels and launch, without a device.  Paramet
 C2 configuration (4 agents of 50 logits, a planner of seven 22-entry rows) and COVID (51 agents of 11 logits with collated
 masks, a planner of 21).  Operands are fake, aligned addresses: a plan dereferences nothing.
 
-Every expectation is written out here from the formulas include/aie.h and csrc/aie_layout.h document, never taken from the
+Every expectation is written out here from the formulas include/aie.h and csrc/aie_trainer_math.h document, never taken from the
 plan: the MLP groups' geometry and the backward's workspace layout, the PPO loss's wavefronts and workspace, the
 evaluator's work items, the GAE grid, the trajectory copy's width, and -- for every refusal include/aie.h documents -- the
 code, a message that names the function, silence with err == NULL, and which refusal wins when two apply.
@@ -20,7 +20,7 @@ from helpers import C2, ROOT, load_covid_golden, make_env
 
 CSRC = os.path.join(ROOT, "ai-economist_amd", "csrc")
 OK, INVALID, UNSUPPORTED = 0, -1, -5
-TILE, CHUNK, SEG, MAX_WAVES, RECORD = 32, 256, 256, 8192, 16  # aie_layout.h / aie.h; checked against the header below
+TILE, CHUNK, SEG, MAX_WAVES, RECORD = 32, 256, 256, 8192, 16  # aie_trainer_math.h / aie.h; checked against the header below
 vp, i32, u32, i64, f32 = C.c_void_p, C.c_int32, C.c_uint32, C.c_int64, C.c_float
 
 
@@ -31,7 +31,7 @@ def _struct(name, *groups):
     return type(name, (C.Structure,), {"_fields_": fields})
 
 
-# ---- mirrors of the kernel arguments (aie_layout.h) and of the plans; the shim's sizeof guards them ----
+# ---- mirrors of the kernel arguments (aie_trainer_math.h) and of the plans; the shim's sizeof guards them ----
 EvalGroup = _struct("EvalGroup", (vp, "lg mk act g_logp g_ent logp ent grad"), (u32, "lg_bstride mk_bstride"),
                     (i32, "len lrs mrs mks lsh rows items generic"))
 EvalArgs = _struct("EvalArgs", (EvalGroup, "agents planner"), (vp, "params"), (u32, "B items"), (i32, "act_a_width ragged"))
@@ -58,6 +58,7 @@ PLANS = [EvalPlan, GaePlan, PpoPlan, MlpFwdPlan, MlpBwdPlan, TrajPlan]
 
 SHIM = r"""
 #include <stdlib.h>
+#include "aie_layout_build.h"
 #include "aie_trainer_plan.h"
 typedef const void* cv;
 void* shim_params(const aie_config* c, char* err, int n) {
@@ -229,7 +230,7 @@ def grad_class(S, F, H, M, value=True, **kw):
 
 
 def want_group(F, H, M, rows):
-    """aie_layout.h: the two LDS images' row strides and the row tiles of a class."""
+    """aie_trainer_math.h: the two LDS images' row strides and the row tiles of a class."""
     return dict(F=F, H=H, M=M, rows=rows, lds_a=max(min(pad4(F), CHUNK), H) + 2, lds_h=H + 2, blocks=ceil(rows, TILE))
 
 
@@ -278,7 +279,7 @@ def test_mlp_class_fill_forward_and_backward_agree(S, cfg, n, shape):
 
 
 def want_backward(F, H, M, v, rows):
-    """include/aie.h: the workspace; aie_layout.h: the partials' three blocks [(K + 1), N] and the second launch's items (four
+    """include/aie.h: the workspace; aie_trainer_math.h: the partials' three blocks [(K + 1), N] and the second launch's items (four
     16-row bands by up to four 16-column tiles, per layer and segment)."""
     nseg = ceil(rows, SEG)
     N3 = M + v

@@ -1,4 +1,4 @@
-"""Generalised advantage estimation, CPU side: the header's aie_gae_step (csrc/aie_layout.h -- what aie_gae's kernel calls),
+"""Generalised advantage estimation, CPU side: the header's aie_gae_step (csrc/aie_trainer_math.h -- what aie_gae's kernel calls),
 compiled here with the host C compiler (contraction off) and run down columns, against the plain NumPy float32 loop
 (tests/gae_ref.py), bit for bit; and the two new exports of the built library with their ctypes bindings."""
 import ctypes
@@ -16,7 +16,7 @@ from helpers import ROOT
 CSRC = os.path.join(ROOT, "ai-economist_amd", "csrc")
 
 SHIM = r"""
-#include "aie_layout.h"
+#include "aie_trainer_math.h"
 /* columns side by side: r, done [T][C], v [T + 1][C] -> adv, ret [T][C] */
 void shim_gae(const float* r, const float* done, const float* v, long T, long C, float gamma, float lambda, float* adv, float* ret) {
   const float gl = aie_gae_gl(gamma, lambda);
