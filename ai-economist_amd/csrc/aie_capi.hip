@@ -147,6 +147,10 @@ __global__ void aie_set_flags_kernel(const aie_params P, uint8_t* __restrict__ a
   uint32_t* w = reinterpret_cast<uint32_t*>(arena + P.a_records + (int64_t)e * P.rec_bytes + P.o_cells) + cell;
   const uint32_t fl = flags[shared ? cell : q];
   *w = (*w & 0x00ffffffu) | (fl << 24);
+  if (P.o_cells8) {  // the cell's byte follows its word (aie_layout.h: o_cells8)
+    uint8_t* b = arena + P.a_records + (int64_t)e * P.rec_bytes + P.o_cells8 + cell;
+    *b = (uint8_t)((*b & ~7u) | (fl & 7u));
+  }
 }
 
 // The replicas' source-double lists (record fields o_src_n / o_src_list, aie_layout.h) from the cells' flag bytes in

@@ -1,8 +1,9 @@
 // aie_gtb_state.h -- the gather-trade-build family's per-replica state helpers: the world helpers (can_agent_occupy,
-// log_event, agent_can_build), the agents' registers (Agents, agents_load / agents_store, hist_bit, decode_actions) and
-// the change log of one step (dirty_*, store_record_step).  The foot of the family's headers: it includes aie_device.h
-// only, and aie_gtb_components.h and aie_gtb_observe.h both include it.  No kernel.  Part of the gather-trade-build
-// cache key (aie_jit.h: kSourcesGtb).
+// log_event, agent_can_build), the agents' registers (Agents, agents_load / agents_store, hist_bit, decode_actions), the
+// change log of one step (dirty_*) and the record's way in and out of a step with the cells' byte plane
+// (load_record_step, store_record_step).  The foot of the family's headers: it includes aie_device.h only, and
+// aie_gtb_components.h and aie_gtb_observe.h both include it.  No kernel.  Part of the gather-trade-build cache key
+// (aie_jit.h: kSourcesGtb).
 #pragma once
 #include "aie_device.h"
 
@@ -222,11 +223,87 @@ __device__ __forceinline__ void dirty_add_lane(const Ctx& c, int cell) {
 __device__ __forceinline__ void dirty_agent_moved(MTL& m, int i) {
   if (i < 32) m.mv0 |= 1u << i; else m.mv1 |= 1u << (i - 32);
 }
+// ------------------------------------------------------------------------------------
+// The record's way in and out of a step, and the cells' byte plane (aie_layout.h: o_cells8, aie_cell_pack8).
+// ------------------------------------------------------------------------------------
+// Four cells of the plane -> their four words.  Byte-parallel arithmetic on the dword (the four Stone bytes, Wood bytes,
+// owner bytes, flag bytes), then a 4 x 4 byte transpose with v_perm_b32 (selector bytes 0-3: second operand, 4-7: first).
+__device__ __forceinline__ uint4 cells8_expand(uint32_t d) {
+  const uint32_t st = (d >> 3) & 0x01010101u, wd = (d >> 4) & 0x01010101u, fl = d & 0x07070707u;
+  // per byte 0 -> 0xff (no house), k + 1 -> k: the borrow stops at bit 7 of each byte
+  const uint32_t ow = ((((d >> 5) & 0x07070707u) | 0x80808080u) - 0x01010101u) ^ 0x80808080u;
+  const uint32_t sw01 = __builtin_amdgcn_perm(wd, st, 0x05010400u), sw23 = __builtin_amdgcn_perm(wd, st, 0x07030602u);
+  const uint32_t of01 = __builtin_amdgcn_perm(fl, ow, 0x05010400u), of23 = __builtin_amdgcn_perm(fl, ow, 0x07030602u);
+  uint4 w;
+  w.x = __builtin_amdgcn_perm(of01, sw01, 0x05040100u);
+  w.y = __builtin_amdgcn_perm(of01, sw01, 0x07060302u);
+  w.z = __builtin_amdgcn_perm(of23, sw23, 0x05040100u);
+  w.w = __builtin_amdgcn_perm(of23, sw23, 0x07060302u);
+  return w;
+}
+// The step's way in.  The cells are 2.5 of the 4.3 KB image of BASELINE configs[1], and the burst of record loads that
+// every workgroup of a launch starts with is priced by its bytes: where the record has the byte plane, the 16-byte units
+// that hold nothing but cells are not fetched -- plane dword k expands into unit k -- and only the rest of the image
+// comes as it is (the unit the cells share with the next field brings the last H W % 4 words).  The plane holds while
+// obs_valid != 0, which is known once the image is in LDS: load_record_cells is the other case.
+// (A/B on one MI355X, BASELINE configs[1] at 4096 replicas, profiles/cell_plane_ab.txt: with one wait per load, as the
+// word-per-cell copy has them, the plane gains nothing -- 19.97 us per launch, the parent's 19.96 -- however the two waves
+// share it; with the loads below requested together 19.62 us.)
+__device__ __forceinline__ void load_record_step(const Ctx& c, const uint8_t* __restrict__ arena, int wave, int nwaves) {
+  if (!c.P.o_cells8) {
+    MT none;
+    load_record(c, arena, none, wave, nwaves, /*key_wave=*/-1);
+    return;
+  }
+  const uint8_t* g = arena + (int64_t)c.e * c.P.rec_bytes;  // (a_records == 0, see load_record)
+  const uint4* src = reinterpret_cast<const uint4*>(g);
+  const uint32_t* plane = reinterpret_cast<const uint32_t*>(g + c.P.o_cells8);
+  uint4* dst = reinterpret_cast<uint4*>(c.rec);
+  const int nq = rec_lds_bytes(c.P) >> 4, q0 = (4 * c.P.HW) >> 4;  // units [0, q0): cells only (o_cells == 0)
+  // The first wave takes the whole plane: the second has the draw window and the constant tables to fetch behind its
+  // units.  A lane's first unit and its first three plane dwords -- all there is up to 27 x 27 -- are requested together
+  // and waited for once; what a larger world has beyond them follows one by one.
+  const int q = q0 + wave * AIE_NT + c.tid, k0 = wave == 0 ? c.tid : q0;
+  const bool hu = q < nq, h0 = k0 < q0, h1 = k0 + AIE_NT < q0, h2 = k0 + 2 * AIE_NT < q0;
+  uint4 u = {0u, 0u, 0u, 0u};
+  uint32_t d0 = 0u, d1 = 0u, d2 = 0u;
+  if (hu) u = src[q];
+  if (h0) d0 = plane[k0];
+  if (h1) d1 = plane[k0 + AIE_NT];
+  if (h2) d2 = plane[k0 + 2 * AIE_NT];
+  if (hu) dst[q] = u;
+  if (h0) dst[k0] = cells8_expand(d0);
+  if (h1) dst[k0 + AIE_NT] = cells8_expand(d1);
+  if (h2) dst[k0 + 2 * AIE_NT] = cells8_expand(d2);
+  for (int qq = q + nwaves * AIE_NT; qq < nq; qq += nwaves * AIE_NT) dst[qq] = src[qq];
+  for (int k = k0 + 3 * AIE_NT; k < q0; k += AIE_NT) dst[k] = cells8_expand(plane[k]);
+}
+// ... and the cell units themselves, over what the plane gave: the launch found obs_valid == 0, so something outside the
+// kernels may have edited the words and the plane is not to be trusted.  Such a launch writes the whole plane on its
+// way out (step_body starts its change log past AIE_DIRTY_CAP).
+__device__ __forceinline__ void load_record_cells(const Ctx& c, const uint8_t* __restrict__ arena, int wave, int nwaves) {
+  const uint4* src = reinterpret_cast<const uint4*>(arena + (int64_t)c.e * c.P.rec_bytes);
+  uint4* dst = reinterpret_cast<uint4*>(c.rec);
+  const int q0 = (4 * c.P.HW) >> 4;
+  for (int q = wave * AIE_NT + c.tid; q < q0; q += nwaves * AIE_NT) dst[q] = src[q];
+}
+// the whole plane (padding: zero) from the LDS image's words
+__device__ __forceinline__ void store_cells8(const Ctx& c, uint8_t* __restrict__ arena, int wave = 0, int nwaves = 1) {
+  uint32_t* plane = reinterpret_cast<uint32_t*>(arena + (int64_t)c.e * c.P.rec_bytes + c.P.o_cells8);
+  const int nd = ((c.P.HW + 15) >> 4) << 2;
+  for (int k = wave * AIE_NT + c.tid; k < nd; k += nwaves * AIE_NT) {
+    uint32_t d = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (4 * k + j < c.P.HW) d |= aie_cell_pack8(R_CELLS(c)[4 * k + j]) << (8 * j);
+    plane[k] = d;
+  }
+}
 // The step's way out (round 6).  A step changes a handful of the H W map cells -- the ones its change log lists for the
 // in-place map observations (dirty_*: every cell whose word or occupant changed) -- so the 16-byte units that hold
-// nothing but cells stay as they are in HBM and the listed cells go out one word per lane: 2.4 of the 4.2 KB image of
-// BASELINE configs[1] are not written.  A log overflow writes everything.  (The generator's rows left right behind the
-// regeneration: store_generator_rows.)
+// nothing but cells stay as they are in HBM and the listed cells go out one word per lane, each with its byte of the
+// plane: 2.4 of the 4.2 KB image of BASELINE configs[1] are not written.  A log overflow writes everything, the plane
+// included.  (The generator's rows left right behind the regeneration: store_generator_rows.)
 __device__ __forceinline__ void store_record_step(const Ctx& c, uint8_t* __restrict__ arena, int wave, int nwaves) {
   uint8_t* g = arena + (int64_t)c.e * c.P.rec_bytes;
   uint4* dst = reinterpret_cast<uint4*>(g);
@@ -237,8 +314,11 @@ __device__ __forceinline__ void store_record_step(const Ctx& c, uint8_t* __restr
   for (int q = q0 + wave * AIE_NT + c.tid; q < nq; q += nwaves * AIE_NT) dst[q] = src[q];
   if (wave == nwaves - 1 && q0 > 0 && c.tid < cnt) {
     const int cell = (int)dirty_list(c)[c.tid];
-    reinterpret_cast<uint32_t*>(g + c.P.o_cells)[cell] = R_CELLS(c)[cell];
+    const uint32_t w = R_CELLS(c)[cell];
+    reinterpret_cast<uint32_t*>(g + c.P.o_cells)[cell] = w;
+    if (c.P.o_cells8) (g + c.P.o_cells8)[cell] = (uint8_t)aie_cell_pack8(w);
   }
+  if (c.P.o_cells8 && q0 == 0) store_cells8(c, arena, wave, nwaves);
 }
 
 }  // namespace aie

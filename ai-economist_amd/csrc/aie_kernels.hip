@@ -44,7 +44,8 @@
 // components in list order, scenario_step, observations, masks, rewards, done.
 //
 // A replica is a workgroup of TWO wavefronts sharing the LDS record.
-//   both   record HBM -> LDS (alternate 16-byte units)  ||  wave 1 also: the next 128+ tempered MT19937 words ->
+//   both   record HBM -> LDS (alternate 16-byte units;  ||
+//          cells: a byte each, expanded -- o_cells8)   ||  wave 1 also: the next 128+ tempered MT19937 words ->
 //                                                        ||         the LDS draw window (rows fetched from HBM)
 //   wave 0 action decode, price-history decay          ||  wave 1 occupancy map
 //   wave 0 components (draws read the draw window)     ||  wave 1 generator rows HBM -> registers, next step's
@@ -179,12 +180,21 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
     // -- the loop below comes out as load, wait, LDS write per unit, behind decode_actions' two load-wait-decode rounds --
     // made the launch SLOWER, 22.5 -> 23.5 us, and so did milder orders (both action loads first: 22.7; the record ahead of
     // the decode: 22.9): 4096 workgroups start together, and what their first microseconds are short of is the memory
-    // system's capacity for requests, not patience -- the loop's own pace spreads them)
-    MT none;
-    load_record(c, arena, none, 0, 2, /*key_wave=*/-1);
+    // system's capacity for requests, not patience -- the loop's own pace spreads them.  That was the word-per-cell image
+    // of 4.3 KB; with the cells' byte plane the image is 2.5 KB and load_record_step's loads, requested together, are
+    // 0.35 us FASTER than with a wait each: aie_gtb_state.h)
+    load_record_step(c, arena, 0, 2);
     __syncthreads();  // (2) the record is in LDS
+    // (the cells came as bytes, aie_gtb_state.h: load_record_step -- unless something outside the kernels touched the
+    // state: then both waves fetch the words, and a change log that starts out overflowed makes the way out write every
+    // cell and the whole plane.  Uniform over the workgroup: nobody writes obs_valid before barrier (4).)
+    const bool cells_stale = P.o_cells8 != 0 && uni(*R_I32(c, o_obs_valid)) == 0;
+    if (cells_stale) {
+      load_record_cells(c, arena, 0, 2);
+      __syncthreads();
+    }
     if (TRACE && R.dev_trace && c.tid == 0) R.dev_trace[12 * blockIdx.x + 8] = wall_clock64();
-    MTL ml{draw_w, 0, 0u, -AIE_MT_N, 0, 0u, 0u, 0, 0, 0, FAST ? reinterpret_cast<uint32_t*>(c.rec + P.o_mt) : gkey, draw_cap, FAST};
+    MTL ml{draw_w, 0, 0u, -AIE_MT_N, cells_stale ? AIE_DIRTY_CAP + 1 : 0, 0u, 0u, 0, 0, 0, FAST ? reinterpret_cast<uint32_t*>(c.rec + P.o_mt) : gkey, draw_cap, FAST};
     ml.pos = ml.base = uni(*R_I32(c, o_mt_pos));
     ml.avail = ml.cap < AIE_MT_N - ml.pos ? ml.cap : AIE_MT_N - ml.pos;  // what the second wave's draw_window_publish left
     if (FAST) {  // (draw_window_publish_fast: whole pairs, one word less when the position is odd)
@@ -268,7 +278,7 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
     MT m;
     mt_init(m, P);
     const int gpos = *reinterpret_cast<const int32_t*>(grec + P.o_mt_pos);
-    load_record(c, arena, m, 1, 2, /*key_wave=*/-1);
+    load_record_step(c, arena, 1, 2);
     // behind its share of the copy: the words the components will draw -> the LDS draw window (two or three rows of the
     // generator's state, fetched from HBM; the state itself follows while the components run)
     if (skip & AIE_DEV_SKIP_DRAW_WINDOW) {}  // (development: the load phase without the draw window)
@@ -282,6 +292,10 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
       for (int q = c.tid; q < P.MA; q += AIE_NT) const_cast<uint32_t*>(c.mtab)[q] = P.mask_test[q];
     }
     __syncthreads();  // (2)
+    if (P.o_cells8 != 0 && uni(*R_I32(c, o_obs_valid)) == 0) {  // (the first wave's cells_stale)
+      load_record_cells(c, arena, 1, 2);
+      __syncthreads();
+    }
     if (!(skip & AIE_DEV_SKIP_LOCMAP)) rebuild_locmap(c);
     __syncthreads();  // (3)
     // nothing to do until the components are done but the next step's random actions
@@ -654,6 +668,7 @@ __device__ __forceinline__ void reset_body(const aie_params* __restrict__ params
   }
   __syncthreads();
   store_record(c, arena, m);
+  if (P.o_cells8) store_cells8(c, arena);  // the plane goes with the words it is derived from
 }
 }  // namespace aie
 

@@ -221,7 +221,13 @@ typedef struct aie_params {
    * result); behind every reset launch a one-thread kernel decides whether enough layouts were consumed for a refill
    * launch to pay (its duration is that of the slowest replica, however many it draws). */
   int64_t a_layout_stage, a_layout_tag, a_layout_ctl;
-  int32_t layout_stage_stride, layout_pad_;
+  int32_t layout_stage_stride;
+  int32_t o_cells8;      /* record: u8 [H*W] padded to 16, tensor "cells_packed": one byte per map cell (aie_cell_pack8,
+                          * below), derived from o_cells and kept beside it by the reset and step kernels, so that a step
+                          * fetches a byte per cell on its way in and expands it into the LDS image's words.  Holds
+                          * WHENEVER obs_valid != 0; a step that finds obs_valid == 0 reads the words and rewrites the
+                          * plane.  Behind the generator's state like o_src_list, i.e. outside the LDS image.  0 = absent
+                          * (aie__cell_plane: the byte cannot hold the configuration's cells) */
   int64_t a_src_list;    /* shared, fixed layouts with shared_layout only (aie__shared_src_list): int32 count (16 B), then
                           * uint16 [AIE_SRC_CAP]: the regeneration draws that target a source block (double d of a step's
                           * 2 H W np.random.rand values: Wood cell d, or Stone cell d - H W), derived once by
@@ -461,6 +467,11 @@ static inline int aie__shared_src_list(const aie_config* c) {
 static inline int aie__record_src_list(const aie_config* c) {
   return c->scenario == AIE_SCN_GTB && !(aie__shared_src_list(c) && c->rng_mode == AIE_RNG_FAST);
 }
+/* Whether a map cell fits the byte of aie_cell_pack8 (record field o_cells8): Stone and Wood are 0 or 1 and the owner is
+ * one of at most 7 agents.  Everybody else keeps the word-per-cell way in and the record's bytes as they were. */
+static inline int aie__cell_plane(const aie_config* c) {
+  return c->scenario == AIE_SCN_GTB && c->max_health[0] == 1 && c->max_health[1] == 1 && c->n_agents <= 7;
+}
 /* words of generator state in a replica's record ("mt"): MT19937's key, or (key32, block number, salt, 0) of the
  * counter stream (include/aie.h: AIE_RNG_FAST) */
 static inline int32_t aie__rng_state_words(const aie_config* c) { return c->rng_mode == AIE_RNG_FAST ? 4 : AIE_MT_N; }
@@ -549,6 +560,15 @@ AIE_HD static inline double aie_annealed_tax_limit(int completions, double warmu
 #define AIE_CELL_FLAGS(w) (((w) >> 24) & 0xffu)
 #define AIE_CELL_PACK(st, wd, own, fl) \
   ((uint32_t)(st) | ((uint32_t)(wd) << 8) | (((uint32_t)(own) & 0xffu) << 16) | ((uint32_t)(fl) << 24))
+
+/* ... and its byte (o_cells8, where aie__cell_plane holds): bits 0-2 the flag byte, bit 3 Stone, bit 4 Wood, bits 5-7 the
+ * owner -- 0 none (0xff in the word), k + 1 agent k.  unpack8(pack8(w)) == w for every word such a configuration holds. */
+AIE_HD static inline uint32_t aie_cell_pack8(uint32_t w) {
+  return (AIE_CELL_FLAGS(w) & 7u) | ((w & 1u) << 3) | (((w >> 8) & 1u) << 4) | (((((w >> 16) & 0xffu) + 1u) & 7u) << 5);
+}
+AIE_HD static inline uint32_t aie_cell_unpack8(uint32_t b) {
+  return AIE_CELL_PACK((b >> 3) & 1u, (b >> 4) & 1u, (b >> 5) - 1u, b & 7u);
+}
 
 /* order word packing: agent | price << 8 | lifetime << 16 */
 #define AIE_ORD_AGENT(o) ((o) & 0xff)

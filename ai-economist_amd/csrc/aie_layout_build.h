@@ -877,6 +877,7 @@ static inline int aie_build_params(const aie_config* c, aie_params* p, aie_tenso
     p->o_src_n = aie__rec(&cur, 16, 16);
     p->o_src_list = aie__rec(&cur, 2 * AIE_SRC_CAP, 16);
   }
+  p->o_cells8 = aie__cell_plane(c) ? aie__rec(&cur, (int32_t)aie__align(HW, 16), 16) : 0;  /* (likewise outside the image) */
   p->rec_bytes = (int32_t)aie__align(cur, 16);
 
   /* ---- arena ------------------------------------------------------------------- */
@@ -909,7 +910,6 @@ static inline int aie_build_params(const aie_config* c, aie_params* p, aie_tenso
   p->a_layout_prob = a;
   if (c->layout_gen != AIE_LAYOUT_FIXED) a = aie__align(a + (int64_t)AIE_N_RES * HW * 8, 256);
   p->layout_stage_stride = (HW + 15) / 16 * 16;
-  p->layout_pad_ = 0;
   p->a_layout_stage = p->a_layout_tag = p->a_layout_ctl = a;
   if (aie__layout_staged(c)) {
     p->a_layout_stage = a; a = aie__align(a + E * p->layout_stage_stride, 256);
@@ -984,6 +984,7 @@ static inline int aie_build_params(const aie_config* c, aie_params* p, aie_tenso
       REC("regen_src_n", AIE_I32, p->o_src_n, 0, 0, 0, 0);
       REC("regen_src_list", AIE_I16, p->o_src_list, 1, AIE_SRC_CAP, 0, 0);
     }
+    if (p->o_cells8) REC("cells_packed", AIE_U8, p->o_cells8, 2, p->H, p->W, 0);
     REC("mt", AIE_U32, p->o_mt, 1, aie__rng_state_words(&p->c), 0, 0);
     REC("mt_pos", AIE_I32, p->o_mt_pos, 0, 0, 0, 0);
     REC("mt_has_gauss", AIE_I32, p->o_mt_has_gauss, 0, 0, 0, 0);
