@@ -2,7 +2,7 @@
 
 Only plain C types cross this boundary: pointers, sizes, ints, doubles.  torch is used
 by env.py (the environment's calls) and _trainer_ops.py (the trainer operators' calls and
-their argument structures: AieTrajSegment, AiePpoClass, AieMlpClass, AieMlpGradClass)
+their argument structures: AieTrajSegment, AiePpoClass, AieMlpClass, AieMlpGradClass, AieOptGroup)
 purely as the owner of device memory / streams.
 """
 import ctypes as C
@@ -192,6 +192,20 @@ class AieMlpGradClass(C.Structure):  # aie_mlp_grad_class
                [(k, C.c_void_p) for k in ("g_logits", "g_values", "gw1", "gb1", "gw2", "gb2", "gw3", "gb3", "gwv", "gbv")]
 
 
+class AieOptTensor(C.Structure):  # aie_opt_tensor
+    _fields_ = [(k, C.c_void_p) for k in ("w", "g", "m", "v")] + [("n", C.c_int64)]
+
+
+class AieOptGroup(C.Structure):  # aie_opt_group
+    _fields_ = [("tensors", C.POINTER(AieOptTensor)), ("n_tensors", C.c_int32)] + \
+               [(k, C.c_float) for k in ("beta1", "beta2", "eps", "max_norm")] + \
+               [(k, C.c_void_p) for k in ("d_lr", "d_state", "d_stats")]
+
+
+OPT_CHUNK = 1024       # AIE_OPT_CHUNK
+OPT_MAX_TENSORS = 16   # AIE_OPT_MAX_TENSORS
+OPT_N_STATS = 4        # AIE_OPT_N_STATS
+OPT_STATE_BYTES = 32   # AIE_OPT_STATE_BYTES
 MLP_BWD_SEG = 256     # AIE_MLP_BWD_SEG
 PPO_N_STATS = 8       # AIE_PPO_N_STATS
 PPO_MAX_WAVES = 8192  # AIE_PPO_MAX_WAVES
@@ -254,6 +268,10 @@ def bind(lib):
     lib.aie_policy_mlp_backward_workspace_bytes.argtypes = [vp, C.c_int64, C.POINTER(AieMlpGradClass), C.POINTER(AieMlpGradClass)]
     lib.aie_policy_mlp_backward.restype = C.c_int
     lib.aie_policy_mlp_backward.argtypes = [vp, C.c_int64, C.POINTER(AieMlpGradClass), C.POINTER(AieMlpGradClass), vp, C.c_int64, vp]
+    lib.aie_adam_workspace_bytes.restype = C.c_int64
+    lib.aie_adam_workspace_bytes.argtypes = [vp, C.POINTER(AieOptGroup), C.POINTER(AieOptGroup)]
+    lib.aie_adam_step.restype = C.c_int
+    lib.aie_adam_step.argtypes = [vp, C.POINTER(AieOptGroup), C.POINTER(AieOptGroup), vp, C.c_int64, vp]
     lib.aie_trajectory_store.restype = C.c_int
     lib.aie_trajectory_store.argtypes = [vp, C.POINTER(AieTrajSegment), C.c_int32, C.c_int32, vp, vp]
     lib.aie_sample_random_actions.restype = C.c_int
@@ -307,6 +325,7 @@ EXPORTED_SYMBOLS = [
     "aie_arena_info", "aie_step_range", "aie_sample_policy_actions_logp", "aie_policy_evaluate", "aie_policy_evaluate_backward",
     "aie_gae", "aie_trajectory_store", "aie_ppo_workspace_bytes", "aie_ppo_loss",
     "aie_policy_mlp_forward", "aie_policy_mlp_backward_workspace_bytes", "aie_policy_mlp_backward",
+    "aie_adam_workspace_bytes", "aie_adam_step",
 ]
 STEP_HEAD, STEP_TAIL, STEP_OBSERVE, STEP_REBASE, STEP_RETAX = 1, 2, 4, 8, 16  # AIE_STEP_*
 STEP_REGEN, STEP_EMIT, STEP_CLOSE = 64, 128, 256  # the end of a step in three parts (scenario hooks run between them)

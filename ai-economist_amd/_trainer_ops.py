@@ -1,5 +1,5 @@
 """The trainer operators of the device backend (env.DeviceBackend inherits TrainerOps): policy evaluation and its backward,
-trajectory storage, GAE, the PPO loss, the policy MLP.  A method checks its operands, hands plain pointers to one C ABI call
+trajectory storage, GAE, the PPO loss, the policy MLP, the optimizer step.  A method checks its operands, hands plain pointers to one C ABI call
 (the library plans and launches: csrc/aie_trainer_plan.h) and returns torch tensors.  Network outputs and the evaluate calls'
 operands are CONVERTED (`.to(...).contiguous()`); stored operands, `out=` tensors and weights are REFUSED unless right."""
 import ctypes as C
@@ -348,3 +348,47 @@ class TrainerOps:
         self._check(self.lib.aie_policy_mlp_backward(self.handle, B, ref(classes[0]), ref(classes[1]), ptr(ws),
                                                      ws.numel() * 4 if ws is not None else 0, self._stream()))
         return res[0], res[1]
+
+    def adam_group(self, tensors, lr, state, stats, betas=(0.9, 0.999), eps=1e-8, max_norm=0.0):
+        """One aie_opt_group for adam_step.  tensors: a sequence of (w, g, m, v), at most _cabi.OPT_MAX_TENSORS, each four
+        contiguous float32 device tensors of one element count; lr: a float32 device tensor of one element; state: an
+        int64 device tensor of _cabi.OPT_STATE_BYTES // 8 elements, zeroed by the caller before the first step; stats: a
+        float32 device tensor of _cabi.OPT_N_STATS elements.  Nothing is converted: a tensor of another dtype, device or
+        layout is an error.  Returns (the structure, what it points at): keep the pair alive while a call may use it."""
+        import torch
+        fn = "adam_step"
+        tensors = [tuple(q) for q in tensors]
+        if not 1 <= len(tensors) <= _cabi.OPT_MAX_TENSORS or any(len(q) != 4 for q in tensors):
+            raise ValueError("%s: a group is 1 .. %d tensors, each (w, g, m, v)" % (fn, _cabi.OPT_MAX_TENSORS))
+        arr = (_cabi.AieOptTensor * len(tensors))()
+        for i, (w, g, m, v) in enumerate(tensors):
+            n = w.numel() if hasattr(w, "numel") else -1
+            for what, t in (("w", w), ("g", g), ("m", m), ("v", v)):
+                operand(fn, "tensor %d's %s" % (i, what), t, torch.float32, self.device, max(n, 1))
+            arr[i] = _cabi.AieOptTensor(ptr(w), ptr(g), ptr(m), ptr(v), n)
+        operand(fn, "lr", lr, torch.float32, self.device, 1)
+        operand(fn, "state", state, torch.int64, self.device, _cabi.OPT_STATE_BYTES // 8)
+        operand(fn, "stats", stats, torch.float32, self.device, _cabi.OPT_N_STATS)
+        group = _cabi.AieOptGroup(tensors=arr, n_tensors=len(tensors), beta1=betas[0], beta2=betas[1], eps=eps, max_norm=max_norm,
+                                  d_lr=ptr(lr), d_state=ptr(state), d_stats=ptr(stats))
+        return group, (arr, tensors, lr, state, stats)
+
+    def adam_workspace_bytes(self, group_a, group_p):
+        """aie_adam_workspace_bytes for two adam_group structures (either None)."""
+        g = [x[0] if isinstance(x, tuple) else x for x in (group_a, group_p)]
+        return int(self.lib.aie_adam_workspace_bytes(self.handle, ref(g[0]), ref(g[1])))
+
+    def adam_step(self, group_a, group_p, workspace):
+        """aie_adam_step: one Adam step under a gradient-norm clip, in place, for the agents' and the planner's parameter
+        group (what adam_group returns; either None) -- TWO launches on the current stream for both groups together,
+        capturable: the step count, the bias-correction products and the learning rate live in device memory, so a replay
+        advances them and a schedule is lr.fill_(x).  workspace: a float64 device tensor of at least
+        adam_workspace_bytes(...) bytes, the call's own until it has run.  The arithmetic contract (the norm's fixed order,
+        every float32 operation rounded on its own, a group with a non-finite norm skipped: two runs give the same bits)
+        is include/aie.h's.  The gradients are neither modified nor zeroed."""
+        import torch
+        g = [x[0] if isinstance(x, tuple) else x for x in (group_a, group_p)]
+        if g[0] is None and g[1] is None:
+            raise ValueError("adam_step: no parameter group")
+        operand("adam_step", "the workspace", workspace, torch.float64, self.device, per=1)
+        self._check(self.lib.aie_adam_step(self.handle, ref(g[0]), ref(g[1]), ptr(workspace), workspace.numel() * 8, self._stream()))

@@ -17,6 +17,7 @@
 #include "aie_kernels_mlp.hip"
 #include "aie_kernels_mlp_bwd.hip"
 #include "aie_kernels_covid.hip"
+#include "aie_kernels_optim.hip"
 #include "aie_jit.h"
 #include "aie_layout_build.h"  // host only: aie_build_params and the tensor table
 #include "aie_trainer_plan.h"  // host only: the trainer calls' plans
@@ -1048,6 +1049,25 @@ int aie_policy_mlp_backward(aie_env* env, int64_t B, const aie_mlp_grad_class* a
   hipLaunchKernelGGL(aie_policy_mlp_bwd_rows_kernel, dim3(p.grid_rows), dim3(p.block), p.lds, s, p.A);
   hipLaunchKernelGGL(aie_policy_mlp_bwd_atd_kernel, dim3(p.grid_atd), dim3(p.block), 0, s, p.A);
   hipLaunchKernelGGL(aie_policy_mlp_bwd_reduce_kernel, dim3(p.grid_reduce), dim3(p.block), 0, s, p.A);
+  return aie_launched(env);
+}
+
+int64_t aie_adam_workspace_bytes(const aie_env* env, const aie_opt_group* agents, const aie_opt_group* planner) {
+  if (!env) return AIE_E_INVALID;
+  aie_adam_plan p;
+  const int rc = aie_plan_adam_groups(agents, planner, nullptr, 0, &p);
+  return rc != AIE_OK ? rc : p.need;
+}
+int aie_adam_step(aie_env* env, const aie_opt_group* agents, const aie_opt_group* planner, void* d_workspace,
+                  int64_t workspace_bytes, void* stream) {
+  if (!env) return AIE_E_INVALID;
+  aie_adam_plan p;
+  if (const int rc = aie_plan_adam(agents, planner, d_workspace, workspace_bytes, env->err, sizeof(env->err), &p)) return rc;
+  if (!p.grid) return AIE_OK;
+  AIE_HIP_CHECK(env, hipSetDevice(env->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(aie_adam_norm_kernel, dim3(p.grid), dim3(p.block), 0, s, p.A);
+  hipLaunchKernelGGL(aie_adam_update_kernel, dim3(p.grid), dim3(p.block), 0, s, p.A);
   return aie_launched(env);
 }
 

@@ -1,12 +1,13 @@
 /*
  * aie_trainer_math.h -- the trainer side's arithmetic, stated once: the policy sampler and evaluator, the PPO loss,
- * generalised advantage estimation and the policy MLP's forward and backward rows, with the kernels' argument records
+ * generalised advantage estimation, the policy MLP's forward and backward rows and the optimizer step (Adam under a
+ * gradient-norm clip), with the kernels' argument records
  * (aie_sampler_args, aie_sampler_check, aie_sampler_args_of).  The long comment below defines the sampler's and the
- * evaluator's operations; the comments above aie_ppo_*, aie_gae_step and aie_mlp_* define the others.
+ * evaluator's operations; the comments above aie_ppo_*, aie_gae_step, aie_mlp_* and aie_opt_* define the others.
  *
  * Plain C99 with AIE_HD (also included from HIP C++): the device kernels, the host plans (aie_trainer_plan.h), the CPU
  * restatement (oracle/aie_oracle.c) and the CPU tests compile the same helpers.  Included by aie_kernels_sampler.hip
- * and aie_kernels_mlp.hip (the roots of the two trainer chains), aie_trainer_plan.h and the oracle -- not by
+ * and aie_kernels_mlp.hip (the roots of the two trainer chains), aie_kernels_optim.hip, aie_trainer_plan.h and the oracle -- not by
  * aie_device.h, so no step or reset kernel is compiled from it and it is in no specialisation cache key (aie_jit.h).
  */
 #ifndef AIE_TRAINER_MATH_H_
@@ -556,6 +557,146 @@ typedef struct aie_mlp_bwd_args {
   aie_mlp_bwd_group agents, planner;
   int32_t reduce_blocks_a;                  /* the third launch: workgroups [0, reduce_blocks_a) are the agents' */
 } aie_mlp_bwd_args;
+/* Adam with gradient-norm clipping (include/aie.h: aie_adam_step), stated once -- the kernels call these helpers,
+ * tests/test_adam_cpu.py compiles them, tests/optim_ref.py transcribes include/aie.h's text.
+ *   aie_opt_chunk_sumsq  one chunk's sum of squares in float64: 256 slots of four consecutive elements each, added ascending
+ *                        from +0, then the butterfly slot[i] += slot[i ^ 2^L], L = 0 .. 7 (the kernel's six cross-lane steps
+ *                        and its four wave sums through LDS: (s0 + s1) + (s2 + s3)).  The product (double)g * (double)g is
+ *                        exact (48 bits), so fusing it into the addition changes nothing;
+ *   aie_opt_scalars      the group's float64 scalars from n2 (its chunks' sums added ascending from +0) and the old state,
+ *                        rounded to float32 once; skipped = n2 is not finite: the new state is the old one;
+ *   aie_opt_element      one element's float32 step, every operation rounded on its own. */
+/* sqrtf is the correctly rounded one on the device too: hipcc's default (-fhip-fp32-correctly-rounded-divide-sqrt), which
+ * the library's build leaves alone; HIP's __fsqrt_rn is the hardware's approximation here, so it is not used */
+#define AIE_OPT_SLOTS (AIE_OPT_CHUNK / 4)
+#if AIE_OPT_SLOTS != 256
+#error "a chunk is 256 slots of four elements: the butterfly has eight levels"
+#endif
+typedef struct aie_opt_state {   /* d_state: AIE_OPT_STATE_BYTES */
+  int64_t t;
+  double p1, p2;                 /* beta1^t, beta2^t (unused while t == 0) */
+  int64_t pad_;
+} aie_opt_state;
+/* (a comparison, false for a NaN and for both infinities -- not the bits through an 8-byte memcpy: on the device memcpy is a
+ * function the compiler specialises on its callers' sizes, and a second size beside aie_sampler_logf's 4 reorders the
+ * instructions of every kernel that inlines that one: profiles/adam_step_isa.txt) */
+AIE_HD static inline int aie_opt_finite(double x) {
+  return fabs(x) <= 1.7976931348623157e308;
+}
+/* a slot's four elements: count = how many of them exist (1 .. 4) */
+AIE_HD static inline double aie_opt_slot_sumsq(const float* g, int count) {
+  double acc = 0.0;
+  for (int k = 0; k < count; ++k) acc += (double)g[k] * (double)g[k];
+  return acc;
+}
+AIE_HD static inline double aie_opt_chunk_sumsq(const float* g, int64_t count) {   /* count: 1 .. AIE_OPT_CHUNK */
+  double slot[AIE_OPT_SLOTS], next[AIE_OPT_SLOTS];
+  for (int s = 0; s < AIE_OPT_SLOTS; ++s) {
+    const int64_t left = count - 4 * (int64_t)s;
+    slot[s] = left > 0 ? aie_opt_slot_sumsq(g + 4 * s, left < 4 ? (int)left : 4) : 0.0;
+  }
+  for (int L = 0; L < 8; ++L) {
+    for (int i = 0; i < AIE_OPT_SLOTS; ++i) next[i] = slot[i] + slot[i ^ (1 << L)];
+    for (int i = 0; i < AIE_OPT_SLOTS; ++i) slot[i] = next[i];
+  }
+  return slot[0];
+}
+typedef struct aie_opt_step {
+  float coef, step, b2s;                 /* the float64 scalars, rounded once */
+  float beta1, beta2, omb1, omb2, eps;   /* omb = 1 - beta in float32 */
+  float norm;                            /* stats[0] */
+  int32_t skipped;
+  aie_opt_state next;                    /* the state after the call (the old one for a skipped group) */
+} aie_opt_step;
+AIE_HD static inline aie_opt_step aie_opt_scalars(double n2, float max_norm, float beta1, float beta2, float eps, float lr,
+                                                  aie_opt_state old) {
+  AIE_NOCONTRACT
+  aie_opt_step S;
+  const double norm = sqrt(n2);
+  const double sum = norm + 1e-6;
+  const double ratio = (double)max_norm / sum;
+  const double coef = max_norm > 0.0f ? (ratio < 1.0 ? ratio : 1.0) : 1.0;
+  S.skipped = !aie_opt_finite(n2);
+  S.norm = (float)norm;
+  S.next = old;
+  double p1 = old.t == 0 ? 1.0 : old.p1, p2 = old.t == 0 ? 1.0 : old.p2;
+  p1 = p1 * (double)beta1;
+  p2 = p2 * (double)beta2;
+  if (!S.skipped) S.next.t = old.t + 1, S.next.p1 = p1, S.next.p2 = p2;
+  const double c1 = 1.0 - p1, c2 = 1.0 - p2;
+  S.coef = S.skipped ? 0.0f : (float)coef;
+  S.step = (float)((double)lr / c1);
+  S.b2s = (float)sqrt(c2);
+  S.beta1 = beta1, S.beta2 = beta2, S.eps = eps;
+  S.omb1 = 1.0f - beta1;
+  S.omb2 = 1.0f - beta2;
+  return S;
+}
+AIE_HD static inline void aie_opt_element(const aie_opt_step* S, float g, float* w, float* m, float* v) {
+  AIE_NOCONTRACT
+  const float gc = g * S->coef;
+  const float bm = S->beta1 * *m;
+  const float mn = fmaf(S->omb1, gc, bm);
+  const float bv = S->beta2 * *v;
+  const float og = S->omb2 * gc;
+  const float vn = fmaf(og, gc, bv);
+  const float rt = sqrtf(vn);
+  const float q = AIE_FDIV_RN(rt, S->b2s);
+  const float d = q + S->eps;
+  const float u = AIE_FDIV_RN(mn, d);
+  *w = fmaf(-S->step, u, *w);
+  *m = mn;
+  *v = vn;
+}
+AIE_HD static inline void aie_opt_stats(const aie_opt_step* S, float* stats) {
+  stats[0] = S->norm;
+  stats[1] = S->coef;
+  stats[2] = (float)S->next.t;
+  stats[3] = S->skipped ? 1.0f : 0.0f;
+}
+/* The whole step of one group on the host: every pointer of the descriptor is host memory here. */
+static inline void aie_adam_group_host(const aie_opt_group* G) {
+  double n2 = 0.0;
+  for (int i = 0; i < G->n_tensors; ++i)
+    for (int64_t e = 0; e < G->tensors[i].n; e += AIE_OPT_CHUNK) {
+      const int64_t left = G->tensors[i].n - e;
+      n2 += aie_opt_chunk_sumsq(G->tensors[i].g + e, left < AIE_OPT_CHUNK ? left : AIE_OPT_CHUNK);
+    }
+  aie_opt_state* st = (aie_opt_state*)G->d_state;
+  const aie_opt_step S = aie_opt_scalars(n2, G->max_norm, G->beta1, G->beta2, G->eps, *G->d_lr, *st);
+  aie_opt_stats(&S, G->d_stats);
+  if (S.skipped) return;
+  *st = S.next;
+  for (int i = 0; i < G->n_tensors; ++i) {
+    const aie_opt_tensor* T = &G->tensors[i];
+    for (int64_t e = 0; e < T->n; ++e) aie_opt_element(&S, T->g[e], T->w + e, T->m + e, T->v + e);
+  }
+}
+/* The kernels' argument (aie_adam_step fills it: aie_plan_adam).  Workgroup b of either launch owns one chunk: b <
+ * grp[0].chunks the agents' group's chunk b, else the planner's chunk b - grp[0].chunks; a group's chunk c belongs to the last
+ * tensor i with t[i].first <= c and is that tensor's chunk c - t[i].first.  wide != 0: w, g, m and v are all 16-byte
+ * aligned (16-byte lane accesses on whole quads), else 4-byte ones.  ws: the group's share of the workspace, 4 float64
+ * words for the state's copy {t, p1, p2, 0}, then one float64 per chunk. */
+typedef struct aie_opt_tensor_k {
+  float* w;
+  const float* g;
+  float *m, *v;
+  int64_t n;
+  int32_t first, wide;
+} aie_opt_tensor_k;
+typedef struct aie_opt_group_k {
+  aie_opt_tensor_k t[AIE_OPT_MAX_TENSORS];
+  const float* lr;
+  aie_opt_state* state;
+  float* stats;
+  double* ws;
+  float beta1, beta2, eps, max_norm;
+  int32_t n_tensors, chunks;   /* chunks 0: the group is left out */
+} aie_opt_group_k;
+typedef struct aie_adam_args {
+  aie_opt_group_k grp[2];
+} aie_adam_args;
+#define AIE_OPT_WS_HEAD 4 /* float64 words ahead of a group's chunk sums */
 /* aie_trajectory_store's kernel argument: the caller's segments (include/aie.h: aie_traj_segment, 32 bytes each) with the
  * copy width decided on the host: wide != 0 = 16-byte lane accesses (source, destination, stride and size allow it for
  * every replica and slot), else 4-byte ones. */

@@ -345,6 +345,76 @@ static inline int aie_plan_mlp_backward_launch(aie_mlp_bwd_plan* p, int64_t B, c
   return AIE_OK;
 }
 
+/* ---- aie_adam_step: a workgroup per chunk of AIE_OPT_CHUNK elements, the same grid for both launches ----
+ * aie_plan_adam_groups checks the descriptors in include/aie.h's order, fills the kernels' argument without the workspace
+ * pointers -- the chunk table (a tensor's first chunk in its group), the `wide` flags -- and sizes each group's share of the
+ * workspace (the workspace-bytes query stops here); aie_plan_adam adds the workspace's own check and carves it. */
+typedef struct aie_adam_plan {
+  aie_adam_args A;
+  int64_t ws_bytes[2], need;   /* each group's share (0: left out); workspace bytes of this call */
+  uint32_t grid, block;
+} aie_adam_plan;
+
+static inline int aie_plan_adam_groups(const aie_opt_group* agents, const aie_opt_group* planner, char* err, size_t errlen,
+                                       aie_adam_plan* p) {
+  const char* fn = "aie_adam_step";
+  memset(p, 0, sizeof(*p));
+  const aie_opt_group* grp[2] = {agents, planner};
+  int64_t total = 0;
+  for (int c = 0; c < 2; ++c) {
+    const aie_opt_group* g = grp[c];
+    if (!g) continue;
+    const char* who = c ? "planner's" : "agents'";
+    aie_opt_group_k* G = &p->A.grp[c];
+    if (g->n_tensors < 1 || g->n_tensors > AIE_OPT_MAX_TENSORS || !g->tensors)
+      AIE_PLAN_REFUSE(AIE_E_INVALID, "%s: the %s group has %d tensors at %p (needs 1 .. %d, not NULL)", fn, who, g->n_tensors,
+                      (const void*)g->tensors, AIE_OPT_MAX_TENSORS);
+    if (!(g->beta1 >= 0.0f && g->beta1 < 1.0f) || !(g->beta2 >= 0.0f && g->beta2 < 1.0f) || !(g->eps > 0.0f))
+      AIE_PLAN_REFUSE(AIE_E_INVALID, "%s: the %s group needs beta1 (%g) and beta2 (%g) in [0, 1) and eps (%g) > 0", fn, who,
+                      (double)g->beta1, (double)g->beta2, (double)g->eps);
+    if (!g->d_lr || ((uintptr_t)g->d_lr & 3) || !g->d_state || ((uintptr_t)g->d_state & 7) || !g->d_stats || ((uintptr_t)g->d_stats & 3))
+      AIE_PLAN_REFUSE(AIE_E_INVALID, "%s: the %s group needs d_lr (%p) and d_stats (%p) 4-byte aligned and d_state (%p) 8-byte "
+                      "aligned, none NULL", fn, who, (const void*)g->d_lr, (const void*)g->d_stats, (const void*)g->d_state);
+    int64_t chunks = 0;
+    for (int i = 0; i < g->n_tensors; ++i) {
+      const aie_opt_tensor* t = &g->tensors[i];
+      const uintptr_t any = (uintptr_t)t->w | (uintptr_t)t->g | (uintptr_t)t->m | (uintptr_t)t->v;
+      if (!t->w || !t->g || !t->m || !t->v || (any & 3) || t->n < 1)
+        AIE_PLAN_REFUSE(AIE_E_INVALID, "%s: tensor %d of the %s group (w %p, g %p, m %p, v %p, n %lld) needs four 4-byte aligned "
+                        "pointers, none NULL, and n >= 1", fn, i, who, (const void*)t->w, (const void*)t->g, (const void*)t->m,
+                        (const void*)t->v, (long long)t->n);
+      const int64_t nc = t->n / AIE_OPT_CHUNK + (t->n % AIE_OPT_CHUNK ? 1 : 0);
+      if (nc > AIE_PLAN_GRID_MAX - total - chunks)
+        AIE_PLAN_REFUSE(AIE_E_INVALID, "%s: tensor %d of the %s group (n %lld) brings the call over the %lld chunks one launch "
+                        "takes", fn, i, who, (long long)t->n, (long long)AIE_PLAN_GRID_MAX);
+      aie_opt_tensor_k* k = &G->t[i];
+      k->w = t->w, k->g = t->g, k->m = t->m, k->v = t->v, k->n = t->n;
+      k->first = (int32_t)chunks, k->wide = !(any & 15);
+      chunks += nc;
+    }
+    G->lr = g->d_lr, G->state = (aie_opt_state*)g->d_state, G->stats = g->d_stats;
+    G->beta1 = g->beta1, G->beta2 = g->beta2, G->eps = g->eps, G->max_norm = g->max_norm;
+    G->n_tensors = g->n_tensors, G->chunks = (int32_t)chunks;
+    p->ws_bytes[c] = (AIE_OPT_WS_HEAD + chunks) * (int64_t)sizeof(double);
+    total += chunks;
+  }
+  p->need = p->ws_bytes[0] + p->ws_bytes[1];
+  p->grid = (uint32_t)total, p->block = AIE_OPT_SLOTS;
+  return AIE_OK;
+}
+
+static inline int aie_plan_adam(const aie_opt_group* agents, const aie_opt_group* planner, void* d_workspace,
+                                int64_t workspace_bytes, char* err, size_t errlen, aie_adam_plan* p) {
+  const int rc = aie_plan_adam_groups(agents, planner, err, errlen, p);
+  if (rc != AIE_OK || !p->grid) return rc;
+  if (!d_workspace || ((uintptr_t)d_workspace & 7) || workspace_bytes < p->need)
+    AIE_PLAN_REFUSE(AIE_E_INVALID, "aie_adam_step: the workspace (%p, %lld bytes) must be device memory, 8-byte aligned, of at "
+                    "least %lld bytes (aie_adam_workspace_bytes)", d_workspace, (long long)workspace_bytes, (long long)p->need);
+  p->A.grp[0].ws = (double*)d_workspace;
+  p->A.grp[1].ws = (double*)((uint8_t*)d_workspace + p->ws_bytes[0]);
+  return AIE_OK;
+}
+
 /* ---- aie_trajectory_store: a workgroup per replica ---- */
 typedef struct aie_traj_plan { aie_traj_args A; uint32_t grid, block; } aie_traj_plan;
 

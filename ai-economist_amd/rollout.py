@@ -395,6 +395,97 @@ def policy_mlp(be, x_a, x_p, weights_a, weights_p):
     return _policy_mlp_function().apply(be, x_a, x_p, names[0], names[1], *flat)
 
 
+class Adam:
+    """Adam under a gradient-norm clip for the two actor classes' parameters, ONE library call of two launches per step
+    (Backend.adam_step, aie_adam_step) -- the optimizer the reference's tutorials train with (lr 0.0003, grad_clip 10), one
+    parameter group and one norm per class.  params_a / params_p: a mapping of tensors (a MaskedMLPPolicy's weights_a /
+    weights_p) or a sequence of them, at most 16 per class, contiguous float32 device tensors that are updated where they
+    lie (the next policy_mlp_forward, eager or replayed, reads the new values); None leaves a class out.  This object owns
+    the moments m and v, each class's state (int64 [4]: the step count t, then the bits of beta1^t and beta2^t) and
+    statistics, the learning rate (ONE float32 on the device for both classes) and the workspace; nothing is allocated
+    after the constructor.  max_norm <= 0: no clipping.
+    step(grads=None): grads = (grads_a, grads_p), shaped like the parameters (mappings with their keys, or sequences in
+    their order: policy_mlp_backward's dicts); None reads each parameter's .grad (for a view, such as MaskedMLPPolicy's
+    value column, its base's).  Gradients are used where they lie -- contiguous float32 device tensors, never converted --
+    and are neither modified, zeroed nor freed.  Captured in a graph, a replay advances t and reads the learning rate
+    anew: set_lr(x) between replays is a schedule.  A class whose gradient norm is not finite is skipped (stats()[..][3]
+    == 1): its weights, moments and step count stay.  The arithmetic is include/aie.h's: two runs give the same bits."""
+
+    def __init__(self, be, params_a, params_p, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, max_norm=10.0):
+        import torch
+
+        from . import _cabi
+
+        self.be = be
+        self.betas, self.eps, self.max_norm = (float(betas[0]), float(betas[1])), float(eps), float(max_norm)
+        self.lr = torch.full((1,), float(lr), dtype=torch.float32, device=be.device)
+        self.groups = []
+        need = 0
+        for params in (params_a, params_p):
+            if params is None:
+                self.groups.append(None)
+                continue
+            keys = list(params.keys()) if hasattr(params, "keys") else None
+            ps = [params[k] for k in keys] if keys is not None else list(params)
+            if not 1 <= len(ps) <= _cabi.OPT_MAX_TENSORS:
+                raise ValueError("Adam: a class has 1 .. %d parameter tensors (%d given)" % (_cabi.OPT_MAX_TENSORS, len(ps)))
+            for p in ps:
+                if not isinstance(p, torch.Tensor) or p.dtype != torch.float32 or p.device != be.device or not p.is_contiguous() \
+                        or p.numel() < 1:
+                    raise ValueError("Adam: parameters are contiguous float32 tensors on the backend's device")
+            f = dict(dtype=torch.float32, device=be.device)
+            self.groups.append(dict(
+                keys=keys, params=[p.detach() for p in ps], src=ps,
+                m=[torch.zeros(p.numel(), **f) for p in ps], v=[torch.zeros(p.numel(), **f) for p in ps],
+                state=torch.zeros(_cabi.OPT_STATE_BYTES // 8, dtype=torch.int64, device=be.device),
+                stats=torch.zeros(_cabi.OPT_N_STATS, **f)))
+            need += 4 + sum(-(-p.numel() // _cabi.OPT_CHUNK) for p in ps)  # float64 words: include/aie.h's formula
+        if need == 0:
+            raise ValueError("Adam: no parameters")
+        self.workspace = torch.zeros(need, dtype=torch.float64, device=be.device)
+
+    @staticmethod
+    def _grad_of(p):
+        g = p.grad
+        base = getattr(p, "_base", None)
+        if g is None and base is not None and base.numel() == p.numel() and base.is_contiguous():
+            g = base.grad
+        if g is None:
+            raise ValueError("Adam.step: a parameter has no .grad (run backward first, or pass grads=)")
+        return g
+
+    def step(self, grads=None):
+        """One step of both classes: one Backend.adam_step call on the current stream."""
+        descs = []
+        for c, G in enumerate(self.groups):
+            if G is None:
+                descs.append(None)
+                continue
+            if grads is None:
+                gs = [self._grad_of(p) for p in G["src"]]
+            else:
+                given = grads[c]
+                gs = [given[k] for k in G["keys"]] if G["keys"] is not None and hasattr(given, "keys") else list(given)
+            if len(gs) != len(G["params"]):
+                raise ValueError("Adam.step: %d gradients for %d parameters" % (len(gs), len(G["params"])))
+            descs.append(self.be.adam_group(zip(G["params"], gs, G["m"], G["v"]), self.lr, G["state"], G["stats"],
+                                            betas=self.betas, eps=self.eps, max_norm=self.max_norm))
+        self.be.adam_step(descs[0], descs[1], self.workspace)
+
+    def set_lr(self, lr):
+        """Fills the learning rate's device scalar: seen by the next step, or the next replay of a captured one."""
+        self.lr.fill_(float(lr))
+
+    def stats(self):
+        """(stats_a, stats_p): float32 [4] device tensors -- the gradient norm before clipping, the clip coefficient, the
+        step count after the last call, 1 if that call skipped the class -- or None for a class left out."""
+        return tuple(None if G is None else G["stats"] for G in self.groups)
+
+    def steps(self):
+        """(t_a, t_p): each class's step count as a 0-dim int64 device tensor (a view of its state), or None."""
+        return tuple(None if G is None else G["state"][0] for G in self.groups)
+
+
 def __getattr__(name):  # rollout.MaskedCategorical, rollout.PPOLoss, rollout.PolicyMLP: the classes, made when first asked for
     if name == "MaskedCategorical":
         return _masked_categorical()

@@ -778,6 +778,64 @@ int64_t aie_policy_mlp_backward_workspace_bytes(const aie_env* env, int64_t B, c
 int aie_policy_mlp_backward(aie_env* env, int64_t B, const aie_mlp_grad_class* agents, const aie_mlp_grad_class* planner,
                             void* d_workspace, int64_t workspace_bytes, void* stream);
 
+/* Adam with gradient-norm clipping, in place, for up to two parameter groups (one per actor class), TWO launches for both
+ * groups together: the last step of an update -- what a trainer otherwise writes as clip_grad_norm_ and a capturable
+ * torch.optim.Adam, several dozen small launches over the sixteen tensors of aie_policy_mlp_backward (the reference's
+ * tutorials train with Adam, lr 0.0003, grad_clip 10).  No weight decay, no AMSGrad.
+ * Per group (aie_opt_group): `tensors`, an array in HOST memory of n_tensors (1 .. AIE_OPT_MAX_TENSORS) descriptors, copied
+ * into the kernel argument: w (the weights), g (their gradient), m and v (Adam's moments, zeroed by the caller before the
+ * first step): n >= 1 float32 each, any device memory, 4-byte aligned; beta1, beta2 in [0, 1), eps > 0, max_norm (<= 0, or a
+ * NaN: no clipping); d_lr: ONE float32 in device memory, read at every launch -- a learning-rate schedule is a fill of that
+ * float, not a recapture; d_state: AIE_OPT_STATE_BYTES of device memory, 8-byte aligned, {int64 t; double p1, p2; 8 bytes
+ * unused}, zeroed by the caller before the first step: the step count and the running products beta1^t, beta2^t, advanced
+ * by every call, replays of a captured one included; d_stats: AIE_OPT_N_STATS float32 in device memory, written by every call.
+ * THE ARITHMETIC (csrc/aie_trainer_math.h states it once -- aie_opt_chunk_sumsq, aie_opt_scalars, aie_opt_element -- and the
+ * CPU test compiles those helpers):
+ *   sum of squares, float64 throughout (the square (double)g * (double)g is exact): a tensor is cut into chunks of
+ *     AIE_OPT_CHUNK consecutive elements (the last may be short).  Slot s = 0 .. 255 of a chunk adds its elements 4s .. 4s + 3
+ *     in ascending order from +0 (an element past the chunk's end counts as +0); the 256 slots are combined by the binary
+ *     tree slot[i] += slot[i ^ 2^L] for L = 0 .. 7, all i at once per level (addition commutes: every slot ends with the same
+ *     bits); the group's n2 = its chunks' sums added in ascending order from +0, tensor after tensor, chunk after chunk.
+ *     Nothing depends on the device or on how many compute units ran the call.
+ *   scalars, float64:  norm = sqrt(n2);  coef = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1 (torch's formula);
+ *     with t == 0: p1 = p2 = 1;  then t += 1, p1 *= beta1, p2 *= beta2;  step = lr / (1 - p1);  b2s = sqrt(1 - p2);
+ *     coef, step and b2s are rounded to float32 once, where the elements take them.
+ *   per element, float32, every operation rounded on its own (fmaf: rounded once; division and square root correctly rounded):
+ *     gc = g * coef;  m = fmaf(1 - beta1, gc, beta1 * m);  v = fmaf((1 - beta2) * gc, gc, beta2 * v);
+ *     d = sqrtf(v) / b2s + eps;  w = fmaf(-step, m / d, w).          g is not modified.
+ *   A group whose n2 is not finite (a NaN or an infinity among its gradients) is SKIPPED: w, m, v and the state keep their
+ *     bits; the other group proceeds (aie_ppo_loss's treatment of a non-finite actor, one level up).
+ *   stats: [0] the norm before clipping, [1] coef (0 for a skipped group), [2] t after the call, [3] 1 if skipped, else 0.
+ * Two runs from equal starts give the same bits.  No atomics and no ordering between workgroups: the first launch reads g
+ * and d_state and writes only the workspace (one float64 per chunk, and a copy of the state); the second reads the workspace,
+ * g and d_lr and writes w, m, v, d_state and d_stats.  d_workspace: device memory, 8-byte aligned, the call's own until it has
+ * run (two streams: one each; a captured call keeps the pointer), of 8 * (4 + chunks) bytes per group given, chunks = the sum
+ * of ceil(n / AIE_OPT_CHUNK) over its tensors: what the workspace_bytes function returns (0 with no group, or the negative
+ * code of the call's own refusal).  Accesses are 16 bytes per lane for a tensor whose w, g, m and v are all 16-byte aligned,
+ * else 4 bytes; nothing is read or written past n.  Tensors must not overlap one another.
+ * Either group may be NULL; with both NULL the call launches nothing and returns AIE_OK.  Asynchronous on `stream`, no
+ * allocation, no synchronisation, capturable in a hipGraph.  AIE_E_INVALID, checked in this order (the agents' group first):
+ * n_tensors outside 1 .. AIE_OPT_MAX_TENSORS or a NULL `tensors`; a beta outside [0, 1) or eps <= 0 (a NaN included); a NULL
+ * or misaligned d_lr, d_state or d_stats; per tensor in order a NULL or misaligned w, g, m or v, or n < 1; more chunks than
+ * one launch takes; at last a workspace that is NULL, not 8-byte aligned or too small.  A refused call launches and writes
+ * nothing.  All scenarios: the environment only carries the device and the error text. */
+#define AIE_OPT_CHUNK 1024        /* elements per workgroup: 256 threads x 4 consecutive */
+#define AIE_OPT_MAX_TENSORS 16
+#define AIE_OPT_N_STATS 4
+#define AIE_OPT_STATE_BYTES 32
+typedef struct aie_opt_tensor {
+  float* w; const float* g; float *m, *v;   /* weights, their gradient, first and second moment: n float32 each */
+  int64_t n;
+} aie_opt_tensor;
+typedef struct aie_opt_group {
+  const aie_opt_tensor* tensors; int32_t n_tensors;   /* host memory */
+  float beta1, beta2, eps, max_norm;                  /* max_norm <= 0: no clipping */
+  const float* d_lr; void* d_state; float* d_stats;   /* device memory: 1 float32; AIE_OPT_STATE_BYTES; AIE_OPT_N_STATS float32 */
+} aie_opt_group;
+int64_t aie_adam_workspace_bytes(const aie_env* env, const aie_opt_group* agents, const aie_opt_group* planner);
+int aie_adam_step(aie_env* env, const aie_opt_group* agents, const aie_opt_group* planner, void* d_workspace,
+                  int64_t workspace_bytes, void* stream);
+
 /* Trajectory storage with the slot index on the device: one launch per step copies up to AIE_TRAJ_MAX_SEGMENTS per-replica
  * blocks (observations, masks, actions, log-probabilities, values -- any device memory, arena tensors included) into
  * replica e's slot d_slot[e] of the caller's ring buffers, then d_slot[e] becomes (d_slot[e] + 1) % n_slots.
