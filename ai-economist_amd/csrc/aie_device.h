@@ -700,18 +700,40 @@ __device__ __forceinline__ int draw_window_publish(uint32_t* w, int cap, const M
   return avail;
 }
 // The same from the state in HBM: only the rows the window covers are fetched (step start: the wave that will hold
-// the state later has nothing but the record copy to do, and the fetch rides behind it).
-__device__ __forceinline__ int draw_window_publish_from_hbm(uint32_t* w, int cap, const uint32_t* __restrict__ gkey, int pos,
-                                                            int lane) {
+// the state later has nothing but the record copy to do, and the fetch rides behind it).  In two halves, so that the
+// fetch can be in flight together with the caller's other loads and everything is waited for once (step_body):
+// draw_rows_request asks for a lane's word of each of the first three rows the window covers -- all there are up to a
+// window of 128 words -- and waits for nothing; draw_rows_commit writes them to the window and fetches what a larger
+// window has beyond them, row by row.  Word i of the state is addressed as the (wave-uniform) state pointer plus an
+// unsigned 32-bit byte offset of the lane.
+struct DrawRows { uint32_t v[3]; };
+__device__ __forceinline__ const uint32_t* draw_row_word(const uint32_t* __restrict__ gkey, int i) {
+  return reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(gkey) + 4u * (uint32_t)i);
+}
+// (slot < avail implies i < 624; the words are raw: see draw_window_publish)
+__device__ __forceinline__ bool draw_row_has(int cap, int pos, int d, int lane) {
   const int avail = cap < AIE_MT_N - pos ? cap : AIE_MT_N - pos;
+  const int slot = 64 * ((pos >> 6) + d) + lane - pos;
+  return pos >= 0 && d * 64 < cap + 64 && slot >= 0 && slot < avail;
+}
+__device__ __forceinline__ DrawRows draw_rows_request(int cap, const uint32_t* __restrict__ gkey, int pos, int lane) {
+  DrawRows rows = {{0u, 0u, 0u}};
+#pragma unroll
+  for (int d = 0; d < 3; ++d)
+    if (draw_row_has(cap, pos, d, lane)) rows.v[d] = *draw_row_word(gkey, 64 * ((pos >> 6) + d) + lane);
+  return rows;
+}
+__device__ __forceinline__ int draw_rows_commit(uint32_t* w, int cap, const DrawRows& rows, const uint32_t* __restrict__ gkey,
+                                                int pos, int lane) {
   const int r0 = pos >> 6;
-  for (int d = 0; d * 64 < cap + 64; ++d) {
-    const int r = r0 + d, i = 64 * r + lane;
-    if (r > 9) break;
-    const int slot = i - pos;
-    if (slot >= 0 && slot < avail) w[slot] = gkey[i];  // (slot < avail implies i < 624; raw: see draw_window_publish)
+#pragma unroll
+  for (int d = 0; d < 3; ++d)
+    if (draw_row_has(cap, pos, d, lane)) w[64 * (r0 + d) + lane - pos] = rows.v[d];
+  for (int d = 3; d * 64 < cap + 64; ++d) {
+    if (r0 + d > 9) break;
+    if (draw_row_has(cap, pos, d, lane)) w[64 * (r0 + d) + lane - pos] = *draw_row_word(gkey, 64 * (r0 + d) + lane);
   }
-  return avail;
+  return cap < AIE_MT_N - pos ? cap : AIE_MT_N - pos;
 }
 __device__ __forceinline__ void mt_rows_from_hbm(MT& m, const uint32_t* gkey, int lane) {
   // agent-scope loads: the rows may have been rewritten by the other wave of the workgroup during this launch

@@ -1,7 +1,7 @@
 // aie_gtb_state.h -- the gather-trade-build family's per-replica state helpers: the world helpers (can_agent_occupy,
 // log_event, agent_can_build), the agents' registers (Agents, agents_load / agents_store, hist_bit, decode_actions), the
 // change log of one step (dirty_*) and the record's way in and out of a step with the cells' byte plane
-// (load_record_step, store_record_step).  The foot of the family's headers: it includes aie_device.h only, and
+// (load_record_step_request / _commit, store_record_step).  The foot of the family's headers: it includes aie_device.h only, and
 // aie_gtb_components.h and aie_gtb_observe.h both include it.  No kernel.  Part of the gather-trade-build cache key
 // (aie_jit.h: kSourcesGtb).
 #pragma once
@@ -122,10 +122,26 @@ __device__ __forceinline__ void agents_store(const Ctx& c, const Agents& A) {
 // the tensors keep what the step's first launch wrote.  No other kernel ever runs an environment with such subspaces
 // (aie_capi.hip: aie_step_impl sends it to the full-featured kernel, aie_jit_eligible keeps it off the run-time
 // instances); elsewhere the decode is the plain one, which leaves foreign slots out of the packed word.
+// The loads of a lane that has one word to decode -- a single-action agent, a planner bracket -- can be asked for ahead
+// of the decode (action_words_request) and handed to it; a multi-action agent's words and everything of the `host`
+// branches are loaded where they are decoded.
+struct ActionWords { int32_t a, p; bool pre; };
+__device__ __forceinline__ ActionWords action_words_request(const Ctx& c, const int32_t* __restrict__ aa,
+                                                            const int32_t* __restrict__ ap, uint8_t* __restrict__ arena = nullptr) {
+  const aie_params& P = c.P;
+  ActionWords w = {0, 0, !(c.full && arena)};
+  if (!w.pre) return w;
+  const int i = c.tid;
+  if (i < P.n && aa && !P.c.multi_action_mode_agents) w.a = aa[((int64_t)c.e * P.n + i) * P.act_a_width];
+  if (i < AIE_MAX_BRACKETS && ap && i < P.n_sub_p) w.p = ap[(int64_t)c.e * P.act_p_width + (P.c.multi_action_mode_planner ? i : 0)];
+  return w;
+}
 __device__ __forceinline__ int decode_actions(const Ctx& c, Agents& A, const int32_t* __restrict__ aa,
-                               const int32_t* __restrict__ ap, uint8_t* __restrict__ arena = nullptr) {
+                               const int32_t* __restrict__ ap, uint8_t* __restrict__ arena = nullptr,
+                               const ActionWords* pre = nullptr) {
   const aie_params& P = c.P;
   const bool host = c.full && arena;  // (compile-time false in the common step kernel, see Ctx::full)
+  if (pre && !pre->pre) pre = nullptr;
   const int i = c.tid;
   uint32_t act = 0;
   bool bad_a = false, bad_p = false;  // out-of-range indices: NO-OP here, an exception in the reference (AIE_ERR_*)
@@ -142,7 +158,7 @@ __device__ __forceinline__ int decode_actions(const Ctx& c, Agents& A, const int
           else if (P.sub_a_slot[s] != AIE_SUB_HOST) act |= (uint32_t)v << shift[P.sub_a_slot[s]];
         }
       } else {
-        const int v = a[0];
+        const int v = pre ? pre->a : a[0];
         bad_a = v < 0 || v >= P.A;
         for (int s = 0; s < P.n_sub_a; ++s)
           if (P.sub_a_slot[s] != AIE_SUB_HOST && v >= P.sub_a_base[s] && v < P.sub_a_base[s] + P.sub_a_dim[s])
@@ -174,11 +190,11 @@ __device__ __forceinline__ int decode_actions(const Ctx& c, Agents& A, const int
       // (the tax block's first row / first single-action index: 0 / 1 without foreign planner rows ahead of it)
       const int row0 = (host && P.n_host_p) ? P.tax_p_row0 : 0, x0 = (host && P.n_host_p) ? P.tax_p_base : 1;
       if (P.c.multi_action_mode_planner) {
-        v = a[row0 + i];
+        v = pre ? pre->p : a[row0 + i];
         bad_p = v < 0 || v > P.sub_p_dim;  // (the tax component ignores what its mask forbids; out of range is an error)
         if (bad_p) v = 0;
       } else {
-        const int x = a[0];
+        const int x = pre ? pre->p : a[0];
         bad_p = x < 0 || x >= ((host && P.n_host_p) ? P.AP : 1 + P.n_sub_p * P.sub_p_dim);
         if (x >= x0 && x < x0 + P.n_sub_p * P.sub_p_dim && (x - x0) / P.sub_p_dim == i) v = (x - x0) % P.sub_p_dim + 1;
       }
@@ -249,34 +265,76 @@ __device__ __forceinline__ uint4 cells8_expand(uint32_t d) {
 // (A/B on one MI355X, BASELINE configs[1] at 4096 replicas, profiles/cell_plane_ab.txt: with one wait per load, as the
 // word-per-cell copy has them, the plane gains nothing -- 19.97 us per launch, the parent's 19.96 -- however the two waves
 // share it; with the loads below requested together 19.62 us.)
-__device__ __forceinline__ void load_record_step(const Ctx& c, const uint8_t* __restrict__ arena, int wave, int nwaves) {
-  if (!c.P.o_cells8) {
-    MT none;
-    load_record(c, arena, none, wave, nwaves, /*key_wave=*/-1);
-    return;
-  }
+// In two halves, so that a wave has its other loads in flight beside these and waits once for all of them (step_body;
+// profiles/prologue_loads_ab.txt): load_record_step_request says which units and plane dwords the lane owns -- the one
+// statement of it -- and asks for a lane's first three loads of either kind; load_record_step_commit writes them to the
+// image and copies what a larger image has beyond them, one by one.  A record without the plane (more than 7 agents,
+// max_health > 1) is 16-byte units throughout, every nwaves-th group of 64 a wave's: there the three are a lane's first
+// three units (BASELINE configs[2], ten agents, at 4096 replicas: 35.66 -> 35.16 us per launch against load, wait, LDS
+// write per unit -- round 6 had found the opposite with the whole share of a 4.3 KB image requested at once, step_body).
+struct RecordIn {
+  int q, k0;            // the lane's first unit of the image; with the plane: its first plane dword (k0 == q0: none)
+  bool hu, h0, h1, h2;  // which of unit q and plane dwords k0, k0 + 64, k0 + 128 exist; without the plane: units q, q + st, q + 2 st
+  uint4 u, u1, u2;      // (u1, u2: without the plane only)
+  uint32_t d0, d1, d2;
+};
+__device__ __forceinline__ RecordIn load_record_step_request(const Ctx& c, const uint8_t* __restrict__ arena, int wave,
+                                                             int nwaves) {
+  RecordIn in;
+  in.u = in.u1 = in.u2 = uint4{0u, 0u, 0u, 0u};
+  in.d0 = in.d1 = in.d2 = 0u;
   const uint8_t* g = arena + (int64_t)c.e * c.P.rec_bytes;  // (a_records == 0, see load_record)
   const uint4* src = reinterpret_cast<const uint4*>(g);
+  const int nq = rec_lds_bytes(c.P) >> 4, st = nwaves * AIE_NT;
+  if (!c.P.o_cells8) {
+    in.q = wave * AIE_NT + c.tid;
+    in.k0 = 0;
+    in.hu = false;
+    in.h0 = in.q < nq;
+    in.h1 = in.q + st < nq;
+    in.h2 = in.q + 2 * st < nq;
+    if (in.h0) in.u = src[in.q];
+    if (in.h1) in.u1 = src[in.q + st];
+    if (in.h2) in.u2 = src[in.q + 2 * st];
+    return in;
+  }
   const uint32_t* plane = reinterpret_cast<const uint32_t*>(g + c.P.o_cells8);
+  const int q0 = (4 * c.P.HW) >> 4;  // units [0, q0): cells only (o_cells == 0)
+  // The first wave takes the whole plane: the second has the draw window and the constant tables to fetch beside its
+  // units.  A lane's first unit and its first three plane dwords are all there is up to 27 x 27.
+  in.q = q0 + wave * AIE_NT + c.tid;
+  in.k0 = wave == 0 ? c.tid : q0;
+  in.hu = in.q < nq;
+  in.h0 = in.k0 < q0;
+  in.h1 = in.k0 + AIE_NT < q0;
+  in.h2 = in.k0 + 2 * AIE_NT < q0;
+  if (in.hu) in.u = src[in.q];
+  if (in.h0) in.d0 = plane[in.k0];
+  if (in.h1) in.d1 = plane[in.k0 + AIE_NT];
+  if (in.h2) in.d2 = plane[in.k0 + 2 * AIE_NT];
+  return in;
+}
+__device__ __forceinline__ void load_record_step_commit(const Ctx& c, const uint8_t* __restrict__ arena, int nwaves,
+                                                        const RecordIn& in) {
+  const uint8_t* g = arena + (int64_t)c.e * c.P.rec_bytes;
+  const uint4* src = reinterpret_cast<const uint4*>(g);
   uint4* dst = reinterpret_cast<uint4*>(c.rec);
-  const int nq = rec_lds_bytes(c.P) >> 4, q0 = (4 * c.P.HW) >> 4;  // units [0, q0): cells only (o_cells == 0)
-  // The first wave takes the whole plane: the second has the draw window and the constant tables to fetch behind its
-  // units.  A lane's first unit and its first three plane dwords -- all there is up to 27 x 27 -- are requested together
-  // and waited for once; what a larger world has beyond them follows one by one.
-  const int q = q0 + wave * AIE_NT + c.tid, k0 = wave == 0 ? c.tid : q0;
-  const bool hu = q < nq, h0 = k0 < q0, h1 = k0 + AIE_NT < q0, h2 = k0 + 2 * AIE_NT < q0;
-  uint4 u = {0u, 0u, 0u, 0u};
-  uint32_t d0 = 0u, d1 = 0u, d2 = 0u;
-  if (hu) u = src[q];
-  if (h0) d0 = plane[k0];
-  if (h1) d1 = plane[k0 + AIE_NT];
-  if (h2) d2 = plane[k0 + 2 * AIE_NT];
-  if (hu) dst[q] = u;
-  if (h0) dst[k0] = cells8_expand(d0);
-  if (h1) dst[k0 + AIE_NT] = cells8_expand(d1);
-  if (h2) dst[k0 + 2 * AIE_NT] = cells8_expand(d2);
-  for (int qq = q + nwaves * AIE_NT; qq < nq; qq += nwaves * AIE_NT) dst[qq] = src[qq];
-  for (int k = k0 + 3 * AIE_NT; k < q0; k += AIE_NT) dst[k] = cells8_expand(plane[k]);
+  const int nq = rec_lds_bytes(c.P) >> 4, st = nwaves * AIE_NT;
+  if (!c.P.o_cells8) {
+    if (in.h0) dst[in.q] = in.u;
+    if (in.h1) dst[in.q + st] = in.u1;
+    if (in.h2) dst[in.q + 2 * st] = in.u2;
+    for (int qq = in.q + 3 * st; qq < nq; qq += st) dst[qq] = src[qq];
+    return;
+  }
+  const uint32_t* plane = reinterpret_cast<const uint32_t*>(g + c.P.o_cells8);
+  const int q0 = (4 * c.P.HW) >> 4;
+  if (in.hu) dst[in.q] = in.u;
+  if (in.h0) dst[in.k0] = cells8_expand(in.d0);
+  if (in.h1) dst[in.k0 + AIE_NT] = cells8_expand(in.d1);
+  if (in.h2) dst[in.k0 + 2 * AIE_NT] = cells8_expand(in.d2);
+  for (int qq = in.q + st; qq < nq; qq += st) dst[qq] = src[qq];
+  for (int k = in.k0 + 3 * AIE_NT; k < q0; k += AIE_NT) dst[k] = cells8_expand(plane[k]);
 }
 // ... and the cell units themselves, over what the plane gave: the launch found obs_valid == 0, so something outside the
 // kernels may have edited the words and the plane is not to be trusted.  Such a launch writes the whole plane on its

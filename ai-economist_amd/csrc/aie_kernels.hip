@@ -172,20 +172,25 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
     A.hist_dirty = 0;
     A.tax_dirty = false;
     int act_err = 0;
-    if (!(skip & AIE_DEV_SKIP_ACTION_DECODE)) act_err = decode_actions(c, A, act_a, act_p, arena);  // (c.act_p is LDS scratch)
+    // Everything this wave fetches ahead of barrier (2) is asked for before anything is waited for: a lane's action
+    // word and planner word (action_words_request), its unit of the record and its plane dwords -- or, without the
+    // plane, its first three units (load_record_step_request).  The decode waits for the two words alone, the loads
+    // behind them stay in flight under it; then the LDS writes.
+    // (profiles/prologue_loads_ab.txt, one MI355X, 4096 replicas: decode_actions' two load-wait-decode rounds and then
+    // the record batch, 19.37 us per launch; both action words at once, ahead of the record batch, 18.96; everything in
+    // one batch, as here, 18.89.  Round 6 had measured the opposite -- 22.5 -> 23.5 us, milder orders 22.7 and 22.9 --
+    // on the word-per-cell image of 4.3 KB, whose copy was a loop of load, wait, LDS write per unit; with the loads of a
+    // lane in flight together the same holds without the plane: ten agents 35.66 -> 35.16 us.)
+    ActionWords aw = {0, 0, false};
+    if (!(skip & AIE_DEV_SKIP_ACTION_DECODE)) aw = action_words_request(c, act_a, act_p, arena);
+    const RecordIn rin = load_record_step_request(c, arena, 0, 2);
+    if (!(skip & AIE_DEV_SKIP_ACTION_DECODE)) act_err = decode_actions(c, A, act_a, act_p, arena, &aw);  // (c.act_p is LDS scratch)
     else A.act = 0;
     if (TRACE && R.dev_trace && c.tid == 0) R.dev_trace[12 * blockIdx.x] = wall_clock64();
     if (TRACE && R.dev_trace && c.tid == 0) R.dev_trace[12 * blockIdx.x + 9] = wall_clock64();
-    // (round 6, tools/ab2.sh: requesting the action words and the wave's whole share of the image before anything waits
-    // -- the loop below comes out as load, wait, LDS write per unit, behind decode_actions' two load-wait-decode rounds --
-    // made the launch SLOWER, 22.5 -> 23.5 us, and so did milder orders (both action loads first: 22.7; the record ahead of
-    // the decode: 22.9): 4096 workgroups start together, and what their first microseconds are short of is the memory
-    // system's capacity for requests, not patience -- the loop's own pace spreads them.  That was the word-per-cell image
-    // of 4.3 KB; with the cells' byte plane the image is 2.5 KB and load_record_step's loads, requested together, are
-    // 0.35 us FASTER than with a wait each: aie_gtb_state.h)
-    load_record_step(c, arena, 0, 2);
+    load_record_step_commit(c, arena, 2, rin);
     __syncthreads();  // (2) the record is in LDS
-    // (the cells came as bytes, aie_gtb_state.h: load_record_step -- unless something outside the kernels touched the
+    // (the cells came as bytes, aie_gtb_state.h: load_record_step_request -- unless something outside the kernels touched the
     // state: then both waves fetch the words, and a change log that starts out overflowed makes the way out write every
     // cell and the whole plane.  Uniform over the workgroup: nobody writes obs_valid before barrier (4).)
     const bool cells_stale = P.o_cells8 != 0 && uni(*R_I32(c, o_obs_valid)) == 0;
@@ -278,18 +283,31 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
     MT m;
     mt_init(m, P);
     const int gpos = *reinterpret_cast<const int32_t*>(grec + P.o_mt_pos);
-    load_record_step(c, arena, 1, 2);
-    // behind its share of the copy: the words the components will draw -> the LDS draw window (two or three rows of the
-    // generator's state, fetched from HBM; the state itself follows while the components run)
-    if (skip & AIE_DEV_SKIP_DRAW_WINDOW) {}  // (development: the load phase without the draw window)
-    else if (FAST) draw_window_publish_fast(draw_w, draw_cap, (uint32_t)uni((int)gkey[0]), (uint32_t)uni((int)gkey[1]), (uint32_t)uni((int)gkey[2]), uni(gpos), c.tid);
-    else draw_window_publish_from_hbm(draw_w, draw_cap, gkey, uni(gpos), c.tid);
-
-    if (SPEC >= 0 && const_tables_in_lds(P)) {
-      // the small constant tables (Ctx.rtab / mtab) -> LDS, published by the barrier below
-      if (P.has_tax && P.c.tax_model == AIE_TAX_MODEL_WRAPPER)
-        for (int q = c.tid; q < P.c.tax_n_disc_rates; q += AIE_NT) const_cast<double*>(c.rtab)[q] = R.c.tax_disc_rates[q];
-      for (int q = c.tid; q < P.MA; q += AIE_NT) const_cast<uint32_t*>(c.mtab)[q] = P.mask_test[q];
+    // Everything this wave fetches ahead of barrier (2) is asked for before anything is waited for: its unit of the
+    // record and a lane's first entry of the two small constant tables (Ctx.rtab / mtab -> LDS) at once, then -- they
+    // hang on the position, a scalar load -- the words the components will draw (up to three rows of the generator's
+    // state; the state itself follows while the components run).  One wait, then the LDS writes.
+    const bool TABS = SPEC >= 0 && const_tables_in_lds(P);
+    const bool RATES = TABS && P.has_tax && P.c.tax_model == AIE_TAX_MODEL_WRAPPER;
+    const bool ROWS = !FAST && !(skip & AIE_DEV_SKIP_DRAW_WINDOW);  // (development: the load phase without the draw window)
+    const RecordIn rin = load_record_step_request(c, arena, 1, 2);
+    double rate0 = 0.0;
+    uint32_t mask0 = 0u;
+    if (RATES && c.tid < P.c.tax_n_disc_rates) rate0 = R.c.tax_disc_rates[c.tid];
+    if (TABS && c.tid < P.MA) mask0 = P.mask_test[c.tid];
+    DrawRows rows = {{0u, 0u, 0u}};
+    if (ROWS) rows = draw_rows_request(draw_cap, gkey, uni(gpos), c.tid);
+    load_record_step_commit(c, arena, 2, rin);
+    if (ROWS) draw_rows_commit(draw_w, draw_cap, rows, gkey, uni(gpos), c.tid);
+    else if (FAST && !(skip & AIE_DEV_SKIP_DRAW_WINDOW))  // (the counter stream: computed, nothing to fetch)
+      draw_window_publish_fast(draw_w, draw_cap, (uint32_t)uni((int)gkey[0]), (uint32_t)uni((int)gkey[1]), (uint32_t)uni((int)gkey[2]), uni(gpos), c.tid);
+    if (RATES) {
+      if (c.tid < P.c.tax_n_disc_rates) const_cast<double*>(c.rtab)[c.tid] = rate0;
+      for (int q = c.tid + AIE_NT; q < P.c.tax_n_disc_rates; q += AIE_NT) const_cast<double*>(c.rtab)[q] = R.c.tax_disc_rates[q];
+    }
+    if (TABS) {
+      if (c.tid < P.MA) const_cast<uint32_t*>(c.mtab)[c.tid] = mask0;
+      for (int q = c.tid + AIE_NT; q < P.MA; q += AIE_NT) const_cast<uint32_t*>(c.mtab)[q] = P.mask_test[q];
     }
     __syncthreads();  // (2)
     if (P.o_cells8 != 0 && uni(*R_I32(c, o_obs_valid)) == 0) {  // (the first wave's cells_stale)
