@@ -271,6 +271,17 @@ __device__ __forceinline__ void buf_store_f32x4(BufRsrc r, float a, float b, flo
   const u32x4 v = {__float_as_uint(a), __float_as_uint(b), __float_as_uint(c), __float_as_uint(d)};
   __builtin_amdgcn_raw_buffer_store_b128(v, r, voff + soff, 0, 0);
 }
+// 16 bytes, write-through (aux 16 = sc1: `buffer_store_dwordx4 ... sc1`): the line leaves the XCD's L2 with the store
+// instead of staying dirty until the end of the launch, whose write-back the next launch on the stream waits for.  For
+// bytes that nothing in the launch reads again, and for 16-byte stores ONLY: a narrower sc1 store is one fabric write
+// each, 2.7 (8 bytes) to 6 times (4 bytes) the time per byte.  No scalar offset register (buf_store_f32x4).
+// It pays in the middle of a wave's work, not as its last act: the generator's rows gain 0.40 us per launch of BASELINE
+// configs[1] (store_generator_rows), the record image behind the last barrier LOSES 0.09 us on its own and stays plain
+// (profiles/record_write_through_ab.txt).
+__device__ __forceinline__ void buf_store_u32x4_wt(BufRsrc r, uint4 v, int voff) {
+  const u32x4 d = {v.x, v.y, v.z, v.w};
+  __builtin_amdgcn_raw_buffer_store_b128(d, r, voff, 0, 16);
+}
 // 16 bytes with dword alignment: global dwordx4 accesses need no more on gfx950
 struct __attribute__((packed, aligned(4))) f32x4_a4 { float x, y, z, w; };
 
@@ -387,8 +398,27 @@ __device__ __forceinline__ void store_record(const Ctx& c, uint8_t* __restrict__
   for (int j = 0; j < 9; ++j) key[64 * j + c.tid] = m.r[j];
   if (c.tid < 48) key[576 + c.tid] = m.r[9];
 }
-__device__ __forceinline__ void store_generator_rows(const Ctx& c, uint8_t* __restrict__ arena, const MT& m) {
+// The step kernel's second wave, behind the regeneration.  `from_window`: the LDS window holds the rows (the result of
+// scenario_step_regen) -- 624 words are 156 16-byte units and o_mt is 16-byte aligned, so a lane sends three units,
+// write-through (buf_store_u32x4_wt: nothing in the launch reads the rows again) where it sent ten dwords; the
+// descriptor ends with word 623, the source count starts right behind it.  Everyone else -- the row-by-row
+// regeneration, a skipped regeneration, records without the window -- keeps the ten dword stores, and those stay plain.
+// (One MI355X, BASELINE configs[1] at 4096 replicas: 18.87 -> 18.47 us per launch; the same three stores WITHOUT the
+// write-through bit 18.85 -- the width alone is nothing, the 2.5 KB per replica that no longer wait dirty in L2 for the
+// end of the launch are the gain.)
+__device__ __forceinline__ void store_generator_rows(const Ctx& c, uint8_t* __restrict__ arena, const MT& m,
+                                                     bool from_window = false) {
   if (rng_fast(c.P)) return;
+  if (from_window && c.mtwin) {
+    const BufRsrc rows = make_rsrc(arena + (int64_t)c.e * c.P.rec_bytes + c.P.o_mt, AIE_MT_N * 4);
+    const uint4* win = reinterpret_cast<const uint4*>(c.mtwin);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int q = k * AIE_NT + c.tid;
+      if (q < AIE_MT_N / 4) buf_store_u32x4_wt(rows, win[q], q << 4);
+    }
+    return;
+  }
   uint32_t* key = reinterpret_cast<uint32_t*>(arena + (int64_t)c.e * c.P.rec_bytes + c.P.o_mt);
 #pragma unroll
   for (int j = 0; j < 9; ++j) key[64 * j + c.tid] = m.r[j];

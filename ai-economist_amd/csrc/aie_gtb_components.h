@@ -844,7 +844,9 @@ __device__ __forceinline__ SrcList src_list_from_arena(const Ctx& c, const uint8
   for (int k = 0; k < AIE_SRC_CAP / AIE_NT; ++k) L.d[k] = (int)lst[k * AIE_NT + c.tid];  // (entries past the count are zero)
   return L;
 }
-__device__ __forceinline__ void scenario_step_regen(const Ctx& c, MT& m, const SrcList& src) {
+// Returns whether the generator's LDS window (Ctx.mtwin) holds the rows as this call leaves them, words 0 .. 623 in
+// order: store_generator_rows then sends them out from there.  Only the sparse MT19937 path with the window does.
+__device__ __forceinline__ bool scenario_step_regen(const Ctx& c, MT& m, const SrcList& src) {
   if (c.full && c.snap) {  // P.regen_general: the planes the reference convolves, before any of this step's respawns
     const int HW = c.P.HW, stride = (HW + 15) / 16 * 16;
     const uint8_t* cb = reinterpret_cast<const uint8_t*>(R_CELLS(c));
@@ -860,7 +862,7 @@ __device__ __forceinline__ void scenario_step_regen(const Ctx& c, MT& m, const S
   if (S > AIE_SRC_CAP) {
     if (m.fast && m.pos < AIE_MT_N) mt_fast_rows(m, c.tid);  // (the counter stream keeps no rows between steps)
     scenario_step_regen_rows(c, m);
-    return;
+    return false;
   }
   const int lane = c.tid;
   const int total = 4 * c.P.HW;
@@ -885,7 +887,7 @@ __device__ __forceinline__ void scenario_step_regen(const Ctx& c, MT& m, const S
     m.pos = pos0 + total - last_win * AIE_MT_N;
     m.fblk += (uint32_t)last_win;
     AIE_WSYNC();
-    return;
+    return false;
   }
   int off_a[AIE_SRC_CAP / AIE_NT];
   uint32_t wa[AIE_SRC_CAP / AIE_NT], wb[AIE_SRC_CAP / AIE_NT];
@@ -933,6 +935,8 @@ __device__ __forceinline__ void scenario_step_regen(const Ctx& c, MT& m, const S
   for (int k = 0; k < AIE_SRC_CAP / AIE_NT; ++k)
     if (k < nchunk && off_a[k] >= 0) regen_cell(c, mt_temper(wa[k]), mt_temper(wb[k]), (off_a[k] - pos0) >> 1);
   AIE_WSYNC();
+  // (the loop above runs at least once, and its last round stored the rows behind the last twist: nothing twists after it)
+  return c.mtwin != nullptr;
 }
 
 }  // namespace aie

@@ -360,12 +360,13 @@ __device__ __forceinline__ void step_body(const aie_params* __restrict__ params,
     }
     m.pos = uni(*R_I32(c, o_mt_pos));
     if (REGEN) {
-      if (!(skip & AIE_DEV_SKIP_REGEN)) scenario_step_regen(c, m, src);
+      bool rows_in_window = false;  // (a skipped regeneration leaves the window as it was)
+      if (!(skip & AIE_DEV_SKIP_REGEN)) rows_in_window = scenario_step_regen(c, m, src);
       if (c.tid == 0) {
         *R_I32(c, o_mt_pos) = m.pos;
         if (FAST) R_U32(c, o_mt)[1] = m.fblk;
       }
-      if (!(skip & AIE_DEV_SKIP_RECORD_STORE)) store_generator_rows(c, arena, m);  // (the rows' registers are free from here on)
+      if (!(skip & AIE_DEV_SKIP_RECORD_STORE)) store_generator_rows(c, arena, m, rows_in_window);  // (the rows' registers are free from here on)
     }
     if (TRACE && R.dev_trace && c.tid == 0) R.dev_trace[12 * blockIdx.x + 6] = wall_clock64();
     AIE_WSYNC();
