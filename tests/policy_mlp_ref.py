@@ -20,6 +20,89 @@ U = 2.0 ** -24
 # (F, H, M): C2's agents and planner, the smallest, two ragged ones
 SHAPES = [(136, 128, 50), (86, 128, 154), (1, 16, 1), (7, 32, 3), (33, 256, 67)]
 
+# ---- the widths the kernel's loops branch on (csrc/aie_kernels_mlp.hip: mlp_tiles, mlp_layer) ----
+# A layer with K inputs walks them in k-steps of 4, a staged chunk of CHUNK columns at a time (the first layer; a hidden
+# layer's K = H <= CHUNK is one chunk).  Of a chunk's steps the first `nfull` lie wholly inside K; mlp_tiles takes
+# G = nfull // KC whole groups of KC steps without a branch -- its loop has four shapes: G = 0, G = 1, G even, G odd and >= 3
+# (the `g + 2 < G` refill, then the left-over group) -- and the `tail` steps behind them under their count (the last of them
+# ragged where K is no multiple of 4).  The workgroup's four waves share a layer's NT = ceil(N / 16) output tiles in groups
+# of eight: NT = 3, 5, 9, 13 leave waves without a tile inside loops that hold barriers.  The value head is column M of the
+# head's matrix: where M is a multiple of 16 it opens a tile of its own.
+KC, STEP, CHUNK, TILE = 8, 4, 256, 16  # MLP_KC, the MFMA's k, AIE_MLP_CHUNK, the MFMA's columns: test_policy_mlp_cpu.py reads them back
+EDGE_SHAPES = [(63, 48, 15), (64, 80, 16), (65, 96, 17), (96, 112, 63), (255, 144, 64), (256, 160, 65), (257, 208, 31),
+               (100, 224, 32), (12, 240, 48), (128, 64, 128), (40, 176, 5), (40, 192, 5)]
+
+
+def loop_shape(K):
+    """[(G, tail steps, ragged last step?)] per staged chunk of a layer with K inputs."""
+    out, kpad = [], -(-K // STEP) * STEP
+    for k0 in range(0, kpad, CHUNK):
+        nsteps = min(kpad - k0, CHUNK) // STEP
+        nfull = min((K - k0) // STEP, nsteps)
+        out.append((nfull // KC, nsteps - nfull // KC * KC, nfull < nsteps))
+    return out
+
+
+def tiles(N):
+    return -(-N // TILE)
+
+
+def loop_class(G):
+    return "G=0" if G == 0 else "G=1" if G == 1 else "G even" if G % 2 == 0 else "G odd >= 3"
+
+
+def coverage_table(shapes=None):
+    """One line per shape: per layer the (G, tail) of every chunk and NT (the head's with the value column and without)."""
+    lines = []
+    for F, H, M in (EDGE_SHAPES if shapes is None else shapes):
+        first = " + ".join("G %d tail %d%s" % (g, t, "r" if r else "") for g, t, r in loop_shape(F))
+        (g, t, _), = loop_shape(H)
+        lines.append("(%3d, %3d, %3d)  first: %s, NT %d;  hidden and head: G %d tail %d;  hidden NT %d, head NT %d / %d" % (
+            F, H, M, first, tiles(H), g, t, tiles(H), tiles(M + 1), tiles(M)))
+    return "\n".join(lines)
+
+
+# coverage_table() of EDGE_SHAPES ("r": the tail's last step is ragged; head NT with / without the value column);
+# test_policy_mlp_cpu.py holds this text to the function and asserts the classes below it
+EDGE_COVERAGE = """\
+( 63,  48,  15)  first: G 1 tail 8r, NT 3;  hidden and head: G 1 tail 4;  hidden NT 3, head NT 1 / 1
+( 64,  80,  16)  first: G 2 tail 0, NT 5;  hidden and head: G 2 tail 4;  hidden NT 5, head NT 2 / 1
+( 65,  96,  17)  first: G 2 tail 1r, NT 6;  hidden and head: G 3 tail 0;  hidden NT 6, head NT 2 / 2
+( 96, 112,  63)  first: G 3 tail 0, NT 7;  hidden and head: G 3 tail 4;  hidden NT 7, head NT 4 / 4
+(255, 144,  64)  first: G 7 tail 8r, NT 9;  hidden and head: G 4 tail 4;  hidden NT 9, head NT 5 / 4
+(256, 160,  65)  first: G 8 tail 0, NT 10;  hidden and head: G 5 tail 0;  hidden NT 10, head NT 5 / 5
+(257, 208,  31)  first: G 8 tail 0 + G 0 tail 1r, NT 13;  hidden and head: G 6 tail 4;  hidden NT 13, head NT 2 / 2
+(100, 224,  32)  first: G 3 tail 1, NT 14;  hidden and head: G 7 tail 0;  hidden NT 14, head NT 3 / 2
+( 12, 240,  48)  first: G 0 tail 3, NT 15;  hidden and head: G 7 tail 4;  hidden NT 15, head NT 4 / 3
+(128,  64, 128)  first: G 4 tail 0, NT 4;  hidden and head: G 2 tail 0;  hidden NT 4, head NT 9 / 8
+( 40, 176,   5)  first: G 1 tail 2, NT 11;  hidden and head: G 5 tail 4;  hidden NT 11, head NT 1 / 1
+( 40, 192,   5)  first: G 1 tail 2, NT 12;  hidden and head: G 6 tail 0;  hidden NT 12, head NT 1 / 1"""
+
+
+def edge_coverage(shapes=None):
+    """The classes the shapes reach, as a set of names (test_policy_mlp_cpu.py asserts the ones the kernel's loops have)."""
+    got = set()
+    for F, H, M in (EDGE_SHAPES if shapes is None else shapes):
+        for g, t, r in loop_shape(F):
+            got.add("first layer: %s" % loop_class(g))
+        (g, t, _), = loop_shape(H)
+        got.add("hidden layer: %s" % loop_class(g))
+        if g and g % 2 == 0 and t == KC // 2:
+            got.add("hidden layer: G even, a tail of %d steps" % t)
+        if g % 2 == 1 and g >= 3 and t == KC // 2:
+            got.add("hidden layer: G odd >= 3, a tail of %d steps" % t)
+        got.add("NT=%d" % tiles(H))
+        got.add("head NT=%d" % tiles(M + 1))
+        if M % TILE == 0:
+            got.add("the value column alone in a tile")
+        got.add("M=%d" % M)
+        got.add("F=%d" % F)
+        if F > CHUNK:
+            got.add("a second staged chunk")
+        if F % 64 == 0:
+            got.add("the bias row of the backward's [(F + 1), H] block alone in a 64-row group")
+    return got
+
 
 def fma32(a, b, c):
     """float32 fmaf(a, b, c), elementwise with broadcasting."""

@@ -2,7 +2,9 @@
 rollout.mlp_weights) against the header's helper compiled on the CPU (tests/test_policy_mlp_cpu.py holds it to an
 independent transcription):
 
-  * values: the five shapes of policy_mlp_ref.SHAPES as the planner class at 1 .. 130 rows (either row tile meets its
+  * values: the shapes of policy_mlp_ref.SHAPES and EDGE_SHAPES (the widths at which the kernel's loops take another shape:
+    an odd number of k-step groups, a tail of four steps, waves without an output tile, the value column alone in a tile,
+    F at the staged chunk's edge) as the planner class at 1 .. 130 rows (either row tile meets its
     edge) with another shape as the agents' class in the same launch, each class alone, the value column on and off --
     float == with no NaN anywhere, every entry in range written (the buffers start as NaN), 64 sentinel rows behind them
     untouched; COVID's 51 agents give the agents' class row counts that are no multiple of 4;
@@ -85,15 +87,23 @@ def _hold(shim, what, x, W, lg, v, rows):
         assert np.isnan(gv[rows:]).all(), "%s: wrote behind the values" % what
 
 
+ALL_SHAPES = ref.SHAPES + ref.EDGE_SHAPES  # (the edge shapes: the widths the kernel's loops branch on)
+
+
+def _pair(si):
+    """The planner's shape and the agents': the next one of the same list."""
+    group = ref.SHAPES if si < len(ref.SHAPES) else ref.EDGE_SHAPES
+    return ALL_SHAPES[si], group[(group.index(ALL_SHAPES[si]) + 1) % len(group)]
+
+
 @pytest.mark.parametrize("value", [True, False], ids=["value", "novalue"])
-@pytest.mark.parametrize("si", range(len(ref.SHAPES)), ids=["%dx%dx%d" % s for s in ref.SHAPES])
+@pytest.mark.parametrize("si", range(len(ALL_SHAPES)), ids=["%dx%dx%d" % s for s in ALL_SHAPES])
 def test_device_equals_the_header(shim, si, value):
     import torch
 
     be = _be()
     n = be.n
-    Fp, Hp, Mp = ref.SHAPES[si]
-    Fa, Ha, Ma = ref.SHAPES[(si + 1) % len(ref.SHAPES)]  # the agents' class: another shape in the same launch
+    (Fp, Hp, Mp), (Fa, Ha, Ma) = _pair(si)  # the agents' class: another shape in the same launch
     Wp = ref.random_weights(Fp, Hp, Mp, seed=100 + si, value=value)
     Wa = ref.random_weights(Fa, Ha, Ma, seed=200 + si, value=not value)  # (and the other choice of the value column)
     dWp, dWa = _weights(Wp), _weights(Wa)
@@ -109,7 +119,7 @@ def test_device_equals_the_header(shim, si, value):
             got = be.policy_mlp_forward(dxa if use_a else None, dxp if use_p else None, dWa, dWp, out=out)
             torch.cuda.synchronize()
             assert all((g is None and o is None) or g is o for g, o in zip(got, out))
-            what = "%s rows %d (%s)" % (ref.SHAPES[si], B, which)
+            what = "%s rows %d (%s)" % (ALL_SHAPES[si], B, which)
             if use_p:
                 _hold(shim, "planner " + what, xp, Wp, lp, vp, B)
             else:

@@ -5,7 +5,9 @@ transcription):
   * values: each shape of policy_mlp_ref.SHAPES as the planner class with the next one as the agents' class in the same
     call, each class alone, the value column on and off, at B = 1 .. 2 SEG + 17 (the agents' 4 B rows cross the row tile's
     and the segment's edges) -- float == with no NaN anywhere, every gradient entry written (the buffers start as NaN),
-    64 sentinel floats behind each gradient and 4 KiB behind the workspace untouched; COVID's 51 agents once;
+    64 sentinel floats behind each gradient and 4 KiB behind the workspace untouched; COVID's 51 agents once; the shapes of
+    policy_mlp_ref.EDGE_SHAPES (the widths the kernels' loops branch on) the same way at fewer row counts, two of them at
+    the segment's edge;
   * a leading dimension larger than F with an address that is only 8-byte aligned equals the contiguous copy; F beyond one
     and two staged chunks with H = 256;
   * two calls, and a call with a second, larger workspace, give the same bits;
@@ -133,17 +135,31 @@ def _operands(F, H, M, rows, seed, value):
     return x, W, gl, gv
 
 
+ALL_SHAPES = ref.SHAPES + ref.EDGE_SHAPES  # (the edge shapes: the widths the kernels' loops branch on)
+# the edge shapes that also run at the segment's edge: F = 64 (the bias row of the [(F + 1), H] block alone in a 64-row group)
+# with H = 80, and F past one staged chunk with H = 208 -- the planner's rows SEG - 1, SEG, SEG + 1, the agents' four times that
+SEG_EDGE_SHAPES = [(64, 80, 16), (257, 208, 31)]
+
+
+def _pair(si):
+    """The planner's shape and the agents': the next one of the same list."""
+    group = ref.SHAPES if si < len(ref.SHAPES) else ref.EDGE_SHAPES
+    return ALL_SHAPES[si], group[(group.index(ALL_SHAPES[si]) + 1) % len(group)]
+
+
 @pytest.mark.parametrize("value", [True, False], ids=["value", "novalue"])
-@pytest.mark.parametrize("si", range(len(ref.SHAPES)), ids=["%dx%dx%d" % s for s in ref.SHAPES])
+@pytest.mark.parametrize("si", range(len(ALL_SHAPES)), ids=["%dx%dx%d" % s for s in ALL_SHAPES])
 def test_device_equals_the_header(shim, si, value):
     import torch
 
     be = _be()
     n, SEG = be.n, _seg()
     assert n == 4
-    Fp, Hp, Mp = ref.SHAPES[si]
-    Fa, Ha, Ma = ref.SHAPES[(si + 1) % len(ref.SHAPES)]  # the agents' class: the next shape in the same call
-    for B in (1, 3, 31, 33, 65, SEG - 1, SEG, SEG + 1, 2 * SEG + 17):
+    (Fp, Hp, Mp), (Fa, Ha, Ma) = _pair(si)  # the agents' class: the next shape in the same call
+    counts = (1, 3, 31, 33, 65, SEG - 1, SEG, SEG + 1, 2 * SEG + 17)
+    if si >= len(ref.SHAPES):  # the widths are what is new: both row tiles' edges, the agents' 4 B rows past a segment at 65
+        counts = (1, 3, 33, 65) + ((SEG - 1, SEG, SEG + 1) if ALL_SHAPES[si] in SEG_EDGE_SHAPES else ())
+    for B in counts:
         cp = _Class(*_operands(Fp, Hp, Mp, B, 100 + si + B, value))
         ca = _Class(*_operands(Fa, Ha, Ma, B * n, 200 + si + B, not value))  # (and the other choice of the value column)
         want = {}
@@ -151,7 +167,7 @@ def test_device_equals_the_header(shim, si, value):
             ca.clear(), cp.clear()
             use_a, use_p = which != "planner", which != "agents"
             rc, ws, use = _call(be, B, ca if use_a else None, cp if use_p else None)
-            what = "%s B %d (%s)" % (ref.SHAPES[si], B, which)
+            what = "%s B %d (%s)" % (ALL_SHAPES[si], B, which)
             assert rc == 0, (what, be.lib.aie_last_error(be.handle))
             assert bool(torch.isnan(ws[use:]).all()), what + ": wrote behind the workspace"
             for name, cls, used in (("planner", cp, use_p), ("agents", ca, use_a)):

@@ -1,7 +1,8 @@
 """The PPO rollout seam on the device: aie_gae, aie_trajectory_store, rollout.Trajectory and GraphedStep(trajectory=...).
 
   * aie_gae against the plain NumPy float32 loop (tests/gae_ref.py) bit for bit on synthetic logs the test uploads: the
-    three scenario families' (E, n), T = 1, 7, 200, a ring that wraps from first_slot != 0, an all-done row, NaN behind done
+    three scenario families' (E, n), T = 1, 7, 200 and the kernel's chunk edges (8, 9, 15, 16, 17, 24, 33 steps), a ring that
+    wraps from first_slot != 0 -- inside a chunk of 8 steps and exactly between two --, an all-done row, NaN behind done
     steps, every NULL combination, and the invalid arguments (refused, nothing launched);
   * aie_trajectory_store, eager, 7 steps into 4 slots with auto-reset: every slot equals the host snapshot taken just before
     its store, the counters are k % 4 -- segments of 4 B, 344 B, a 16-byte-aligned size, a destination 4 bytes off, a
@@ -96,14 +97,28 @@ def _same_bits(got, want, what):
         what, bad.size, want.size, bad[0], got.reshape(-1)[bad[0]], want.reshape(-1)[bad[0]])
 
 
-@pytest.mark.parametrize("T", [1, 7, 200])
+def _ring_placements(T):
+    """(n_slots, first_slot): a ring that wraps (T >= 3); the trajectory's own; full wrap; then the kernel's chunk edges.  Time
+    runs backwards from step T - 1 in chunks of U = 8 steps (csrc/aie_kernels_rollout.hip: AIE_GAE_U), so a chunk starts at a
+    step t = T (mod 8); the ring wraps in front of step n_slots - first."""
+    out = [(T + 3, T + 1), (T, 0), (T, T - 1)]
+    if T >= 4:
+        out.append((T + 1, T - 3))   # the wrap in front of step 4: inside a chunk unless T = 4 (mod 8)
+    if T >= 9:
+        out.append((T + 3, T - 5))   # first = n_slots - 8: steps 0 .. 7 end the ring, step 8 is slot 0
+        out.append((T, 8))           # the wrap in front of step T - 8: exactly between the first two chunks the kernel takes
+    return out
+
+
+# 8, 9: one full chunk, and one more step; 15, 16, 17: both register buffers, and one more step; 24, 33: an odd number of chunks
+@pytest.mark.parametrize("T", [1, 7, 200, 8, 9, 15, 16, 17, 24, 33])
 @pytest.mark.parametrize("case", list(GAE_ENVS))
 def test_gae_equals_the_numpy_float32_loop(case, T):
     import torch
 
     be = _gae_env(case)
     E, n = be.E, be.n
-    for n_slots, first in ((T + 3, T + 1), (T, 0), (T, T - 1)):  # a ring that wraps (T >= 3); the trajectory's own; full wrap
+    for n_slots, first in _ring_placements(T):
         log, va, vp = _synthetic(E, n, T, n_slots, first, 100 * T + n_slots + first)
         want = gae_ref.from_log(log, first, T, va, vp, GAMMA, LAM)
         got = be.gae(T, torch.tensor(log, device=DEV), torch.tensor(va, device=DEV), torch.tensor(vp, device=DEV), GAMMA, LAM,

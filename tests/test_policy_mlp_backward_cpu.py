@@ -81,12 +81,14 @@ def test_the_constant_is_the_bindings(shim):
 
 
 @pytest.mark.parametrize("value", [True, False], ids=["value", "novalue"])
-@pytest.mark.parametrize("shape", ref.SHAPES, ids=lambda s: "%dx%dx%d" % s)
+@pytest.mark.parametrize("shape", ref.SHAPES + ref.EDGE_SHAPES, ids=lambda s: "%dx%dx%d" % s)
 def test_header_equals_the_transcription(shim, shape, value):
     F, H, M = shape
     SEG = shim.shim_seg()
     largest = sorted(ref.SHAPES, key=lambda s: s[0] * s[1] + s[1] * s[1] + s[1] * s[2])[-2:]
     counts = [1, 33, SEG - 1, SEG, SEG + 1] + ([] if shape in largest else [2 * SEG + 17])
+    if shape in ref.EDGE_SHAPES:  # the widths are what is new: a short segment, and a whole one and a row
+        counts = [1, 33, SEG + 1]
     for i, rows in enumerate(counts):
         W = ref.random_weights(F, H, M, seed=7 * F + i, value=value, dead=True)
         x = bref.rows_with_zeros(rows, F, seed=11 * M + i)
@@ -117,7 +119,7 @@ def _torch_grads(x, W, gl, gv, m1, m2, dtype):
     return {k: t[k].grad.numpy() for k in t}
 
 
-@pytest.mark.parametrize("shape", ref.SHAPES, ids=lambda s: "%dx%dx%d" % s)
+@pytest.mark.parametrize("shape", ref.SHAPES + ref.EDGE_SHAPES, ids=lambda s: "%dx%dx%d" % s)
 def test_accuracy_within_the_derived_bound(shim, shape):
     import torch
 

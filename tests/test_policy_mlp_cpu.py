@@ -2,8 +2,9 @@
 
   * the fma emulation of tests/policy_mlp_ref.py against the C library's fmaf on 10^5 random triples, halfway cases
     (c = -a b rounded, plus or minus one ulp) among them;
-  * values: the header's helper, compiled here with the host C compiler, == the numpy transcription on the five shapes of
-    policy_mlp_ref.SHAPES with 1 - 70 rows, the value column on and off, inputs planted with zeros, dead ReLU columns and
+  * policy_mlp_ref.EDGE_SHAPES reaches every shape of the device kernel's loops (worked out from the kernel's constants);
+  * values: the header's helper, compiled here with the host C compiler, == the numpy transcription on the shapes of
+    policy_mlp_ref.SHAPES and EDGE_SHAPES with 1 - 70 rows, the value column on and off, inputs planted with zeros, dead ReLU columns and
     entries near 1e-38 and 1e30 (float ==: there is no NaN anywhere);
   * accuracy: every logit and value within the running bound of a float32 evaluation around the float64 pass on the same
     float32 numbers (policy_mlp_ref.forward_f64: derived, not measured) -- and torch's CPU float32 MLP inside the same
@@ -105,8 +106,37 @@ def test_fma_emulation_is_the_c_librarys(shim):
         bad.size, a[bad[0]], b[bad[0]], c[bad[0]], got[bad[0]], want[bad[0]])
 
 
+def test_edge_shapes_cover_the_kernels_loop_shapes():
+    """policy_mlp_ref.EDGE_SHAPES reaches every shape of the kernel's loops -- worked out from the kernel's own constants, read
+    back from the sources here -- and the table beside the list is what the function gives."""
+    import re
+
+    src = open(os.path.join(CSRC, "aie_kernels_mlp.hip")).read()
+    hdr = open(os.path.join(CSRC, "aie_trainer_math.h")).read()
+    assert int(re.search(r"constexpr int MLP_KC = (\d+);", src).group(1)) == ref.KC
+    assert int(re.search(r"#define AIE_MLP_CHUNK (\d+)", hdr).group(1)) == ref.CHUNK
+    assert "mfma_f32_16x16x4f32" in src and (ref.TILE, ref.STEP) == (16, 4)
+    assert ref.coverage_table() == ref.EDGE_COVERAGE
+    assert all(16 <= H <= 256 and H % 16 == 0 and 1 <= F <= 1024 and 1 <= M <= 1024 for F, H, M in ref.EDGE_SHAPES)
+    got = ref.edge_coverage()
+    want = ["hidden layer: G odd >= 3", "first layer: G odd >= 3", "hidden layer: G even, a tail of 4 steps",
+            "hidden layer: G odd >= 3, a tail of 4 steps", "hidden layer: G even", "hidden layer: G=1", "first layer: G=0",
+            "first layer: G=1", "first layer: G even", "a second staged chunk", "the value column alone in a tile",
+            "the bias row of the backward's [(F + 1), H] block alone in a 64-row group"]
+    want += ["NT=%d" % t for t in (3, 5, 9, 13)] + ["M=%d" % m for m in (15, 16, 17, 32, 48, 63, 64, 65, 128)]
+    want += ["F=%d" % f for f in (63, 64, 65, 255, 256, 257)]
+    assert not [w for w in want if w not in got], [w for w in want if w not in got]
+    # G odd and >= 3: in a hidden layer at H = 96, 160 and 224, in the first layer at F = 96 .. 127
+    odd = lambda K: [g for g, _, _ in ref.loop_shape(K)][0] % 2 == 1 and ref.loop_shape(K)[0][0] >= 3  # noqa: E731
+    assert all(odd(H) for H in (96, 160, 224)) and {H for _, H, _ in ref.EDGE_SHAPES} >= {96, 160, 224}
+    assert all(odd(F) for F in range(96, 128)) and any(96 <= F < 128 for F, _, _ in ref.EDGE_SHAPES)
+    # what SHAPES alone reaches: G = 0, 1, 4, 8 in the hidden layers and NT = 1, 2, 8, 16 -- none of the above
+    old = ref.edge_coverage(ref.SHAPES)
+    assert not old & {"hidden layer: G odd >= 3", "NT=3", "NT=5", "NT=9", "NT=13", "the value column alone in a tile"}
+
+
 @pytest.mark.parametrize("value", [True, False])
-@pytest.mark.parametrize("shape", ref.SHAPES, ids=lambda s: "%dx%dx%d" % s)
+@pytest.mark.parametrize("shape", ref.SHAPES + ref.EDGE_SHAPES, ids=lambda s: "%dx%dx%d" % s)
 def test_header_equals_the_transcription(shim, shape, value):
     F, H, M = shape
     for i, rows in enumerate((1, 33, 70)):
@@ -125,7 +155,7 @@ def test_header_equals_the_transcription(shim, shape, value):
             assert np.abs(want_l[5]).max() > 1e20
 
 
-@pytest.mark.parametrize("shape", ref.SHAPES, ids=lambda s: "%dx%dx%d" % s)
+@pytest.mark.parametrize("shape", ref.SHAPES + ref.EDGE_SHAPES, ids=lambda s: "%dx%dx%d" % s)
 def test_accuracy_within_the_derived_bound(shim, shape):
     import torch
 
