@@ -2,7 +2,8 @@
 
 Only plain C types cross this boundary: pointers, sizes, ints, doubles.  torch is used
 by env.py (the environment's calls) and _trainer_ops.py (the trainer operators' calls and
-their argument structures: AieTrajSegment, AiePpoClass, AieMlpClass, AieMlpGradClass, AieOptGroup)
+their argument structures: AieTrajSegment, AiePpoClass, AieMlpClass, AieMlpGradClass, AieConvClass,
+AieConvGradClass, AieOptGroup)
 purely as the owner of device memory / streams.
 """
 import ctypes as C
@@ -192,6 +193,18 @@ class AieMlpGradClass(C.Structure):  # aie_mlp_grad_class
                [(k, C.c_void_p) for k in ("g_logits", "g_values", "gw1", "gb1", "gw2", "gb2", "gw3", "gb3", "gwv", "gbv")]
 
 
+class AieConvClass(C.Structure):  # aie_conv_class
+    _fields_ = [("map", C.c_void_p), ("map_ld", C.c_int64), ("idx", C.c_void_p), ("idx_ld", C.c_int64)] + \
+               [(k, C.c_void_p) for k in ("emb", "w1", "b1", "w2", "b2")] + \
+               [("flat", C.c_void_p), ("flat_ld", C.c_int64), ("x_out", C.c_void_p), ("x_ld", C.c_int64)] + \
+               [(k, C.c_int32) for k in ("C_map", "D", "h", "w", "V", "F_flat")]
+
+
+class AieConvGradClass(C.Structure):  # aie_conv_grad_class
+    _fields_ = [("net", AieConvClass), ("g_feat", C.c_void_p), ("g_ld", C.c_int64)] + \
+               [(k, C.c_void_p) for k in ("gemb", "gw1", "gb1", "gw2", "gb2")]
+
+
 class AieOptTensor(C.Structure):  # aie_opt_tensor
     _fields_ = [(k, C.c_void_p) for k in ("w", "g", "m", "v")] + [("n", C.c_int64)]
 
@@ -207,6 +220,7 @@ OPT_MAX_TENSORS = 16   # AIE_OPT_MAX_TENSORS
 OPT_N_STATS = 4        # AIE_OPT_N_STATS
 OPT_STATE_BYTES = 32   # AIE_OPT_STATE_BYTES
 MLP_BWD_SEG = 256     # AIE_MLP_BWD_SEG
+CONV_F1, CONV_F2 = 16, 32  # AIE_CONV_F1, AIE_CONV_F2
 PPO_N_STATS = 8       # AIE_PPO_N_STATS
 PPO_MAX_WAVES = 8192  # AIE_PPO_MAX_WAVES
 
@@ -268,6 +282,15 @@ def bind(lib):
     lib.aie_policy_mlp_backward_workspace_bytes.argtypes = [vp, C.c_int64, C.POINTER(AieMlpGradClass), C.POINTER(AieMlpGradClass)]
     lib.aie_policy_mlp_backward.restype = C.c_int
     lib.aie_policy_mlp_backward.argtypes = [vp, C.c_int64, C.POINTER(AieMlpGradClass), C.POINTER(AieMlpGradClass), vp, C.c_int64, vp]
+    lib.aie_policy_mlp_input_grad.restype = C.c_int
+    lib.aie_policy_mlp_input_grad.argtypes = [vp, C.c_int64, C.POINTER(AieMlpGradClass), C.POINTER(AieMlpGradClass), vp, C.c_int64,
+                                              vp, C.c_int64, C.c_int32, vp, C.c_int64, C.c_int32, vp]
+    lib.aie_policy_conv_forward.restype = C.c_int
+    lib.aie_policy_conv_forward.argtypes = [vp, C.c_int64, C.POINTER(AieConvClass), vp]
+    lib.aie_policy_conv_backward_workspace_bytes.restype = C.c_int64
+    lib.aie_policy_conv_backward_workspace_bytes.argtypes = [vp, C.c_int64, C.POINTER(AieConvGradClass)]
+    lib.aie_policy_conv_backward.restype = C.c_int
+    lib.aie_policy_conv_backward.argtypes = [vp, C.c_int64, C.POINTER(AieConvGradClass), vp, C.c_int64, vp]
     lib.aie_adam_workspace_bytes.restype = C.c_int64
     lib.aie_adam_workspace_bytes.argtypes = [vp, C.POINTER(AieOptGroup), C.POINTER(AieOptGroup)]
     lib.aie_adam_step.restype = C.c_int
@@ -326,6 +349,7 @@ EXPORTED_SYMBOLS = [
     "aie_gae", "aie_trajectory_store", "aie_ppo_workspace_bytes", "aie_ppo_loss",
     "aie_policy_mlp_forward", "aie_policy_mlp_backward_workspace_bytes", "aie_policy_mlp_backward",
     "aie_adam_workspace_bytes", "aie_adam_step",
+    "aie_policy_mlp_input_grad", "aie_policy_conv_forward", "aie_policy_conv_backward_workspace_bytes", "aie_policy_conv_backward",
 ]
 STEP_HEAD, STEP_TAIL, STEP_OBSERVE, STEP_REBASE, STEP_RETAX = 1, 2, 4, 8, 16  # AIE_STEP_*
 STEP_REGEN, STEP_EMIT, STEP_CLOSE = 64, 128, 256  # the end of a step in three parts (scenario hooks run between them)

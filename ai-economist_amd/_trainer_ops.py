@@ -347,7 +347,148 @@ class TrainerOps:
         # (a refusal of the plan makes `need` its negative code: the call below then refuses too, and names itself)
         self._check(self.lib.aie_policy_mlp_backward(self.handle, B, ref(classes[0]), ref(classes[1]), ptr(ws),
                                                      ws.numel() * 4 if ws is not None else 0, self._stream()))
+        # what policy_mlp_input_grad, directly behind this call, reads: the classes (plain pointers: no tensor is kept alive
+        # by them; that call reads only w1 and the workspace), B and the workspace
+        self._mlp_bwd_last = (classes, B, ws)
         return res[0], res[1]
+
+    def policy_mlp_input_grad(self, ncols_a=None, ncols_p=None, out=None):
+        """aie_policy_mlp_input_grad: the gradient with respect to the first ncols columns of x, for a network in front of the
+        MLP -- ONE launch on the current stream, valid only DIRECTLY BEHIND policy_mlp_backward on the same stream: it reads
+        dz1 from that call's workspace and uses that call's classes (their pointers, not their tensors: the weights of that
+        call must still be alive, nothing else is read).  ncols_* None: the class is left out.  Returns
+        (g_x_a [rows_a, ncols_a], g_x_p [B, ncols_p]), None for a class left out; out=(g_x_a, g_x_p) fills the caller's
+        float32 device tensors [rows, >= ncols] with contiguous rows (any row stride) instead."""
+        import torch
+        fn = "policy_mlp_input_grad"
+        last = getattr(self, "_mlp_bwd_last", None)
+        if last is None:
+            raise ValueError("%s: call policy_mlp_backward first" % fn)
+        classes, B, ws = last
+        out = tuple(out) if out is not None else (None, None)
+        args, res = [], []
+        for who, cls, per, ncols, o in (("a", classes[0], self.n, ncols_a, out[0]), ("p", classes[1], 1, ncols_p, out[1])):
+            if ncols is None:
+                args += [None, 0, 0]
+                res.append(None)
+                continue
+            if cls is None:
+                raise ValueError("%s: ncols_%s without that class in the backward" % (fn, who))
+            rows = B * per
+            if o is None:
+                o = torch.empty((rows, int(ncols)), dtype=torch.float32, device=self.device)
+            elif not (o.dim() == 2 and o.dtype == torch.float32 and o.device == self.device and o.shape[0] == rows
+                      and o.shape[1] >= ncols and (o.shape[1] == 1 or o.stride(1) == 1)):
+                raise ValueError("%s: out's g_x_%s is a float32 device tensor [%d, >= %d] with contiguous rows" % (fn, who, rows, ncols))
+            args += [ptr(o), int(o.stride(0)) if rows > 1 else int(o.shape[1]), int(ncols)]
+            res.append(o)
+        self._check(self.lib.aie_policy_mlp_input_grad(self.handle, B, ref(classes[0]), ref(classes[1]), ptr(ws),
+                                                       ws.numel() * 4 if ws is not None else 0, *args, self._stream()))
+        return res[0], res[1]
+
+    def _conv_rows(self, fn, what, t, dtype, inner):
+        """A crop operand [rows, *inner] or [B, n, *inner] with each row's block contiguous and one row stride throughout: a
+        view, never a copy -> (the tensor, rows, the row stride in elements)."""
+        k = len(inner)
+        ok = getattr(t, "dtype", None) == dtype and t.device == self.device and t.dim() in (k + 1, k + 2) \
+            and tuple(t.shape[-k:]) == tuple(inner) and t[(0,) * (t.dim() - k)].is_contiguous() and t.numel() > 0
+        if ok and t.dim() == k + 2 and t.shape[0] > 1 and t.shape[1] > 1 and t.stride(0) != t.shape[1] * t.stride(1):
+            ok = False
+        if not ok:
+            raise ValueError("%s: %s is a %s device tensor [rows, %s] (or [B, n, ...]) whose rows are contiguous blocks one stride apart"
+                             % (fn, what, dtype, ", ".join(map(str, inner))))
+        rows = math.prod(t.shape[:-k])
+        lead = t.dim() - k
+        stride = t.stride(lead - 1) if t.shape[lead - 1] > 1 else (t.stride(0) if lead == 2 and t.shape[0] > 1 else math.prod(inner))
+        return t, rows, int(stride)
+
+    def _conv_operands(self, fn, map_, idx, w):
+        """What policy_conv_forward / policy_conv_backward share -> (a _cabi.AieConvClass without flat and x_out, the dict
+        of the five weight tensors, rows, NF)."""
+        import torch
+        get = w.get if hasattr(w, "get") else lambda k, w=w: getattr(w, k, None)  # noqa: E731
+        t = {k: get(k) for k in ("emb", "w1", "b1", "w2", "b2")}
+        if getattr(map_, "dim", lambda: 0)() < 4 or t["emb"] is None or t["emb"].dim() != 2:
+            raise ValueError("%s: map [rows, C_map, h, w] and conv_weights with emb [V, D], w1, b1, w2, b2" % fn)
+        C_map, h, w_ = (int(v) for v in map_.shape[-3:])
+        V, D = (int(v) for v in t["emb"].shape)
+        _, rows, map_ld = self._conv_rows(fn, "map", map_, torch.float32, (C_map, h, w_))
+        _, rows_i, idx_ld = self._conv_rows(fn, "idx", idx, torch.int16, (2, h, w_))
+        if rows_i != rows:
+            raise ValueError("%s: map has %d rows, idx %d" % (fn, rows, rows_i))
+        C = C_map + 2 * D
+        for k, shape in (("emb", (V, D)), ("w1", (9 * C, _cabi.CONV_F1)), ("b1", (_cabi.CONV_F1,)),
+                         ("w2", (9 * _cabi.CONV_F1, _cabi.CONV_F2)), ("b2", (_cabi.CONV_F2,))):
+            operand(fn, "conv_weights." + k, t[k], torch.float32, self.device, math.prod(shape))
+            if tuple(t[k].shape) != shape:
+                raise ValueError("%s: conv_weights[%r] must have the shape %s" % (fn, k, shape))
+        oh1, ow1 = (h - 3) // 2 + 1, (w_ - 3) // 2 + 1
+        NF = max(0, ((oh1 - 3) // 2 + 1) * ((ow1 - 3) // 2 + 1)) * _cabi.CONV_F2
+        net = _cabi.AieConvClass(map=map_.data_ptr(), map_ld=map_ld, idx=idx.data_ptr(), idx_ld=idx_ld, emb=ptr(t["emb"]),
+                                 w1=ptr(t["w1"]), b1=ptr(t["b1"]), w2=ptr(t["w2"]), b2=ptr(t["b2"]), flat=None, flat_ld=0,
+                                 x_out=None, x_ld=0, C_map=C_map, D=D, h=h, w=w_, V=V, F_flat=0)
+        return net, t, rows, NF
+
+    def policy_conv_forward(self, map, idx, flat, conv_weights, out=None):  # noqa: A002
+        """aie_policy_conv_forward: the convolutional encoder of the agents' egocentric crop -- embedding of the two index
+        planes, two 3x3 stride-2 convolutions (16, then 32 filters) with ReLU, Keras' flatten -- in ONE launch on the current
+        stream.  map: float32 [rows, C_map, h, w] (or [B, n, C_map, h, w]) and idx: int16 [rows, 2, h, w]: device tensors
+        used where they lie (the arena's obs_a_world-map / obs_a_world-idx_map, a trajectory's stored copies, any view
+        whose rows are contiguous blocks one stride apart); flat: float32 [rows, F_flat] (or [B, n, F_flat]) with contiguous
+        rows, or None.  conv_weights: a mapping (or rollout.conv_weights) with float32 device tensors emb [V, D],
+        w1 [9 (C_map + 2 D), 16], b1 [16], w2 [144, 32], b2 [32], contiguous, read where they lie at every launch.
+        Returns x [rows, NF + F_flat]: the features, then a copy of the flat row -- a legal x_a of policy_mlp_forward;
+        out= fills the caller's float32 device tensor [rows, >= NF + F_flat] with contiguous rows instead (columns behind are
+        left alone).  Nothing is converted.  The arithmetic contract and the supported shapes are include/aie.h's."""
+        import torch
+        fn = "policy_conv_forward"
+        net, _, rows, NF = self._conv_operands(fn, map, idx, conv_weights)
+        F_flat = 0
+        if flat is not None:
+            if getattr(flat, "dim", lambda: 0)() not in (2, 3):
+                raise ValueError("%s: flat is a float32 device tensor [rows, F_flat] (or [B, n, F_flat])" % fn)
+            flat, r2, ld = self._conv_rows(fn, "flat", flat, torch.float32, (int(flat.shape[-1]),))
+            if r2 != rows:
+                raise ValueError("%s: flat must have map's %d rows" % (fn, rows))
+            F_flat = int(flat.shape[-1])
+            net.flat, net.flat_ld, net.F_flat = flat.data_ptr(), ld, F_flat
+        if out is None:
+            out = torch.empty((rows, NF + F_flat), dtype=torch.float32, device=self.device)
+        elif not (out.dim() == 2 and out.dtype == torch.float32 and out.device == self.device and out.shape[0] == rows
+                  and out.shape[1] >= NF + F_flat and out.stride(1) == 1):
+            raise ValueError("%s: out is a float32 device tensor [%d, >= %d] with contiguous rows" % (fn, rows, NF + F_flat))
+        net.x_out, net.x_ld = out.data_ptr(), int(out.stride(0)) if rows > 1 else int(out.shape[1])
+        self._check(self.lib.aie_policy_conv_forward(self.handle, rows, C.byref(net), self._stream()))
+        return out
+
+    def policy_conv_backward(self, map, idx, conv_weights, g_feat, out=None):  # noqa: A002
+        """aie_policy_conv_backward: the gradients of the encoder's five tensors from g_feat, the gradient with respect to
+        its NF features (policy_mlp_input_grad's first NF columns) -- THREE launches on the current stream.  map, idx and
+        conv_weights as for policy_conv_forward (the same validation); g_feat: a float32 device tensor [rows, >= NF] with
+        contiguous rows (any row stride).  Returns a dict emb, w1, b1, w2, b2 of new float32 tensors in the weights' shapes;
+        out= (such a dict) fills the caller's contiguous float32 tensors instead.  Every entry is overwritten.  The
+        arithmetic contract (segments of _cabi.MLP_BWD_SEG rows, float64 sums of the segments, no atomics: two runs give the
+        same bits) is include/aie.h's.  The workspace grows with the row count; it is cached per backend and replaced when
+        a call needs more (policy_mlp_backward's rules: one stream at a time, capture the largest batch first)."""
+        import torch
+        fn = "policy_conv_backward"
+        net, t, rows, NF = self._conv_operands(fn, map, idx, conv_weights)
+        if not (getattr(g_feat, "dim", lambda: 0)() == 2 and g_feat.dtype == torch.float32 and g_feat.device == self.device
+                and g_feat.shape[0] == rows and g_feat.shape[1] >= NF and g_feat.stride(1) == 1):
+            raise ValueError("%s: g_feat is a float32 device tensor [%d, >= %d] with contiguous rows" % (fn, rows, NF))
+        if out is not None:
+            grads = {k: operand(fn, "out's " + k, out.get(k), torch.float32, self.device, t[k].numel()) for k in t}
+        else:
+            grads = {k: torch.empty_like(t[k]) for k in t}
+        q = _cabi.AieConvGradClass(net=net, g_feat=g_feat.data_ptr(), g_ld=int(g_feat.stride(0)) if rows > 1 else int(g_feat.shape[1]),
+                                   **{"g" + k: ptr(grads[k]) for k in t})
+        need = int(self.lib.aie_policy_conv_backward_workspace_bytes(self.handle, rows, C.byref(q)))
+        ws = getattr(self, "_conv_bwd_ws", None)
+        if need > 0 and (ws is None or ws.numel() * 4 < need):
+            ws = self._conv_bwd_ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.device)
+        self._check(self.lib.aie_policy_conv_backward(self.handle, rows, C.byref(q), ptr(ws), ws.numel() * 4 if ws is not None else 0,
+                                                      self._stream()))
+        return grads
 
     def adam_group(self, tensors, lr, state, stats, betas=(0.9, 0.999), eps=1e-8, max_norm=0.0):
         """One aie_opt_group for adam_step.  tensors: a sequence of (w, g, m, v), at most _cabi.OPT_MAX_TENSORS, each four

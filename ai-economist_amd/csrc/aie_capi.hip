@@ -16,6 +16,7 @@
 #include "aie_kernels_ppo.hip"
 #include "aie_kernels_mlp.hip"
 #include "aie_kernels_mlp_bwd.hip"
+#include "aie_kernels_conv.hip"
 #include "aie_kernels_covid.hip"
 #include "aie_kernels_optim.hip"
 #include "aie_jit.h"
@@ -1049,6 +1050,48 @@ int aie_policy_mlp_backward(aie_env* env, int64_t B, const aie_mlp_grad_class* a
   hipLaunchKernelGGL(aie_policy_mlp_bwd_rows_kernel, dim3(p.grid_rows), dim3(p.block), p.lds, s, p.A);
   hipLaunchKernelGGL(aie_policy_mlp_bwd_atd_kernel, dim3(p.grid_atd), dim3(p.block), 0, s, p.A);
   hipLaunchKernelGGL(aie_policy_mlp_bwd_reduce_kernel, dim3(p.grid_reduce), dim3(p.block), 0, s, p.A);
+  return aie_launched(env);
+}
+
+int aie_policy_mlp_input_grad(aie_env* env, int64_t B, const aie_mlp_grad_class* agents, const aie_mlp_grad_class* planner,
+                              void* d_workspace, int64_t workspace_bytes, float* d_g_x_a, int64_t ld_a, int32_t ncols_a,
+                              float* d_g_x_p, int64_t ld_p, int32_t ncols_p, void* stream) {
+  if (!env) return AIE_E_INVALID;
+  aie_mlp_igrad_plan p;
+  if (const int rc = aie_plan_mlp_input_grad(&env->P, B, agents, planner, d_workspace, workspace_bytes, d_g_x_a, ld_a, ncols_a,
+                                             d_g_x_p, ld_p, ncols_p, env->err, sizeof(env->err), &p))
+    return rc;
+  if (!p.grid) return AIE_OK;
+  AIE_HIP_CHECK(env, hipSetDevice(env->device));
+  hipLaunchKernelGGL(aie_policy_mlp_input_grad_kernel, dim3(p.grid), dim3(p.block), p.lds, static_cast<hipStream_t>(stream), p.A);
+  return aie_launched(env);
+}
+
+int aie_policy_conv_forward(aie_env* env, int64_t rows, const aie_conv_class* cls, void* stream) {
+  if (!env) return AIE_E_INVALID;
+  aie_conv_fwd_plan p;
+  if (const int rc = aie_plan_conv_forward(rows, cls, env->err, sizeof(env->err), &p)) return rc;
+  AIE_HIP_CHECK(env, hipSetDevice(env->device));
+  hipLaunchKernelGGL(aie_policy_conv_kernel, dim3(p.grid), dim3(p.block), p.lds, static_cast<hipStream_t>(stream), p.A);
+  return aie_launched(env);
+}
+
+int64_t aie_policy_conv_backward_workspace_bytes(const aie_env* env, int64_t rows, const aie_conv_grad_class* cls) {
+  if (!env) return AIE_E_INVALID;
+  aie_conv_bwd_plan p;
+  const int rc = aie_plan_conv_backward(rows, cls, 1, nullptr, 0, nullptr, 0, &p);
+  return rc != AIE_OK ? rc : p.need;
+}
+int aie_policy_conv_backward(aie_env* env, int64_t rows, const aie_conv_grad_class* cls, void* d_workspace, int64_t workspace_bytes,
+                             void* stream) {
+  if (!env) return AIE_E_INVALID;
+  aie_conv_bwd_plan p;
+  if (const int rc = aie_plan_conv_backward(rows, cls, 0, d_workspace, workspace_bytes, env->err, sizeof(env->err), &p)) return rc;
+  AIE_HIP_CHECK(env, hipSetDevice(env->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(aie_policy_conv_bwd_rows_kernel, dim3(p.grid_rows), dim3(p.block), p.lds_rows, s, p.A);
+  hipLaunchKernelGGL(aie_policy_conv_bwd_seg_kernel, dim3(p.grid_seg), dim3(p.block), p.lds_seg, s, p.A);
+  hipLaunchKernelGGL(aie_policy_conv_bwd_reduce_kernel, dim3(p.grid_reduce), dim3(p.block), 0, s, p.A);
   return aie_launched(env);
 }
 

@@ -1,19 +1,20 @@
 /*
  * aie_trainer_math.h -- the trainer side's arithmetic, stated once: the policy sampler and evaluator, the PPO loss,
- * generalised advantage estimation, the policy MLP's forward and backward rows and the optimizer step (Adam under a
+ * generalised advantage estimation, the policy MLP's forward and backward rows, the convolutional encoder and the optimizer step (Adam under a
  * gradient-norm clip), with the kernels' argument records
  * (aie_sampler_args, aie_sampler_check, aie_sampler_args_of).  The long comment below defines the sampler's and the
  * evaluator's operations; the comments above aie_ppo_*, aie_gae_step, aie_mlp_* and aie_opt_* define the others.
  *
  * Plain C99 with AIE_HD (also included from HIP C++): the device kernels, the host plans (aie_trainer_plan.h), the CPU
  * restatement (oracle/aie_oracle.c) and the CPU tests compile the same helpers.  Included by aie_kernels_sampler.hip
- * and aie_kernels_mlp.hip (the roots of the two trainer chains), aie_kernels_optim.hip, aie_trainer_plan.h and the oracle -- not by
+ * and aie_kernels_mlp.hip (the roots of the two trainer chains), aie_kernels_optim.hip, aie_kernels_conv.hip, aie_trainer_plan.h and the oracle -- not by
  * aie_device.h, so no step or reset kernel is compiled from it and it is in no specialisation cache key (aie_jit.h).
  */
 #ifndef AIE_TRAINER_MATH_H_
 #define AIE_TRAINER_MATH_H_
 
 #include <math.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "aie_layout.h"
@@ -557,6 +558,198 @@ typedef struct aie_mlp_bwd_args {
   aie_mlp_bwd_group agents, planner;
   int32_t reduce_blocks_a;                  /* the third launch: workgroups [0, reduce_blocks_a) are the agents' */
 } aie_mlp_bwd_args;
+/* The gradient with respect to the MLP's input (include/aie.h: aie_policy_mlp_input_grad), one entry: dz1_r is row r of
+ * aie_mlp_row_backward's dz1, w1 the first layer's [F, H] weights. */
+AIE_HD static inline float aie_mlp_input_grad_entry(const float* dz1_r, const float* w1, int H, int j) {
+  return aie_mlp_chain(0.0f, dz1_r, w1 + (int64_t)j * H, 1, H);
+}
+typedef struct aie_mlp_igrad_group {
+  const float *dz1, *w1;
+  float* g_x;
+  int64_t ld, rows;
+  int32_t H, ncols, tiles, cgroups, blocks, pad_; /* row tiles of AIE_IGRAD_TILE; groups of 256 columns; their product */
+} aie_mlp_igrad_group;
+typedef struct aie_mlp_igrad_args {
+  aie_mlp_igrad_group agents, planner;
+} aie_mlp_igrad_args;
+#define AIE_IGRAD_TILE 16 /* rows a workgroup carries per weight it reads */
+
+/* The convolutional encoder (include/aie.h: aie_policy_conv_forward / _backward), stated once -- the kernels call these
+ * helpers output by output, tests/test_policy_conv_cpu.py compiles them against an independent transcription
+ * (tests/policy_conv_ref.py).  A row's images, in the layouts the helpers and the kernels' LDS share:
+ *   X  [h w][C]     the input, cell-major: X[(y w + x) C + c] (aie_conv_input_at gives one entry from the caller's tensors)
+ *   a1 [oh1 ow1][F1], a2 = the features [oh2 ow2][F2];  dz1, dz2 likewise;
+ *   dxe [2 h w][D]  the input gradient of the embedding's channels: dxe[(i h w + y w + x) D + d] is channel C_map + i D + d.
+ * Every chain is the MLP's: one accumulator, ascending, one fmaf per term. */
+typedef struct aie_conv_shape {
+  int32_t C_map, D, h, w, V, C, oh1, ow1, oh2, ow2, P1, P2, NF, hw;
+} aie_conv_shape;
+AIE_HD static inline aie_conv_shape aie_conv_shape_of(int C_map, int D, int h, int w, int V) {
+  aie_conv_shape S;
+  S.C_map = C_map, S.D = D, S.h = h, S.w = w, S.V = V, S.C = C_map + 2 * D, S.hw = h * w;
+  S.oh1 = (h - 3) / 2 + 1, S.ow1 = (w - 3) / 2 + 1;
+  S.oh2 = (S.oh1 - 3) / 2 + 1, S.ow2 = (S.ow1 - 3) / 2 + 1;
+  S.P1 = S.oh1 * S.ow1, S.P2 = S.oh2 * S.ow2, S.NF = S.P2 * AIE_CONV_F2;
+  return S;
+}
+AIE_HD static inline int aie_conv_clamp(int v, int V) { return v < 0 ? 0 : v >= V ? V - 1 : v; }
+/* channel c of cell `cell` of a row's input: map_r and idx_r are the row's [C_map][h w] and [2][h w] */
+AIE_HD static inline float aie_conv_input_at(const aie_conv_shape* S, const float* map_r, const int16_t* idx_r, const float* emb,
+                                             int c, int cell) {
+  if (c < S->C_map) return map_r[c * S->hw + cell];
+  const int e = c - S->C_map, i = e / S->D, d = e - i * S->D;
+  return emb[aie_conv_clamp(idx_r[i * S->hw + cell], S->V) * S->D + d];
+}
+/* one output of a 3x3 stride-2 convolution over src [.. sw][sc] (cell-major), weights [9 sc][nf], from its bias, with ReLU */
+AIE_HD static inline float aie_conv_out(const float* src, int sw, int sc, const float* wt, int nf, float bias, int oy, int ox, int f) {
+  float acc = bias;
+  for (int ky = 0; ky < 3; ++ky)
+    for (int kx = 0; kx < 3; ++kx) {
+      const float* s = src + ((2 * oy + ky) * sw + 2 * ox + kx) * sc;
+      const float* q = wt + (ky * 3 + kx) * sc * nf + f;
+      for (int c = 0; c < sc; ++c) acc = fmaf(s[c], q[c * nf], acc);
+    }
+  return aie_mlp_relu(acc);
+}
+AIE_HD static inline float aie_conv1_out(const aie_conv_shape* S, const float* X, const float* w1, const float* b1, int p, int f) {
+  return aie_conv_out(X, S->w, S->C, w1, AIE_CONV_F1, b1[f], p / S->ow1, p % S->ow1, f);
+}
+AIE_HD static inline float aie_conv2_out(const aie_conv_shape* S, const float* a1, const float* w2, const float* b2, int p, int f) {
+  return aie_conv_out(a1, S->ow1, AIE_CONV_F1, w2, AIE_CONV_F2, b2[f], p / S->ow2, p % S->ow2, f);
+}
+/* the gradient with respect to input (y, x, c) of such a convolution with on x ow outputs: over the outputs (oy, ox)
+ * ascending whose window holds (y, x), and inside one over f ascending, of (dz[oy][ox][f], wt[(ky 3 + kx) sc + c][f]) */
+AIE_HD static inline float aie_conv_input_grad(const float* dz, int on, int ow, const float* wt, int sc, int nf, int y, int x, int c) {
+  float acc = 0.0f;
+  for (int oy = 0; oy < on; ++oy) {
+    const int ky = y - 2 * oy;
+    if (ky < 0 || ky > 2) continue;
+    for (int ox = 0; ox < ow; ++ox) {
+      const int kx = x - 2 * ox;
+      if (kx < 0 || kx > 2) continue;
+      const float* d = dz + (oy * ow + ox) * nf;
+      const float* q = wt + ((ky * 3 + kx) * sc + c) * nf;
+      for (int f = 0; f < nf; ++f) acc = fmaf(d[f], q[f], acc);
+    }
+  }
+  return acc;
+}
+AIE_HD static inline float aie_conv_da1(const aie_conv_shape* S, const float* dz2, const float* w2, int p, int c) {
+  return aie_conv_input_grad(dz2, S->oh2, S->ow2, w2, AIE_CONV_F1, AIE_CONV_F2, p / S->ow1, p % S->ow1, c);
+}
+/* e = i D + d: the embedding's channel C_map + e */
+AIE_HD static inline float aie_conv_dx(const aie_conv_shape* S, const float* dz1, const float* w1, int cell, int e) {
+  return aie_conv_input_grad(dz1, S->oh1, S->ow1, w1, S->C, AIE_CONV_F1, cell / S->w, cell % S->w, S->C_map + e);
+}
+/* a row's forward on the host: X [h w C], a1 [P1 F1], feat [NF] */
+static inline void aie_conv_row_forward(const aie_conv_shape* S, const float* map_r, const int16_t* idx_r, const float* emb,
+                                        const float* w1, const float* b1, const float* w2, const float* b2, float* X, float* a1,
+                                        float* feat) {
+  for (int cell = 0; cell < S->hw; ++cell)
+    for (int c = 0; c < S->C; ++c) X[cell * S->C + c] = aie_conv_input_at(S, map_r, idx_r, emb, c, cell);
+  for (int p = 0; p < S->P1; ++p)
+    for (int f = 0; f < AIE_CONV_F1; ++f) a1[p * AIE_CONV_F1 + f] = aie_conv1_out(S, X, w1, b1, p, f);
+  for (int p = 0; p < S->P2; ++p)
+    for (int f = 0; f < AIE_CONV_F2; ++f) feat[p * AIE_CONV_F2 + f] = aie_conv2_out(S, a1, w2, b2, p, f);
+}
+/* a row's share of the embedding's gradient: table [V D], every entry written */
+AIE_HD static inline void aie_conv_row_emb(const aie_conv_shape* S, const int16_t* idx_r, const float* dxe, float* table) {
+  for (int j = 0; j < S->V * S->D; ++j) table[j] = 0.0f;
+  for (int ic = 0; ic < 2 * S->hw; ++ic) {
+    float* t = table + aie_conv_clamp(idx_r[ic], S->V) * S->D;
+    for (int d = 0; d < S->D; ++d) t[d] = t[d] + dxe[ic * S->D + d];
+  }
+}
+/* one weight-gradient entry's segment chain continued over one row: act(p) is the entry's activation at output p (the
+ * constant 1 for a bias: acc + dz, which fmaf(1, dz, acc) equals) */
+#define AIE_CONV_GRAD_ROW(acc, P, nf, f, dz_r, ACT)                                              \
+  for (int p_ = 0; p_ < (P); ++p_) (acc) = fmaf((ACT), (dz_r)[p_ * (nf) + (f)], (acc))
+/* The whole backward on the host.  scratch: rows (h w C + 2 P1 F1 + 2 NF + 2 h w D) + V D floats. */
+static inline void aie_conv_backward_host(const aie_conv_shape* S, int64_t rows, const float* map, int64_t map_ld, const int16_t* idx,
+                                          int64_t idx_ld, const float* emb, const float* w1, const float* b1, const float* w2,
+                                          const float* b2, const float* g_feat, int64_t g_ld, float* scratch, float* gemb, float* gw1,
+                                          float* gb1, float* gw2, float* gb2) {
+  const int C = S->C, P1 = S->P1, P2 = S->P2, NF = S->NF, hwC = S->hw * C, n1 = P1 * AIE_CONV_F1, nx = 2 * S->hw * S->D;
+  float *X = scratch, *a1 = X + rows * hwC, *dz1 = a1 + rows * n1, *a2 = dz1 + rows * n1, *dz2 = a2 + rows * NF,
+        *dxe = dz2 + rows * NF, *table = dxe + rows * nx;
+  for (int64_t r = 0; r < rows; ++r) {
+    float *Xr = X + r * hwC, *a1r = a1 + r * n1, *dz1r = dz1 + r * n1, *a2r = a2 + r * NF, *dz2r = dz2 + r * NF;
+    aie_conv_row_forward(S, map + r * map_ld, idx + r * idx_ld, emb, w1, b1, w2, b2, Xr, a1r, a2r);
+    for (int j = 0; j < NF; ++j) dz2r[j] = a2r[j] > 0.0f ? g_feat[r * g_ld + j] : 0.0f;
+    for (int p = 0; p < P1; ++p)
+      for (int c = 0; c < AIE_CONV_F1; ++c)
+        dz1r[p * AIE_CONV_F1 + c] = a1r[p * AIE_CONV_F1 + c] > 0.0f ? aie_conv_da1(S, dz2r, w2, p, c) : 0.0f;
+    for (int cell = 0; cell < S->hw; ++cell)
+      for (int e = 0; e < 2 * S->D; ++e)
+        dxe[r * nx + ((e / S->D) * S->hw + cell) * S->D + e % S->D] = aie_conv_dx(S, dz1r, w1, cell, e);
+  }
+  /* the weights: k = (ky 3 + kx) sc + c reads the activation at (2 oy + ky, 2 ox + kx, c); the last row is the bias */
+  for (int L = 0; L < 2; ++L) {
+    const int sc = L ? AIE_CONV_F1 : C, nf = L ? AIE_CONV_F2 : AIE_CONV_F1, P = L ? P2 : P1, ow = L ? S->ow2 : S->ow1,
+              sw = L ? S->ow1 : S->w;
+    const float *act = L ? a1 : X, *dz = L ? dz2 : dz1;
+    const int64_t act_ld = L ? n1 : hwC, dz_ld = (int64_t)P * nf;
+    float *gw = L ? gw2 : gw1, *gb = L ? gb2 : gb1;
+    for (int k = 0; k <= 9 * sc; ++k)
+      for (int f = 0; f < nf; ++f) {
+        const int t = k / sc, ky = t / 3, kx = t % 3, c = k % sc;
+        double sum = 0.0;
+        for (int64_t r0 = 0; r0 < rows; r0 += AIE_MLP_BWD_SEG) {
+          const int64_t r1 = r0 + AIE_MLP_BWD_SEG < rows ? r0 + AIE_MLP_BWD_SEG : rows;
+          float acc = 0.0f;
+          for (int64_t r = r0; r < r1; ++r) {
+            const float* ar = act + r * act_ld;
+            if (k < 9 * sc) AIE_CONV_GRAD_ROW(acc, P, nf, f, dz + r * dz_ld, ar[((2 * (p_ / ow) + ky) * sw + 2 * (p_ % ow) + kx) * sc + c]);
+            else AIE_CONV_GRAD_ROW(acc, P, nf, f, dz + r * dz_ld, 1.0f);
+          }
+          sum += (double)acc;
+        }
+        if (k < 9 * sc) gw[k * nf + f] = (float)sum;
+        else gb[f] = (float)sum;
+      }
+  }
+  /* the embedding: a row's table, then the segment's rows ascending, then the segments in float64 */
+  const int VD = S->V * S->D;
+  for (int j = 0; j < VD; ++j) gemb[j] = 0.0f;
+  double* sums = (double*)malloc(sizeof(double) * (size_t)VD);
+  float* accs = (float*)malloc(sizeof(float) * (size_t)VD);
+  for (int j = 0; j < VD; ++j) sums[j] = 0.0;
+  for (int64_t r0 = 0; r0 < rows; r0 += AIE_MLP_BWD_SEG) {
+    const int64_t r1 = r0 + AIE_MLP_BWD_SEG < rows ? r0 + AIE_MLP_BWD_SEG : rows;
+    for (int j = 0; j < VD; ++j) accs[j] = 0.0f;
+    for (int64_t r = r0; r < r1; ++r) {
+      aie_conv_row_emb(S, idx + r * idx_ld, dxe + r * nx, table);
+      for (int j = 0; j < VD; ++j) accs[j] = accs[j] + table[j];
+    }
+    for (int j = 0; j < VD; ++j) sums[j] += (double)accs[j];
+  }
+  for (int j = 0; j < VD; ++j) gemb[j] = (float)sums[j];
+  free(sums);
+  free(accs);
+}
+/* The kernels' arguments (aie_policy_conv_forward / _backward fill them: aie_trainer_plan.h).  A workgroup of the forward
+ * and of the backward's first launch owns `tr` consecutive rows, staged in LDS as [tr][lds_row] floats: X, a1, and in the
+ * backward a2, dz2 and dz1 behind them.  The backward's workspace: a1, dz1 [rows][P1 F1], dz2 [rows][NF], dxe
+ * [rows][2 h w D], then the segments' partials [nseg][Pn]: three blocks [(9 C + 1), F1], [(9 F1 + 1), F2], [V, D]. */
+typedef struct aie_conv_args {
+  const float* map;
+  const int16_t* idx;
+  const float *emb, *w1, *b1, *w2, *b2, *flat;
+  float* x_out;
+  int64_t map_ld, idx_ld, flat_ld, x_ld, rows;
+  aie_conv_shape S;
+  int32_t F_flat, tr, lds_row, pad_;
+} aie_conv_args;
+typedef struct aie_conv_bwd_args {
+  aie_conv_args net;
+  const float* g_feat;
+  int64_t g_ld;
+  float *a1, *dz1, *dz2, *dxe, *partial;
+  float *gemb, *gw1, *gb1, *gw2, *gb2;
+  int32_t nseg, Pn, off2, off3, chunks, pad_;   /* segments; entries; the blocks' offsets; workgroups per segment of the weights' blocks */
+} aie_conv_bwd_args;
+#define AIE_CONV_EMB_TILE 16 /* rows whose embedding tables a segment's workgroup holds in LDS at a time */
+
 /* Adam with gradient-norm clipping (include/aie.h: aie_adam_step), stated once -- the kernels call these helpers,
  * tests/test_adam_cpu.py compiles them, tests/optim_ref.py transcribes include/aie.h's text.
  *   aie_opt_chunk_sumsq  one chunk's sum of squares in float64: 256 slots of four consecutive elements each, added ascending

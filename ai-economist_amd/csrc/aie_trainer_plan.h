@@ -345,6 +345,157 @@ static inline int aie_plan_mlp_backward_launch(aie_mlp_bwd_plan* p, int64_t B, c
   return AIE_OK;
 }
 
+/* ---- aie_policy_mlp_input_grad: the backward's own plan finds dz1 in the workspace; a workgroup per AIE_IGRAD_TILE rows and
+ * 256 columns ---- */
+typedef struct aie_mlp_igrad_plan { aie_mlp_igrad_args A; int64_t need; uint32_t grid, block; size_t lds; } aie_mlp_igrad_plan;
+
+static inline int aie_plan_mlp_input_grad(const aie_params* P, int64_t B, const aie_mlp_grad_class* agents,
+                                          const aie_mlp_grad_class* planner, void* d_workspace, int64_t workspace_bytes,
+                                          float* g_x_a, int64_t ld_a, int32_t ncols_a, float* g_x_p, int64_t ld_p, int32_t ncols_p, char* err, size_t errlen,
+                                          aie_mlp_igrad_plan* p) {
+  const char* fn = "aie_policy_mlp_input_grad";
+  memset(p, 0, sizeof(*p));
+  aie_mlp_bwd_plan b;
+  int rc = aie_plan_mlp_backward(P, B, agents, planner, err, errlen, &b);
+  if (rc != AIE_OK) return rc;
+  const aie_mlp_grad_class* cls[2] = {agents, planner};
+  float* gx[2] = {g_x_a, g_x_p};
+  const int64_t ld[2] = {ld_a, ld_p};
+  const int32_t nc[2] = {ncols_a, ncols_p};
+  for (int c = 0; c < 2; ++c) {
+    if (!gx[c]) continue;
+    if (!cls[c] || nc[c] < 1 || nc[c] > cls[c]->net.F || ld[c] < nc[c] || ((uintptr_t)gx[c] & 3))
+      AIE_PLAN_REFUSE(AIE_E_INVALID, "%s: the %s g_x (%p, ld %lld, ncols %d) needs its class, 1 <= ncols <= F, ld >= ncols and a "
+                      "4-byte aligned pointer", fn, c ? "planner's" : "agents'", (void*)gx[c], (long long)ld[c], nc[c]);
+  }
+  p->need = b.need;
+  if (!agents && !planner) return AIE_OK;
+  if (!d_workspace || ((uintptr_t)d_workspace & 15) || workspace_bytes < b.need)
+    AIE_PLAN_REFUSE(AIE_E_INVALID, "%s: the workspace (%p, %lld bytes) must be aie_policy_mlp_backward's: device memory, 16-byte "
+                    "aligned, of at least %lld bytes", fn, d_workspace, (long long)workspace_bytes, (long long)b.need);
+  rc = aie_plan_mlp_backward_launch(&b, B, agents, planner, d_workspace, err, errlen);
+  if (rc != AIE_OK) return rc;
+  const aie_mlp_bwd_group* bg[2] = {&b.A.agents, &b.A.planner};
+  aie_mlp_igrad_group* ig[2] = {&p->A.agents, &p->A.planner};
+  int64_t blocks = 0;
+  for (int c = 0; c < 2; ++c) {
+    if (!gx[c]) continue;
+    aie_mlp_igrad_group* G = ig[c];
+    G->dz1 = bg[c]->dz1, G->w1 = bg[c]->net.w1, G->g_x = gx[c], G->ld = ld[c], G->rows = bg[c]->net.rows;
+    G->H = bg[c]->net.H, G->ncols = nc[c];
+    const int64_t tiles = (G->rows + AIE_IGRAD_TILE - 1) / AIE_IGRAD_TILE;
+    G->cgroups = (nc[c] + 255) / 256;
+    if (tiles * G->cgroups > AIE_PLAN_GRID_MAX) AIE_PLAN_REFUSE(AIE_E_INVALID, "%s: B = %lld is more than one launch takes", fn, (long long)B);
+    G->tiles = (int32_t)tiles, G->blocks = (int32_t)(tiles * G->cgroups);
+    blocks += G->blocks;
+    const size_t l = (size_t)AIE_IGRAD_TILE * (size_t)G->H * sizeof(float);
+    p->lds = l > p->lds ? l : p->lds;
+  }
+  if (blocks > AIE_PLAN_GRID_MAX) AIE_PLAN_REFUSE(AIE_E_INVALID, "%s: B = %lld is more than one launch takes", fn, (long long)B);
+  p->grid = (uint32_t)blocks, p->block = 256;
+  return AIE_OK;
+}
+
+/* ---- the convolutional encoder: a workgroup per `tr` rows (as many as 64 KB of LDS hold, at most 16) ---- */
+#define AIE_CONV_LDS_BUDGET 65536
+typedef struct aie_conv_fwd_plan { aie_conv_args A; uint32_t grid, block; size_t lds; } aie_conv_fwd_plan;
+
+/* the checks and the fill the two passes share; extra: floats per row the pass stages in LDS behind X and a1 */
+static inline int aie_plan_conv_class(const char* fn, int64_t rows, const aie_conv_class* k, int backward, char* err, size_t errlen,
+                                      aie_conv_args* A, uint32_t* grid, size_t* lds) {
+  if (rows < 1 || !k) AIE_PLAN_REFUSE(AIE_E_INVALID, "%s: rows = %lld with the class at %p (needs rows >= 1 and a class)", fn,
+                                      (long long)rows, (const void*)k);
+  if (!k->map || !k->idx || !k->emb || !k->w1 || !k->b1 || !k->w2 || !k->b2)
+    AIE_PLAN_REFUSE(AIE_E_INVALID, "%s: map, idx, emb, w1, b1, w2 and b2 must not be NULL", fn);
+  if (k->C_map < 1 || k->C_map > 32)
+    AIE_PLAN_REFUSE(AIE_E_UNSUPPORTED, "%s: C_map = %d map channels (supported: 1 .. 32)", fn, k->C_map);
+  if (k->D < 1 || k->D > 8) AIE_PLAN_REFUSE(AIE_E_UNSUPPORTED, "%s: D = %d embedding dimensions (supported: 1 .. 8)", fn, k->D);
+  if (k->h < 7 || k->h > 15 || k->w < 7 || k->w > 15)
+    AIE_PLAN_REFUSE(AIE_E_UNSUPPORTED, "%s: a crop of %d x %d cells (supported: 7 .. 15 each way; full observability's whole "
+                    "map is not)", fn, k->h, k->w);
+  if (k->V < 1 || k->V > 128) AIE_PLAN_REFUSE(AIE_E_UNSUPPORTED, "%s: V = %d embedding rows (supported: 1 .. 128)", fn, k->V);
+  const aie_conv_shape S = aie_conv_shape_of(k->C_map, k->D, k->h, k->w, k->V);
+  if (k->map_ld < (int64_t)S.C_map * S.hw || k->idx_ld < 2 * (int64_t)S.hw)
+    AIE_PLAN_REFUSE(AIE_E_INVALID, "%s: row strides map_ld = %lld (needs >= %d floats) and idx_ld = %lld (needs >= %d elements)", fn,
+                    (long long)k->map_ld, S.C_map * S.hw, (long long)k->idx_ld, 2 * S.hw);
+  if ((((uintptr_t)k->map | (uintptr_t)k->emb | (uintptr_t)k->w1 | (uintptr_t)k->b1 | (uintptr_t)k->w2 | (uintptr_t)k->b2) & 3) ||
+      ((uintptr_t)k->idx & 1))
+    AIE_PLAN_REFUSE(AIE_E_INVALID, "%s: map and the weights must be 4-byte aligned, idx 2-byte aligned", fn);
+  if (!backward) {
+    if (!k->x_out || ((uintptr_t)k->x_out & 3) || ((uintptr_t)k->flat & 3) || k->F_flat < 0 || k->F_flat > 1024 ||
+        (k->flat != NULL) != (k->F_flat > 0) || k->x_ld < (int64_t)S.NF + k->F_flat || (k->flat && k->flat_ld < k->F_flat))
+      AIE_PLAN_REFUSE(AIE_E_INVALID, "%s: x_out (%p, x_ld %lld) must be 4-byte aligned with x_ld >= NF + F_flat = %d + %d; flat (%p, "
+                      "flat_ld %lld) goes with F_flat in 1 .. 1024 and flat_ld >= F_flat, or is NULL with F_flat 0", fn,
+                      (void*)k->x_out, (long long)k->x_ld, S.NF, k->F_flat, (const void*)k->flat, (long long)k->flat_ld);
+  }
+  memset(A, 0, sizeof(*A));
+  A->map = k->map, A->idx = k->idx, A->emb = k->emb, A->w1 = k->w1, A->b1 = k->b1, A->w2 = k->w2, A->b2 = k->b2;
+  A->map_ld = k->map_ld, A->idx_ld = k->idx_ld, A->rows = rows, A->S = S;
+  if (!backward) A->flat = k->flat, A->flat_ld = k->flat_ld, A->x_out = k->x_out, A->x_ld = k->x_ld, A->F_flat = k->F_flat;
+  A->lds_row = S.hw * S.C + S.P1 * AIE_CONV_F1 + (backward ? S.NF + S.P1 * AIE_CONV_F1 : 0);
+  int tr = 16;
+  while (tr > 1 && (size_t)tr * (size_t)A->lds_row * sizeof(float) > AIE_CONV_LDS_BUDGET) tr >>= 1;
+  A->tr = tr;
+  const int64_t nb = (rows + tr - 1) / tr;
+  if (nb > AIE_PLAN_GRID_MAX) AIE_PLAN_REFUSE(AIE_E_INVALID, "%s: %lld rows are more than one launch takes", fn, (long long)rows);
+  *grid = (uint32_t)nb;
+  *lds = (size_t)tr * (size_t)A->lds_row * sizeof(float);
+  return AIE_OK;
+}
+
+static inline int aie_plan_conv_forward(int64_t rows, const aie_conv_class* k, char* err, size_t errlen, aie_conv_fwd_plan* p) {
+  memset(p, 0, sizeof(*p));
+  p->block = 256;
+  return aie_plan_conv_class("aie_policy_conv_forward", rows, k, 0, err, errlen, &p->A, &p->grid, &p->lds);
+}
+
+/* the backward: rows (recompute, dz2, dz1, dx into the workspace); a segment's partials (`chunks` workgroups of 256 weight
+ * entries and one for the embedding per segment); the float64 sums of the segments (256 entries a workgroup) */
+typedef struct aie_conv_bwd_plan {
+  aie_conv_bwd_args A;
+  int64_t need;
+  uint32_t grid_rows, grid_seg, grid_reduce, block;
+  size_t lds_rows, lds_seg;
+} aie_conv_bwd_plan;
+
+static inline int aie_plan_conv_backward(int64_t rows, const aie_conv_grad_class* q, int query, void* d_workspace,
+                                         int64_t workspace_bytes, char* err, size_t errlen, aie_conv_bwd_plan* p) {
+  const char* fn = "aie_policy_conv_backward";
+  memset(p, 0, sizeof(*p));
+  p->block = 256;
+  const int rc = aie_plan_conv_class(fn, rows, q ? &q->net : NULL, 1, err, errlen, &p->A.net, &p->grid_rows, &p->lds_rows);
+  if (rc != AIE_OK) return rc;
+  const aie_conv_shape* S = &p->A.net.S;
+  if (!q->g_feat || !q->gemb || !q->gw1 || !q->gb1 || !q->gw2 || !q->gb2 || q->g_ld < S->NF ||
+      (((uintptr_t)q->g_feat | (uintptr_t)q->gemb | (uintptr_t)q->gw1 | (uintptr_t)q->gb1 | (uintptr_t)q->gw2 | (uintptr_t)q->gb2) & 3))
+    AIE_PLAN_REFUSE(AIE_E_INVALID, "%s: g_feat (g_ld %lld >= NF = %d), gemb, gw1, gb1, gw2 and gb2 must be 4-byte aligned and not NULL",
+                    fn, (long long)q->g_ld, S->NF);
+  aie_conv_bwd_args* A = &p->A;
+  A->g_feat = q->g_feat, A->g_ld = q->g_ld;
+  A->gemb = q->gemb, A->gw1 = q->gw1, A->gb1 = q->gb1, A->gw2 = q->gw2, A->gb2 = q->gb2;
+  const int64_t nseg = (rows + AIE_MLP_BWD_SEG - 1) / AIE_MLP_BWD_SEG;
+  A->nseg = (int32_t)nseg;
+  A->off2 = (9 * S->C + 1) * AIE_CONV_F1;
+  A->off3 = A->off2 + (9 * AIE_CONV_F1 + 1) * AIE_CONV_F2;
+  A->Pn = (A->off3 + S->V * S->D + 3) & ~3;
+  A->chunks = (A->off3 + 255) / 256;
+  const int64_t n1 = (int64_t)S->P1 * AIE_CONV_F1, nx = 2 * (int64_t)S->hw * S->D;
+  const int64_t fl = rows * (2 * n1 + S->NF + nx) + nseg * A->Pn;
+  p->need = ((fl + 63) & ~(int64_t)63) * (int64_t)sizeof(float);
+  if (nseg * (A->chunks + 1) > AIE_PLAN_GRID_MAX)
+    AIE_PLAN_REFUSE(AIE_E_INVALID, "%s: %lld rows are more than one call takes", fn, (long long)rows);
+  if (query) return AIE_OK;   /* (the workspace-bytes query stops here) */
+  if (!d_workspace || ((uintptr_t)d_workspace & 15) || workspace_bytes < p->need)
+    AIE_PLAN_REFUSE(AIE_E_INVALID, "%s: the workspace (%p, %lld bytes) must be device memory, 16-byte aligned, of at least %lld "
+                    "bytes (aie_policy_conv_backward_workspace_bytes)", fn, d_workspace, (long long)workspace_bytes, (long long)p->need);
+  float* ws = (float*)d_workspace;
+  A->a1 = ws, A->dz1 = ws + rows * n1, A->dz2 = ws + 2 * rows * n1, A->dxe = A->dz2 + rows * S->NF, A->partial = A->dxe + rows * nx;
+  p->grid_seg = (uint32_t)(nseg * (A->chunks + 1));
+  p->grid_reduce = (uint32_t)((A->Pn + 255) / 256);
+  p->lds_seg = (size_t)AIE_CONV_EMB_TILE * (size_t)(S->V * S->D) * sizeof(float);
+  return AIE_OK;
+}
+
 /* ---- aie_adam_step: a workgroup per chunk of AIE_OPT_CHUNK elements, the same grid for both launches ----
  * aie_plan_adam_groups checks the descriptors in include/aie.h's order, fills the kernels' argument without the workspace
  * pointers -- the chunk table (a tensor's first chunk in its group), the `wide` flags -- and sizes each group's share of the

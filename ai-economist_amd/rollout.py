@@ -395,6 +395,75 @@ def policy_mlp(be, x_a, x_p, weights_a, weights_p):
     return _policy_mlp_function().apply(be, x_a, x_p, names[0], names[1], *flat)
 
 
+def _policy_conv_mlp_function():
+    """The autograd Function of policy_conv_mlp, built at first use."""
+    global _PolicyConvMLP
+    if _PolicyConvMLP is not None:
+        return _PolicyConvMLP
+    import torch
+
+    class PolicyConvMLP(torch.autograd.Function):
+        """The agents' convolutional encoder in front of both classes' policy network, differentiable in all weights:
+        forward = Backend.policy_conv_forward, then Backend.policy_mlp_forward; backward = Backend.policy_mlp_backward,
+        Backend.policy_mlp_input_grad, Backend.policy_conv_backward, in that order.
+        apply(be, map, idx, flat, x_p, names_c, names_a, names_p, *weights) -> (logits_a, logits_p, value_a, value_p)."""
+
+        @staticmethod
+        def forward(ctx, be, map_, idx, flat, x_p, names_c, names_a, names_p, *weights):
+            nc, na = len(names_c), len(names_a)
+            wc, wa, wp = dict(zip(names_c, weights[:nc])), dict(zip(names_a, weights[nc:nc + na])), dict(zip(names_p, weights[nc + na:]))
+            x_cat = be.policy_conv_forward(map_, idx, flat, wc)
+            out = be.policy_mlp_forward(x_cat, x_p, wa, wp if x_p is not None else None)
+            ctx.be, ctx.names = be, (names_c, names_a, names_p)
+            ctx.has_p = x_p is not None
+            ctx.NF = x_cat.shape[1] - (flat.shape[-1] if flat is not None else 0)
+            ctx.save_for_backward(map_, idx, x_cat, *([x_p] if x_p is not None else []), *weights)
+            return out
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable  # (library calls, not a graph of torch operations)
+        def backward(ctx, g_la, g_lp, g_va, g_vp):
+            saved = list(ctx.saved_tensors)
+            map_, idx, x_cat = saved[:3]
+            del saved[:3]
+            x_p = saved.pop(0) if ctx.has_p else None
+            names_c, names_a, names_p = ctx.names
+            nc, na = len(names_c), len(names_a)
+            wc, wa, wp = dict(zip(names_c, saved[:nc])), dict(zip(names_a, saved[nc:nc + na])), dict(zip(names_p, saved[nc + na:]))
+            c = lambda g: None if g is None else g.contiguous()  # noqa: E731  (a missing one arrives as zeros)
+            be = ctx.be
+            ga, gp = be.policy_mlp_backward(x_cat, x_p, wa, wp, c(g_la), c(g_lp), c(g_va) if "wv" in wa else None,
+                                            c(g_vp) if "wv" in wp else None)
+            g_x, _ = be.policy_mlp_input_grad(ncols_a=ctx.NF)
+            gc = be.policy_conv_backward(map_, idx, wc, g_x)
+            grads = [gc[k] for k in names_c] + [ga[k] for k in names_a] + [gp[k] if gp is not None else None for k in names_p]
+            return (None,) * 8 + tuple(grads)
+
+    _PolicyConvMLP = PolicyConvMLP
+    return PolicyConvMLP
+
+
+_PolicyConvMLP = None
+CONV_NAMES = ("emb", "w1", "b1", "w2", "b2")  # the encoder's tensors: Backend.policy_conv_forward's conv_weights
+
+
+def policy_conv_mlp(be, map, idx, flat, conv_weights, x_p, weights_a, weights_p):  # noqa: A002
+    """policy_mlp with the convolutional encoder of the egocentric crop in front of the agents' network: (logits_a, logits_p,
+    value_a, value_p), where the agents' rows are Backend.policy_conv_forward(map, idx, flat, conv_weights) -- the crop's 128
+    features, then the flat observation -- through weights_a (w1 [NF + F_flat, H]), and the planner's are x_p through weights_p
+    as before (x_p None: left out).  Differentiable in the encoder's five and the networks' sixteen tensors: backward runs,
+    in order, Backend.policy_mlp_backward, Backend.policy_mlp_input_grad and Backend.policy_conv_backward -- seven launches,
+    float32 chains in fixed orders, bit-reproducible (include/aie.h states the arithmetic).  Nothing flows to the observations."""
+    getc = conv_weights.get if hasattr(conv_weights, "get") else (lambda k: getattr(conv_weights, k, None))
+    names, flat_w = [CONV_NAMES], [getc(k) for k in CONV_NAMES]
+    for x, w in ((map, weights_a), (x_p, weights_p)):
+        get = (lambda k: None) if x is None else w.get if hasattr(w, "get") else (lambda k, w=w: getattr(w, k, None))
+        present = tuple(k for k in mlp_weights.NAMES if get(k) is not None)
+        names.append(present)
+        flat_w.extend(get(k) for k in present)
+    return _policy_conv_mlp_function().apply(be, map, idx, flat, x_p, names[0], names[1], names[2], *flat_w)
+
+
 class Adam:
     """Adam under a gradient-norm clip for the two actor classes' parameters, ONE library call of two launches per step
     (Backend.adam_step, aie_adam_step) -- the optimizer the reference's tutorials train with (lr 0.0003, grad_clip 10), one
@@ -493,6 +562,8 @@ def __getattr__(name):  # rollout.MaskedCategorical, rollout.PPOLoss, rollout.Po
         return _ppo_loss_function()
     if name == "PolicyMLP":
         return _policy_mlp_function()
+    if name == "PolicyConvMLP":
+        return _policy_conv_mlp_function()
     raise AttributeError(name)
 
 
@@ -569,10 +640,19 @@ class MaskedMLPPolicy:
     arena's observations and this object's weight tensors where they lie and writes the fixed buffers `logits_a` /
     `logits_p` and `value_a` / `value_p` in place; a call of the policy is then two launches, the network and the sampler.
     float32 only.  evaluate(x_a, x_p) is the same network as an autograd function (rollout.policy_mlp) on the same
-    weight tensors: what a PPO update differentiates.  The default "torch" path is unchanged."""
+    weight tensors: what a PPO update differentiates.  The default "torch" path is unchanged.
+    spatial=True (network="library" only): the agents also see their egocentric crop -- obs_a_world-map and
+    obs_a_world-idx_map through the library's convolutional encoder (Backend.policy_conv_forward: an embedding of emb_dim
+    per index plane over emb_vocab entries, two 3x3 stride-2 convolutions, 128 features on the 11 x 11 crop; the network of
+    the reference's tutorials), concatenated in front of the flat observation in the fixed buffer `x_cat` [E * n, NF + FA].
+    logits() is then two launches, encoder and MLP; evaluate((map, idx, flat), x_p) is the differentiable form
+    (rollout.policy_conv_mlp).  The encoder's five tensors (`conv_weights`) and the NF feature rows of the agents' first
+    layer are drawn behind all other weights, so a seed gives the weights it gave before, and spatial=False is unchanged.
+    `params_a` / `params_p`: every trainable tensor of a class, by name (the agents' 13 with the encoder's as conv_*), what
+    rollout.Adam takes."""
 
     def __init__(self, be, hidden=128, seed=0, dtype=None, sampler="library", sample_seed=1234, record_logp=False,
-                 value_head=False, network="torch"):
+                 value_head=False, network="torch", spatial=False, emb_vocab=100, emb_dim=4):
         import torch
 
         self.torch = torch
@@ -635,6 +715,29 @@ class MaskedMLPPolicy:
                 self.weights_p.update(wv=self.wpv.view(-1), bv=self.bpv)
             self.logits_a = torch.zeros((be.E * be.n, MA), dtype=torch.float32, device=dev)
             self.logits_p = torch.zeros((be.E, MP), dtype=torch.float32, device=dev)
+            self.params_a, self.params_p = dict(self.weights_a), dict(self.weights_p)
+        self.spatial = bool(spatial)
+        if self.spatial:
+            if network != "library":
+                raise ValueError("MaskedMLPPolicy(spatial=True): network='library'")
+            from . import _cabi
+
+            if "obs_a_world-map" not in t or "obs_a_world-idx_map" not in t:
+                raise ValueError("MaskedMLPPolicy(spatial=True): the scenario has no egocentric crop (obs_a_world-map)")
+            C_map, h, w = (int(v) for v in t["obs_a_world-map"].shape[-3:])
+            C = C_map + 2 * int(emb_dim)
+            oh1, ow1 = (h - 3) // 2 + 1, (w - 3) // 2 + 1
+            self.NF = ((oh1 - 3) // 2 + 1) * ((ow1 - 3) // 2 + 1) * _cabi.CONV_F2
+            # drawn behind every weight above: the encoder's tensors, then the first layer's rows for its features
+            emb = torch.randn(int(emb_vocab), int(emb_dim), generator=g).to(dev, dtype)
+            cw1, cb1 = lin(9 * C, _cabi.CONV_F1)
+            cw2, cb2 = lin(9 * _cabi.CONV_F1, _cabi.CONV_F2)
+            self.conv_weights = dict(emb=emb, w1=cw1, b1=cb1, w2=cw2, b2=cb2)
+            w_feat, _ = lin(self.NF, hidden)
+            self.wa1 = torch.cat([w_feat, self.wa1], 0).contiguous()
+            self.weights_a["w1"] = self.wa1
+            self.params_a = dict(self.weights_a, **{"conv_" + k: v for k, v in self.conv_weights.items()})
+            self.x_cat = torch.zeros((be.E * be.n, self.NF + FA), dtype=torch.float32, device=dev)
         self._fused_relu = None  # decided at the first call (outside any capture: GraphedStep warms the policy up first)
         self.counter = torch.zeros((), dtype=torch.float32, device=dev)
         if sampler == "torch":
@@ -671,6 +774,9 @@ class MaskedMLPPolicy:
             xa, xp = tensors["obs_a_flat"], tensors["obs_p_flat"]
             if xa.dtype != torch.float32 or xp.dtype != torch.float32:
                 raise ValueError("MaskedMLPPolicy(network='library'): float32 observations")
+            if self.spatial:
+                xa = self.be.policy_conv_forward(tensors["obs_a_world-map"], tensors["obs_a_world-idx_map"], xa, self.conv_weights,
+                                                 out=self.x_cat)
             self.be.policy_mlp_forward(xa, xp, self.weights_a, self.weights_p,
                                        out=(self.logits_a, self.logits_p, self.value_a, self.value_p))
             return self.logits_a, self.logits_p
@@ -692,12 +798,17 @@ class MaskedMLPPolicy:
         """network="library": policy_mlp's (logits_a, logits_p, value_a, value_p) for the given observations (any batch
         size) on this object's own weight tensors, differentiable in those that require a gradient: with ppo_loss on
         them, backward() fills .grad of wa1 .. bpv, and an in-place optimizer step is what the next call, logits() or
-        replay sees.  New tensors: the fixed buffers of logits() are not touched."""
+        replay sees.  New tensors: the fixed buffers of logits() are not touched.  spatial=True: x_a is the triple
+        (map, idx, flat) -- the crop's two tensors and the flat observation, stored copies included -- and the encoder's
+        tensors take gradients too (rollout.policy_conv_mlp)."""
         if self.network != "library":
             raise NotImplementedError("MaskedMLPPolicy.evaluate: network='library'")
         wa, wp = dict(self.weights_a), dict(self.weights_p)
         if self.value_head:  # (views made now, so that a gradient reaches the [hidden, 1] columns)
             wa["wv"], wp["wv"] = self.wav.view(-1), self.wpv.view(-1)
+        if self.spatial:
+            map_, idx, flat = x_a
+            return policy_conv_mlp(self.be, map_, idx, flat, self.conv_weights, x_p, wa, wp)
         return policy_mlp(self.be, x_a, x_p, wa, wp)
 
     def __call__(self, tensors, actions_a, actions_p):

@@ -778,6 +778,92 @@ int64_t aie_policy_mlp_backward_workspace_bytes(const aie_env* env, int64_t B, c
 int aie_policy_mlp_backward(aie_env* env, int64_t B, const aie_mlp_grad_class* agents, const aie_mlp_grad_class* planner,
                             void* d_workspace, int64_t workspace_bytes, void* stream);
 
+/* The one gradient aie_policy_mlp_backward leaves out, ONE launch: the gradient with respect to the first `ncols` columns
+ * of x, for a network in front of the MLP (aie_policy_conv_backward takes it as g_feat).  Per row r and column j < ncols,
+ *   g_x[r][j] = chain0 over k = 0 .. H-1 ascending of (dz1[r][k], W1[j][k])      (entry (r, j) at g_x[r * ld + j]),
+ * with dz1 READ FROM THE WORKSPACE where aie_policy_mlp_backward left it: the call is valid only directly behind
+ * aie_policy_mlp_backward with the same classes, B, workspace and stream (nothing else may have written the workspace in
+ * between).  It reads the workspace and w1 and writes exactly [rows, ncols] per class; the three launches of the backward
+ * are not touched and their outputs do not depend on whether this call follows.  A NULL g_x leaves that class out (both
+ * NULL: nothing is launched, AIE_OK).  Asynchronous on `stream`, no atomics, no allocation, capturable in a hipGraph.
+ * aie_policy_mlp_backward's refusals for the classes, B and the workspace; AIE_E_INVALID also for a g_x without its class,
+ * ncols outside 1 .. F, ld < ncols or a g_x that is not 4-byte aligned.  A refused call launches and writes nothing. */
+int aie_policy_mlp_input_grad(aie_env* env, int64_t B, const aie_mlp_grad_class* agents, const aie_mlp_grad_class* planner,
+                              void* d_workspace, int64_t workspace_bytes, float* d_g_x_a, int64_t ld_a, int32_t ncols_a,
+                              float* d_g_x_p, int64_t ld_p, int32_t ncols_p, void* stream);
+
+/* The convolutional encoder of the agents' egocentric crop, in front of the MLP, ONE launch: per row (one agent of one
+ * batch element; any row count >= 1) the crop's C_map float32 planes and two planes of int16 indices go through an
+ * embedding and two 3x3 stride-2 convolutions (AIE_CONV_F1, then AIE_CONV_F2 filters, no padding, ReLU each), and the
+ * flattened result is written beside a copy of the row's flat observation: x_out is then a legal x of
+ * aie_policy_mlp_forward with F = NF + F_flat.  This is the network of the reference's tutorials (num_conv 2, idx_emb_dim 4,
+ * input_emb_vocab 100 on the 11 x 11 crop: NF = 128).
+ * Per class record (aie_conv_class): map [rows][C_map][h][w] float32 with the row stride map_ld in floats; idx
+ * [rows][2][h][w] int16 with the row stride idx_ld in int16 elements (the arena's obs_a_world-map / obs_a_world-idx_map
+ * and a trajectory's stored copies differ only in these strides; map 4-byte, idx 2-byte aligned); emb [V, D], w1
+ * [9 C, F1], b1 [F1], w2 [9 F1, F2], b2 [F2] float32, contiguous, read where they lie at every launch; flat [rows, F_flat]
+ * with the leading dimension flat_ld (NULL: no copy, F_flat is then 0); x_out [rows] with the leading dimension x_ld.
+ * THE ARITHMETIC (csrc/aie_trainer_math.h states it once -- aie_conv_input_at, aie_conv1_out, aie_conv2_out -- and the CPU
+ * test compiles those helpers): all float32; chain and relu are aie_policy_mlp_forward's.
+ *   input     C = C_map + 2 D channels on h x w cells: channel c < C_map is the map's plane c; channel C_map + i D + d is
+ *             emb[v][d], v = idx[i][y][x] clamped into 0 .. V-1 (plane i = 0, 1): the reference's concatenation order;
+ *   conv1     oh1 = (h - 3) / 2 + 1, ow1 likewise; a1[oy][ox][f] = relu(chain(b1[f]; over k = (ky 3 + kx) C + c ascending of
+ *             (in[c][2 oy + ky][2 ox + kx], w1[k][f]))): w1 is Keras' HWIO kernel flattened, no permutation;
+ *   conv2     the same on a1 with its F1 channels: oh2 = (oh1 - 3) / 2 + 1, a2[oy][ox][f] with k = (ky 3 + kx) F1 + c;
+ *   features  Keras' Flatten of [oh2, ow2, F2]: x_out[r][(y ow2 + x) F2 + f] = a2[y][x][f]; NF = oh2 ow2 F2;
+ *   flat      x_out[r][NF + j] = flat[r][j], j < F_flat, the same bits.
+ * The device equals the helpers bit for bit: nothing is padded or split.  Exactly [rows, NF + F_flat] is written (with
+ * x_ld larger, the columns behind are left alone).  Two runs give the same bits.
+ * Supported: C_map 1 .. 32, D 1 .. 8, h and w 7 .. 15, V 1 .. 128; anything else (a full_observability crop of 25 x 25,
+ * say) is AIE_E_UNSUPPORTED and the message names the limit.  AIE_E_INVALID: rows < 1, a NULL among map, idx, the five
+ * weight pointers and x_out, strides smaller than a row, F_flat < 0 or > 1024, F_flat without flat or flat with F_flat 0,
+ * misaligned pointers.  Asynchronous on `stream`, no atomics, no allocation, capturable.  A refused call launches nothing.
+ * All scenarios: the environment only carries the device and the error text. */
+#define AIE_CONV_F1 16
+#define AIE_CONV_F2 32
+typedef struct aie_conv_class {
+  const float* map; int64_t map_ld;        /* [rows][C_map][h][w], row stride in floats */
+  const int16_t* idx; int64_t idx_ld;      /* [rows][2][h][w], row stride in int16 elements */
+  const float *emb, *w1, *b1, *w2, *b2;    /* [V,D] [9C,F1] [F1] [9F1,F2] [F2] */
+  const float* flat; int64_t flat_ld;      /* [rows, F_flat] or NULL */
+  float* x_out; int64_t x_ld;              /* [rows, >= NF + F_flat] */
+  int32_t C_map, D, h, w, V, F_flat;
+} aie_conv_class;
+int aie_policy_conv_forward(aie_env* env, int64_t rows, const aie_conv_class* cls, void* stream);
+
+/* The encoder's backward pass, THREE launches: the gradients of emb, w1, b1, w2 and b2 from g_feat, the gradient with
+ * respect to the NF feature columns (aie_policy_mlp_input_grad's output: entry (r, j) at g_feat[r * g_ld + j]).  net: as
+ * for the forward (flat, x_out and their strides are ignored).  Every entry of the five outputs, in the weights' shapes,
+ * is overwritten.  conv1's activations are recomputed.
+ * THE ARITHMETIC (csrc/aie_trainer_math.h: aie_conv_da1, aie_conv_dx, aie_conv_row_emb, aie_conv_backward_host).  Per row:
+ *   dz2[p][f] = a2[p][f] > 0 ? g_feat[p F2 + f] : 0;
+ *   da1[y][x][c] = chain0 over the conv2 outputs (oy, ox) ascending whose window holds (y, x) (ky = y - 2 oy, kx = x - 2 ox
+ *                  in 0 .. 2), and inside one over f = 0 .. F2-1 ascending, of (dz2[oy][ox][f], w2[(ky 3 + kx) F1 + c][f]);
+ *   dz1 = a1 > 0 ? da1 : 0;   dx[c][y][x], for the embedding's channels c >= C_map only: the same chain over conv1's
+ *   outputs and f = 0 .. F1-1 of (dz1[oy][ox][f], w1[(ky 3 + kx) C + c][f]);
+ *   e_r[v][d] = acc after acc = +0; for (i, y, x) ascending with clamped idx[i][y][x] == v: acc = acc + dx[C_map + i D + d][y][x].
+ * Across rows, in segments of AIE_MLP_BWD_SEG rows: partial_s(gw2[k][f]) = chain0 over the segment's rows ascending, and
+ * inside a row over conv2's outputs (oy, ox) ascending, of (a1[2 oy + ky][2 ox + kx][c], dz2[oy][ox][f]); gw1 likewise with
+ * the input and dz1 over conv1's outputs; a bias gradient is the same chain with the activation 1 (acc = acc + dz);
+ * partial_s(gemb[v][d]) = acc after acc = +0; for the segment's rows ascending: acc = acc + e_r[v][d].  An entry is the sum
+ * of its segment partials in float64, ascending, rounded to float32 once.  The order is a function of the row number and
+ * the constant only; no float atomics; two runs give the same bits, and the device equals the helpers bit for bit
+ * wherever no NaN occurs.
+ * d_workspace: device memory, 16-byte aligned, the call's own until it has run; it holds a1, dz1, dz2 and dx of every row
+ * and the segments' partials: floats = rows (2 P1 F1 + NF + 2 h w D) + ceil(rows / AIE_MLP_BWD_SEG) (((9 C + 1) F1 +
+ * (9 F1 + 1) F2 + V D) rounded up to 4), P1 = oh1 ow1, rounded up to a multiple of 64; times 4 bytes is what the
+ * workspace_bytes function returns (or the negative code of the call's own refusal).  The forward's refusals; AIE_E_INVALID
+ * also for a NULL g_feat or gradient pointer, g_ld < NF, and a workspace that is NULL, misaligned or too small.  A refused
+ * call launches and writes nothing.  Asynchronous on `stream`, no allocation, capturable in a hipGraph. */
+typedef struct aie_conv_grad_class {
+  aie_conv_class net;                      /* map, idx, strides, weights and shape as for the forward */
+  const float* g_feat; int64_t g_ld;       /* [rows, >= NF] */
+  float *gemb, *gw1, *gb1, *gw2, *gb2;     /* the weights' shapes */
+} aie_conv_grad_class;
+int64_t aie_policy_conv_backward_workspace_bytes(const aie_env* env, int64_t rows, const aie_conv_grad_class* cls);
+int aie_policy_conv_backward(aie_env* env, int64_t rows, const aie_conv_grad_class* cls, void* d_workspace,
+                             int64_t workspace_bytes, void* stream);
+
 /* Adam with gradient-norm clipping, in place, for up to two parameter groups (one per actor class), TWO launches for both
  * groups together: the last step of an update -- what a trainer otherwise writes as clip_grad_norm_ and a capturable
  * torch.optim.Adam, several dozen small launches over the sixteen tensors of aie_policy_mlp_backward (the reference's
